@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- BFGS iterations/sec on the synthetic n-dim convex quadratic (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one BFGS iteration (direction, More-Thuente line search, rank-2 inverse-Hessian update) on the
@@ -11,8 +11,15 @@ N > 1 runs configs[2]'s problem (n = 32768) with the rows of H and Q sharded ove
 half of its own block-rows (symmetric storage, the same kernels as on one GPU); per iteration the ranks exchange 8 KB of scalars
 per evaluation and the partial n-vectors of the accepted point and of the update pass over RCCL ("scaling": "strong" over
 N = 2,4,8).  If RCCL cannot be brought up the line carries no value and the run fails: nothing else is a measurement.
-Timing: 5 regions, each = reset to (x0, H = I), W untimed warm-up iterations, exactly K timed iterations
-between barrier + synchronize brackets, max over ranks; the MEDIAN region is reported (all five are in `timing.region_ms`).
+Timing: a region = reset to (x0, H = I), W untimed warm-up iterations, exactly K timed iterations
+between barrier + synchronize brackets, max over ranks.  A plain run times ONE region and prints the headline line; nothing else.
+--full adds everything else the benchmark measures: 5 regions with the MEDIAN one reported (all five in `timing.region_ms`), the
+CPU legs (`cpu_baseline`), the fixed cost of a qn_minimize call, the kernel-level profile pass (`roofline`), BASELINE.json's
+configs 4 / 5 and the bounded variants (`extra_configs`), and for N > 1 the exchange probe and the single-GPU scaling reference;
+the --no-* options switch single legs of --full off.
+--dump-outputs DIR writes what the timed path computed, as of its last timed step (the last region's): the iterate x, the
+iteration count k of the last qn_minimize call and, on one GPU up to n = 8192, a seeded sample of rows of the inverse Hessian, as
+float64 .npy files.  The inputs are a fixed function of the arguments, so two builds can be compared output for output.
 Prints ONE JSON line on rank 0.  The product path is libqn_hip.so (hand-written gfx950 kernels); the CPU
 oracle is used only for the `cpu_baseline` leg.  No GPU => hard failure, never a fallback.
 """
@@ -31,6 +38,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 SEED = 0x5EED0001
+DUMP_SEED = 0x5EED0002  # which rows of H --dump-outputs samples
+DUMP_H_ROWS = 256
 KAPPA = 1.0e3
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md:36); 6290 GB/s measured-achievable
 METRIC = "BFGS iterations/sec on n-dim convex quadratic (f64) at 1/2/4/8 MI355X"
@@ -485,6 +494,17 @@ def extra_config5(qn, ctx):
                                          "achieved": alg_h / (ms_h * 1e-3) / 1e9 if n_h else None}}}
 
 
+def dump_outputs(out_dir, solver, n, world):
+    """--dump-outputs: what a caller of the timed path receives after its last step, as float64 .npy files (a few MB at most)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "x.npy"), np.asarray(solver.x(), dtype=np.float64))
+    np.save(os.path.join(out_dir, "k.npy"), np.array([solver.k()], dtype=np.float64))
+    if world == 1 and n <= 8192:  # (the getter assembles all of H on the host: n^2 doubles)
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, DUMP_H_ROWS), replace=False))
+        np.save(os.path.join(out_dir, "inv_hessian_rows.npy"), np.asarray(solver.approx_inv_hessian()[rows], dtype=np.float64))
+        np.save(os.path.join(out_dir, "inv_hessian_row_index.npy"), rows.astype(np.float64))
+
+
 def main():
     if len(sys.argv) in (4, 5, 6) and sys.argv[1] == "--cpu-baseline-child":  # (no torch, no GPU: see cpu_baseline)
         print(json.dumps(cpu_baseline_child(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]) if len(sys.argv) >= 5 else None,
@@ -504,6 +524,11 @@ def main():
                     help="N > 1: skip the single-GPU run of the same workload on rank 0 (strong-scaling denominator)")
     ap.add_argument("--tiling", default=None, help="rows_per_block,col_splits")
     ap.add_argument("--sync-mode", type=int, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: five timed regions (median), CPU legs, per-call cost, "
+                         "profile pass / roofline, extra configs, exchange probe and scaling reference (N > 1)")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -517,9 +542,9 @@ def main():
 
     # The CPU legs run FIRST, in a child, to completion: this process has not loaded torch, HIP or the library yet (see cpu_baseline).
     n_headline = args.dim or (4096 if world == 1 else 32768)
-    want_extra = world == 1 and args.dim is None and not args.no_extra_configs
+    want_extra = args.full and world == 1 and args.dim is None and not args.no_extra_configs
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(n_headline, 200 if n_headline <= 4096 else 4, extra=want_extra)
 
     import torch  # device plumbing + torch.distributed rendezvous only
@@ -577,7 +602,8 @@ def main():
     # on this node -- 8 KB of per-workgroup scalars (one per evaluation), n doubles (q of the accepted point), 2 n doubles ([u, v] of the update
     # pass) per rank.  DESIGN section 5 budgets ~20 us for a small one without ever having run one between devices.
     xprobe = None
-    if world > 1:
+    want_tv = os.environ.get("QN_BENCH_TRIAL_VECTOR", "0")
+    if world > 1 and (args.full or want_tv == "auto"):
         try:
             xprobe = {"scalars_8KB": ctx.exchange_probe(1024), "n_vector": ctx.exchange_probe(n), "two_n_vectors": ctx.exchange_probe(2 * n)}
         except Exception as e:  # noqa: BLE001 -- the probe never loses the bench line
@@ -595,13 +621,14 @@ def main():
             ok = [r for r in per_rank if isinstance(r, dict) and "error" not in r]
             if ok and len(ok) == world:
                 tv["recommended"] = bool(max(r["n_vector"]["median_us"] for r in ok) < 2.0 * max(r["scalars_8KB"]["median_us"] for r in ok))
-            want = os.environ.get("QN_BENCH_TRIAL_VECTOR", "0")
-            if want == "1" or (want == "auto" and tv["recommended"]):
+            if want_tv == "1" or (want_tv == "auto" and tv["recommended"]):
                 ctx.set_trial_vector_exchange(True)
                 tv["used"] = True
         except Exception as e:  # noqa: BLE001
             tv["error"] = repr(e)
         xprobe["trial_vector_exchange"] = tv
+    elif world > 1 and want_tv == "1":
+        ctx.set_trial_vector_exchange(True)
 
     diag, b, x0 = synth_inputs(n)
     obj = qn.Quadratic.synthetic(n, SEED, diag, b, ctx=ctx)  # Q is generated shard-locally on the device
@@ -618,9 +645,9 @@ def main():
         if world > 1:
             dist.barrier()
 
-    # median of 5 timed regions.  Each region is the same thing: back to (x0, H = I), `warmup` untimed iterations,
-    # then EXACTLY `steps` timed iterations of the same solve between barrier + synchronize brackets (max over ranks).
-    regions = 5
+    # one timed region, or (--full) the median of 5.  Each region is the same thing: back to (x0, H = I), `warmup` untimed
+    # iterations, then EXACTLY `steps` timed iterations of the same solve between barrier + synchronize brackets (max over ranks).
+    regions = 5 if args.full else 1
     region_s, region_acc = [], []
     for _ in range(regions):
         solver.reset(x0)
@@ -650,6 +677,8 @@ def main():
     evals, calls = acc["total_oracle_evals"], acc["total_oracle_calls"]
     h_bytes, obj_bytes = acc["total_h_bytes"], acc["total_obj_bytes"]
     its = steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, solver, n, world)  # (every region computes the same thing: this is the last one's)
 
     # fixed cost of one qn_minimize call (entry, the first launch from an idle queue, the last launch's report, the return): wall time
     # of warm calls of 4 and of 24 iterations, the same run continued, medians of 7 -- two points of a straight line whose slope is an
@@ -669,12 +698,14 @@ def main():
             ts.append(time.perf_counter() - t0)
         ts.sort()
         return 1e3 * ts[len(ts) // 2]
-    t4, t24 = timed_call(4), timed_call(24)
-    per_call_fixed_ms = (t4 - 4.0 * (t24 - t4) / 20.0) if (t4 is not None and t24 is not None) else None  # (a negative intercept is reported as it is)
+    per_call_fixed_ms = None
+    if args.full:
+        t4, t24 = timed_call(4), timed_call(24)
+        per_call_fixed_ms = (t4 - 4.0 * (t24 - t4) / 20.0) if (t4 is not None and t24 is not None) else None  # (a negative intercept is reported as it is)
 
     # kernel-level roofline: same workload again with every launch bracketed by HIP events on the solver's stream
     roofline = None
-    if not args.no_profile_pass:
+    if args.full and not args.no_profile_pass:
         prof_steps = min(steps, 50)
         solver.reset(x0)
         solver.set_profiling(True)
@@ -828,7 +859,7 @@ def main():
                        "n": n, "line_search": args.ls, "tol": 1e-10, "parallelism": f"row-shard x{world}",
                        "exchange": "none" if world == 1 else ("host-staged gloo, stream-ordered (rehearsal)" if host_exchange else "rccl all-gather"),
                        **({"rccl_error": rccl_error} if rccl_error else {})},
-            "timing": {"regions": regions, "reported": "median region", "region_ms": [1e3 * t for t in region_s],
+            "timing": {"regions": regions, "reported": "median region" if regions > 1 else "the one region", "region_ms": [1e3 * t for t in region_s],
                        "each_region": f"reset to (x0, H = I), {warmup} untimed iterations, then {steps} timed iterations",
                        "qn_minimize_calls_in_region": acc["total_minimize_calls"],
                        "per_call_fixed_ms": per_call_fixed_ms,
@@ -847,10 +878,10 @@ def main():
                                      "launches_per_iteration": acc["launches"] / steps,
                                      "collectives_of_n_vectors": acc["total_xchg_vector"], "collectives_of_scalars": acc["total_xchg_scalar"],
                                      "collectives_per_iteration": {"n_vectors": acc["total_xchg_vector"] / steps, "scalars_8KB": acc["total_xchg_scalar"] / steps},
-                                     "note": "counters are the solver's cumulative totals differenced around the median timed region"},
+                                     "note": "counters are the solver's cumulative totals differenced around the reported timed region"},
             "roofline": roofline,
         }
-        if world > 1:
+        if xprobe is not None:
             out["multi_gpu_readiness"] = collectives_share(xprobe, acc["total_xchg_scalar"] / steps, acc["total_xchg_vector"] / steps, 1e3 * elapsed / steps)
         if cpu is not None:
             out["cpu_baseline"] = cpu.get("config2", cpu) if "error" not in cpu else cpu
@@ -870,7 +901,7 @@ def main():
                     if isinstance(extra.get(name), dict):
                         extra[name]["cpu_baseline"] = cpu.get(key)
             out["extra_configs"] = extra
-        if world > 1 and not args.no_scaling_ref:
+        if args.full and world > 1 and not args.no_scaling_ref:
             # strong-scaling denominator: the SAME workload unsharded on rank 0's GPU alone (N = 1 of the default run
             # is configs[1], a different problem size, so value(N)/value(1) across default runs is not an efficiency)
             try:

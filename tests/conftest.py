@@ -7,6 +7,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+# torch before anything loads libqn_hip.so, whichever tests run first: torch's HIP libraries ask for `libamdhip64.so` by file name
+# and bring their own copy into a process whose libamdhip64.so.7 came first from libqn_hip.so's link -- two HIP runtimes over one
+# HSA runtime, and the library's hipGetDeviceCount then finds no device.  Loaded first, torch's runtime is the one the library
+# binds to, as in bench.py and in a `-m gpu` session (the device check below imports torch before any test runs).
+try:
+    import torch  # noqa: F401
+except ImportError:
+    pass
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")

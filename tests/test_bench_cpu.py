@@ -103,3 +103,39 @@ def test_collectives_share_estimates_from_probe_and_counts():
     assert abs(out["estimated_fraction_of_ms_per_step"] - 114.0 / 500.0) < 1e-12
     bad = bench.collectives_share({"ranks": 2, "exchange": "rccl", "per_rank": [{"error": "x"}, {"error": "y"}]}, 2.0, 2.0, 0.5)
     assert "error" in bad and "estimated_fraction_of_ms_per_step" not in bad
+
+
+def test_dump_outputs_writes_float64_npy_of_what_a_caller_receives(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): the iterate, k and a seeded sample of rows of the inverse Hessian as float64 .npy files --
+    the same rows on every run, well inside 64 MB; with N > 1 ranks the iterate and k only (assembling H would be a collective)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class Fake:
+        def __init__(self, n):
+            rng = np.random.default_rng(1)
+            self.xv, self.h = rng.standard_normal(n), rng.standard_normal((n, n))
+
+        def x(self):
+            return self.xv.copy()
+
+        def k(self):
+            return 17
+
+        def approx_inv_hessian(self):
+            return self.h.copy()
+
+    n = 300
+    f = Fake(n)
+    bench.dump_outputs(str(tmp_path / "a"), f, n, 1)
+    bench.dump_outputs(str(tmp_path / "b"), f, n, 1)
+    a = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(a) == ["inv_hessian_row_index.npy", "inv_hessian_rows.npy", "k.npy", "x.npy"]
+    assert all(v.dtype == np.float64 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert np.array_equal(a["x.npy"], f.xv) and a["k.npy"].tolist() == [17.0]
+    rows = a["inv_hessian_row_index.npy"].astype(np.int64)
+    assert len(rows) == len(set(rows.tolist())) == bench.DUMP_H_ROWS and np.array_equal(a["inv_hessian_rows.npy"], f.h[rows])
+    assert all(np.array_equal(np.load(tmp_path / "b" / name), v) for name, v in a.items())
+    bench.dump_outputs(str(tmp_path / "c"), f, n, 2)
+    assert sorted(p.name for p in (tmp_path / "c").iterdir()) == ["k.npy", "x.npy"]

@@ -4,7 +4,7 @@
 a=$1; b=$2; shift 2
 for rep in 1 2 3; do
   for lib in $a $b; do
-    v=$(QN_HIP_LIB=$PWD/optimization-solvers_amd/lib/$lib python bench.py --no-cpu-baseline "$@" 2>/dev/null | python -c "
+    v=$(QN_HIP_LIB=$PWD/optimization-solvers_amd/lib/$lib python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d.get('roofline')
 line='%.1f it/s  %.2f us' % (d['value'], 1e3*d['ms_per_step'])

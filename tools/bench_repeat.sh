@@ -5,7 +5,7 @@ tag=${1:-rep}; n=${2:-24}
 out=gpurun_out/$tag; mkdir -p $out
 : > $out/values.txt
 for i in $(seq 1 $n); do
-  python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-configs --no-profile-pass > $out/line.json 2> $out/line.err || { echo "run $i failed"; tail -3 $out/line.err; exit 1; }
+  python bench.py --gpus 1 --steps 20 --warmup 5 > $out/line.json 2> $out/line.err || { echo "run $i failed"; tail -3 $out/line.err; exit 1; }
   python3 -c "import json,sys; d=json.loads(open('$out/line.json').read().strip().splitlines()[-1]); print('%d %.1f %.3f' % ($i, d['value'], d['ms_per_step']*1e3))" | tee -a $out/values.txt
 done
 python3 - $out/values.txt <<'PY'

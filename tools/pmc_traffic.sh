@@ -6,8 +6,8 @@ out=gpurun_out/$tag
 repo="${GRAFT_REPO_ROOT:-$(git rev-parse --show-toplevel 2>/dev/null || pwd)}"
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$repo"
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/fetch -o f -- python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-profile-pass > /dev/null 2> $out/fetch.err
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/write -o w -- python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-profile-pass > /dev/null 2> $out/write.err
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $out/fetch -o f -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-profile-pass > /dev/null 2> $out/fetch.err
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $out/write -o w -- python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline --no-profile-pass > /dev/null 2> $out/write.err
 python3 - "$out" <<'PY'
 import csv, statistics, json, sys, glob
 out = sys.argv[1]

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_REPO_ROOT:-$OLDPWD}"
 for lib in $libs; do
   out=gpurun_out/prof_ab/$lib
   rm -rf $out; mkdir -p $out
-  QN_HIP_LIB=$PWD/optimization-solvers_amd/lib/$lib rocprofv3 --kernel-trace --stats --output-format csv -d $out -o p -- python3 bench.py --steps 200 --no-cpu-baseline --no-profile-pass "$@" > $out/bench.json 2> $out/err.txt
+  QN_HIP_LIB=$PWD/optimization-solvers_amd/lib/$lib rocprofv3 --kernel-trace --stats --output-format csv -d $out -o p -- python3 bench.py --full --steps 200 --no-cpu-baseline --no-profile-pass "$@" > $out/bench.json 2> $out/err.txt
   python3 - "$lib" "$out" <<'PY'
 import sys, csv, glob, json
 lib, out = sys.argv[1], sys.argv[2]

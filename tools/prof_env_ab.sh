@@ -15,7 +15,7 @@ for spec in "${specs[@]}"; do
   rm -rf $out; mkdir -p $out
   (
     IFS=','; for kv in $envs; do [ -n "$kv" ] && export "$kv"; done; unset IFS
-    rocprofv3 --kernel-trace --stats --output-format csv -d $out -o p -- python3 bench.py --steps 200 --no-cpu-baseline --no-profile-pass --no-extra-configs "$@" > $out/bench.json 2> $out/err.txt
+    rocprofv3 --kernel-trace --stats --output-format csv -d $out -o p -- python3 bench.py --full --steps 200 --no-cpu-baseline --no-profile-pass --no-extra-configs "$@" > $out/bench.json 2> $out/err.txt
   )
   python3 - "$tag.$rep" "$out" <<'PY'
 import sys, csv, glob, json

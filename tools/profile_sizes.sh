@@ -8,12 +8,12 @@ repo="${GRAFT_REPO_ROOT:-$(pwd)}"
 cd /tmp && export TMPDIR=/tmp && cd "$repo"
 for n in $sizes; do
   steps=$([ $n -ge 16384 ] && echo 30 || echo 100)
-  python3 bench.py --dim $n --steps $steps --no-cpu-baseline > $out/bench_n$n.json 2> $out/bench_n$n.err
+  python3 bench.py --full --dim $n --steps $steps --no-cpu-baseline > $out/bench_n$n.json 2> $out/bench_n$n.err
   rm -rf $out/prof_n$n; mkdir -p $out/prof_n$n
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_n$n -o p -- python3 bench.py --dim $n --steps $steps --no-cpu-baseline --no-profile-pass > $out/bench_under_rocprof_n$n.json 2> $out/rocprof_n$n.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_n$n -o p -- python3 bench.py --full --dim $n --steps $steps --no-cpu-baseline --no-profile-pass > $out/bench_under_rocprof_n$n.json 2> $out/rocprof_n$n.err
   for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf $out/pmc_${c}_n$n; mkdir -p $out/pmc_${c}_n$n
-    rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/pmc_${c}_n$n -o c -- python3 bench.py --dim $n --steps 10 --warmup 2 --no-cpu-baseline --no-profile-pass > /dev/null 2> $out/pmc_${c}_n$n.err
+    rocprofv3 --pmc $c --kernel-trace --output-format csv -d $out/pmc_${c}_n$n -o c -- python3 bench.py --full --dim $n --steps 10 --warmup 2 --no-cpu-baseline --no-profile-pass > /dev/null 2> $out/pmc_${c}_n$n.err
   done
   python3 - "$out" "$n" <<'PY'
 import csv, glob, json, statistics, sys

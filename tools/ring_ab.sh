@@ -9,7 +9,7 @@ for rep in $(seq 1 $reps); do
   for ring in 0 1; do
     out=gpurun_out/ring_ab/r${ring}_$rep
     rm -rf $out; mkdir -p $out
-    QN_S2_RING=$ring rocprofv3 --kernel-trace --stats --output-format csv -d $out -o p -- python3 bench.py --steps 200 --no-cpu-baseline --no-profile-pass --no-extra-configs "$@" > $out/bench.json 2> $out/err.txt
+    QN_S2_RING=$ring rocprofv3 --kernel-trace --stats --output-format csv -d $out -o p -- python3 bench.py --full --steps 200 --no-cpu-baseline --no-profile-pass --no-extra-configs "$@" > $out/bench.json 2> $out/err.txt
     python3 - "$ring" "$out" <<'PY'
 import sys, csv, glob, json
 ring, out = sys.argv[1], sys.argv[2]

@@ -5,7 +5,7 @@ repo="${GRAFT_REPO_ROOT:-$PWD}"
 cd /tmp && export TMPDIR=/tmp && cd "$repo"
 for rep in $(seq 1 $reps); do for lib in $libs; do
   out=gpurun_out/ring_libs/${lib}_$rep; rm -rf $out; mkdir -p $out
-  QN_S2_RING=${RING:-1} QN_HIP_LIB=$PWD/optimization-solvers_amd/lib/$lib rocprofv3 --kernel-trace --stats --output-format csv -d $out -o p -- python3 bench.py --steps 200 --no-cpu-baseline --no-profile-pass --no-extra-configs > $out/bench.json 2> $out/err.txt
+  QN_S2_RING=${RING:-1} QN_HIP_LIB=$PWD/optimization-solvers_amd/lib/$lib rocprofv3 --kernel-trace --stats --output-format csv -d $out -o p -- python3 bench.py --full --steps 200 --no-cpu-baseline --no-profile-pass --no-extra-configs > $out/bench.json 2> $out/err.txt
   python3 - "$lib" "$out" <<'PY'
 import sys, csv, glob, json
 lib, out = sys.argv[1], sys.argv[2]

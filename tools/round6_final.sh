@@ -6,11 +6,11 @@ out=gpurun_out/$tag
 repo="${GRAFT_REPO_ROOT:-$(git rev-parse --show-toplevel 2>/dev/null || pwd)}"
 mkdir -p $out
 for i in 1 2 3; do
-  ( time python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_steps20_$i.json 2> $out/bench_steps20_$i.err ) 2> $out/bench_steps20_$i.time || echo "bench20 $i failed"
+  ( time python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_steps20_$i.json 2> $out/bench_steps20_$i.err ) 2> $out/bench_steps20_$i.time || echo "bench20 $i failed"
 done
-python bench.py --no-extra-configs > $out/bench_default.json 2> $out/bench_default.err || echo "bench default failed"
+python bench.py --full --no-extra-configs > $out/bench_default.json 2> $out/bench_default.err || echo "bench default failed"
 cd /tmp && export TMPDIR=/tmp && cd "$repo"
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o prof -- python3 bench.py --steps 200 --no-cpu-baseline --no-profile-pass --no-extra-configs > $out/bench_under_rocprof.json 2> $out/rocprof.err || echo "rocprof failed"
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof -o prof -- python3 bench.py --full --steps 200 --no-cpu-baseline --no-profile-pass --no-extra-configs > $out/bench_under_rocprof.json 2> $out/rocprof.err || echo "rocprof failed"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/c5 -o c5 -- python3 tools/bench_config5.py 16384 20 > $out/c5_rocprof.json 2> $out/c5_rocprof.err || echo "rocprof c5 failed"
 bash tools/pmc_traffic.sh $tag/pmc > $out/pmc.txt 2>&1
 python3 - "$out" <<'PY'
