@@ -104,7 +104,8 @@ void* qn_context_stream(qn_context* ctx); /* hipStream_t */
  *   QN_LS_BACKTRACKING: BackTracking       (backtracking.rs:3-58)
  * ------------------------------------------------------------------------------------------- */
 enum { QN_LS_MORETHUENTE = 0, QN_LS_BACKTRACKING = 1,
-       QN_LS_MORETHUENTE_B = 2 /* MoreThuenteB, morethuente_b.rs */, QN_LS_BACKTRACKING_B = 3 /* BackTrackingB, backtracking_b.rs */ };
+       QN_LS_MORETHUENTE_B = 2 /* MoreThuenteB, morethuente_b.rs */, QN_LS_BACKTRACKING_B = 3 /* BackTrackingB, backtracking_b.rs */,
+       QN_LS_GLL_QUADRATIC = 4 /* GLLQuadratic, gll_quadratic.rs: the non-monotone search of Grippo, Lampariello, Lucidi; QN_SPG / QN_PROJECTED_GRADIENT only */ };
 typedef struct {
     int32_t kind;
     int32_t _pad;
@@ -115,6 +116,11 @@ typedef struct {
     const double* lower_bound_host;
     const double* upper_bound_host;
 } qn_linesearch;
+/* GLLQuadratic (gll_quadratic.rs:3-10) travels in the fields above, the struct keeps its layout: kind = QN_LS_GLL_QUADRATIC, c1 = c1,
+ * _pad = m (the look-back, :6), delta_min = sigma1, delta_max = sigma2.  m = 0 or m > 64 makes qn_minimize return QN_ERROR_INPUT_PARAMS: the
+ * history f_previous (:7) is a fixed ring of 64 values on the device.  ONE DIFFERENCE FROM THE REFERENCE: this struct is plain data passed
+ * by value, so the history belongs to the SOLVER, not to the line-search value -- it survives successive qn_minimize calls on one solver
+ * (as the reference's survives successive minimize calls with one GLLQuadratic), and qn_solver_reset empties it. */
 
 void qn_morethuente_default(qn_linesearch* ls);                      /* MoreThuente::default, morethuente.rs:16-28 */
 int qn_morethuente_with_deltas(qn_linesearch* ls, double dmin, double d, double dmax); /* :31-41 */
@@ -127,6 +133,8 @@ void qn_morethuente_b_new(qn_linesearch* ls);                          /* MoreTh
 void qn_backtracking_b_new(qn_linesearch* ls, double c1, double beta, const double* lower_bound_host, const double* upper_bound_host); /* backtracking_b.rs:10-23 */
 void qn_linesearch_with_lower_bound(qn_linesearch* ls, const double* lower_bound_host); /* morethuente_b.rs:32-35 */
 void qn_linesearch_with_upper_bound(qn_linesearch* ls, const double* upper_bound_host); /* morethuente_b.rs:36-39 */
+void qn_gll_quadratic_new(qn_linesearch* ls, double c1, size_t m);                      /* GLLQuadratic::new, gll_quadratic.rs:13-23: sigma1 = 0.1, sigma2 = 0.9 */
+void qn_gll_quadratic_with_sigmas(qn_linesearch* ls, double sigma1, double sigma2);     /* :24-28 */
 
 /* ---------------------------------------------------------------------------------------------
  * Oracle: `impl FnMut(&DVector<f64>) -> FuncEvalMultivariate` (ls_solver.rs:69, func_eval.rs:4-41).
@@ -179,7 +187,18 @@ int qn_objective_get_rows(qn_objective* obj, size_t row0, size_t nrows, double* 
  * Solvers: BFGS (bfgs.rs:4-127), DFP (dfp.rs), GradientDescent (gradient_descent.rs:7-82), Newton (newton/mod.rs).
  * ------------------------------------------------------------------------------------------- */
 enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton/mod.rs:8-69, SURVEY.md 8(f) row f2 */,
-       QN_SR1 = 4 /* sr1_b.rs (row f4; SR1B once qn_solver_set_bounds is called) */ };
+       QN_SR1 = 4 /* sr1_b.rs (row f4; SR1B once qn_solver_set_bounds is called) */,
+       /* The first-order family: O(n) state (no inverse Hessian), one rank, every vector operation on a device-wide grid (QN_PATH_VECTOR).
+        * Line searches: QN_LS_GLL_QUADRATIC, QN_LS_BACKTRACKING, QN_LS_BACKTRACKING_B (More-Thuente: QN_ERROR_INPUT_PARAMS).  The box is
+        * qn_solver_set_bounds' (-inf, +inf without it).  trace: gnorm = ||projected gradient||_inf (ls_solver.rs:121-133), s_norm = ||s|| (SPG).
+        * qn_solver_reset projects x0 onto the box, as ::new does (spg.rs:35).  qn_solver_compute_direction on these methods is a HOST utility for
+        * bindings (it downloads x and the box and forms P(x - lambda g) - x in a host loop); qn_minimize forms its directions on the device.
+        * Device closures and device objectives are enqueued a whole iteration at a time, ahead of the device-side decisions: the LAST batch of a
+        * run that ends at its loop top (convergence or an out-of-domain f) still evaluates once at a stale point.  That evaluation is not used
+        * and not counted in qn_stats; a device closure that counts its own invocations sees one more than oracle_evals reports for such a run
+        * (none for a run that ends on the iteration cap, none for SPG's constructor evaluation).  Host closures are called only for points the solver asked for. */
+       QN_SPG = 5 /* SpectralProjectedGradient, steepest_descent/spg.rs */,
+       QN_PROJECTED_GRADIENT = 6 /* ProjectedGradientDescent, steepest_descent/projected_gradient_descent.rs */ };
 typedef struct qn_solver qn_solver;
 
 /* BFGS::new(tol, x0) / DFP::new / GradientDescent::new(grad_tol, x0): H = I (no identity copy is kept) */
@@ -188,6 +207,12 @@ void qn_solver_destroy(qn_solver* s);
 /* Row f4: BFGSB / DFPB / SR1B (bfgs_b.rs:43-77, dfp_b.rs, sr1_b.rs): box bounds on a BFGS / DFP / SR1 solver.  The current x
  * is projected (bfgs_b.rs:49) and every direction becomes P(x - H g) - x (bfgs_b.rs:72-75). */
 int qn_solver_set_bounds(qn_solver* s, const double* lower_bound_host, const double* upper_bound_host);
+/* QN_SPG: with_lambdas (spg.rs:23-27; defaults 1e-3 / 1e3, :36-37; the current lambda is not clamped again).  Other methods: QN_ERROR_INPUT_PARAMS. */
+int qn_solver_set_spg_lambdas(qn_solver* s, double lambda_min, double lambda_max);
+/* QN_SPG: lambda(), the Barzilai-Borwein scalar.  SpectralProjectedGradient::new calls the oracle (spg.rs:40-46); qn_solver_create has none, so
+ * the first qn_minimize after create / reset makes that call (counted in oracle_calls; with memoize = 1 the point is evaluated once):
+ * is_some = 0 until then.  A qn_minimize with max_iter_solver = 0 does just that and returns QN_MAX_ITER_REACHED. */
+int qn_solver_spg_lambda(qn_solver* s, double* out, int* is_some);
 /* back to the state right after BFGS::new(tol, x0): x = x0, H = I, k = 0, s_norm = y_norm = None */
 int qn_solver_reset(qn_solver* s, const double* x0_host);
 
@@ -287,6 +312,7 @@ typedef struct {
 #define QN_PATH_SYM2 16u       /* QN_PATH_SYM with the solver's decisions taken in every kernel's prologue (5 launches per iteration) */
 #define QN_PATH_TILES1 32u     /* QN_PATH_SYM2 whose update pass streams H through the first-generation tile kernel (one workgroup per tile) behind a
                                   one-workgroup launch that runs the state machine: H's share past the Infinity Cache, and the log-sum-exp objective */
+#define QN_PATH_VECTOR 64u     /* the first-order family's device-wide vector kernels (csrc/qn_vec.hip.h): QN_SPG, QN_PROJECTED_GRADIENT */
 int qn_solver_get_stats(qn_solver* s, qn_stats* out);
 /* profiling != 0: bracket every launch with HIP events on the solver's stream (slower; for roofline reports) */
 int qn_solver_set_profiling(qn_solver* s, int on);

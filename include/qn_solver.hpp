@@ -137,6 +137,33 @@ class BackTracking {
     qn_linesearch& ffi() { return s_; }
 };
 
+// gll_quadratic.rs: the non-monotone search for SpectralProjectedGradient / ProjectedGradientDescent (the history lives in the solver)
+class GLLQuadratic {
+    qn_linesearch s_;
+  public:
+    template <class Oracle>
+    Floating compute_step_len(const DVector& x_k, const FuncEvalMultivariate& eval_x_k, const DVector& direction_k, Oracle&& oracle, size_t max_iter) {
+        return optimization_solvers::compute_step_len(*this, x_k, eval_x_k, direction_k, oracle, max_iter);
+    }
+    GLLQuadratic(Floating c1, size_t m) { qn_gll_quadratic_new(&s_, c1, m); }
+    static GLLQuadratic new_(Floating c1, size_t m) { return GLLQuadratic(c1, m); }
+    GLLQuadratic with_sigmas(Floating sigma1, Floating sigma2) && { qn_gll_quadratic_with_sigmas(&s_, sigma1, sigma2); return *this; }
+    Floating c1() const { return s_.c1; }
+    qn_linesearch& ffi() { return s_; }
+};
+
+// backtracking_b.rs: projected trial points; keeps its own copies of the box
+class BackTrackingB {
+    qn_linesearch s_;
+    DVector lb_, ub_;
+  public:
+    BackTrackingB(Floating c1, Floating beta, DVector lower_bound, DVector upper_bound) : lb_(std::move(lower_bound)), ub_(std::move(upper_bound)) {
+        qn_backtracking_b_new(&s_, c1, beta, lb_.data(), ub_.data());
+    }
+    BackTrackingB(const BackTrackingB&) = delete; // (the struct points into lb_ / ub_)
+    qn_linesearch& ffi() { return s_; }
+};
+
 // a device-resident objective (built-in quadratic f = 1/2 x'Qx - b'x)
 class Quadratic {
     qn_objective* h_ = nullptr;
@@ -168,6 +195,7 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
     LineSearchSolver(Floating tol, const DVector& x0, Context& ctx = Context::default_context()) : n_(x0.size()) {
         check(qn_solver_create(ctx.handle(), METHOD, tol, x0.data(), x0.size(), &h_));
     }
+    qn_solver* handle() const { return h_; }
     static Self new_(Floating tol, const DVector& x0) { return Self(tol, x0); }
     LineSearchSolver(const Self&) = delete;
     LineSearchSolver(Self&& o) noexcept : h_(o.h_), n_(o.n_) { o.h_ = nullptr; }
@@ -235,5 +263,68 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
 using BFGS = LineSearchSolver<QN_BFGS>;                       // quasi_newton/bfgs.rs
 using DFP = LineSearchSolver<QN_DFP>;                         // quasi_newton/dfp.rs
 using GradientDescent = LineSearchSolver<QN_GRADIENT_DESCENT>; // steepest_descent/gradient_descent.rs
+
+// The bounded first-order solvers (O(n) device memory): the box, projected_gradient (ls_solver.rs:121-133), has_converged on its
+// infinity norm (spg.rs:89-92, projected_gradient_descent.rs:76-83).
+template <int METHOD>
+class ProjectedSolver : public LineSearchSolver<METHOD> {
+    DVector lb_, ub_;
+  public:
+    ProjectedSolver(Floating grad_tol, const DVector& x0, DVector lower_bound, DVector upper_bound, Context& ctx = Context::default_context())
+        : LineSearchSolver<METHOD>(grad_tol, x0, ctx), lb_(std::move(lower_bound)), ub_(std::move(upper_bound)) {
+        check(qn_solver_set_bounds(this->handle(), lb_.data(), ub_.data())); // x0.box_projection(..), spg.rs:35
+    }
+    Floating grad_tol() const { return this->tol(); }
+    const DVector& lower_bound() const { return lb_; }
+    const DVector& upper_bound() const { return ub_; }
+    DVector projected_gradient(const FuncEvalMultivariate& eval) const {
+        DVector pg = eval.g();
+        const DVector& x = this->x();
+        for (size_t i = 0; i < pg.size(); ++i)
+            if ((x[i] == lb_[i] && pg[i] > 0.0) || (x[i] == ub_[i] && pg[i] < 0.0)) pg[i] = 0.0;
+        return pg;
+    }
+    bool has_converged(const FuncEvalMultivariate& eval) const {
+        Floating acc = -INFINITY;
+        for (Floating v : projected_gradient(eval)) acc = std::fmax(std::fabs(v), acc);
+        return acc < this->tol();
+    }
+    DVector compute_direction(const FuncEvalMultivariate& eval) const { // spg.rs:76-86 / projected_gradient_descent.rs:51-60
+        DVector d(eval.g().size());
+        check(qn_solver_compute_direction(this->handle(), eval.g().data(), d.data()));
+        return d;
+    }
+};
+
+// steepest_descent/projected_gradient_descent.rs: new(grad_tol, x0, lower_bound, upper_bound)
+class ProjectedGradientDescent : public ProjectedSolver<QN_PROJECTED_GRADIENT> {
+  public:
+    using ProjectedSolver<QN_PROJECTED_GRADIENT>::ProjectedSolver;
+    static ProjectedGradientDescent new_(Floating grad_tol, const DVector& x0, DVector lb, DVector ub) {
+        return ProjectedGradientDescent(grad_tol, x0, std::move(lb), std::move(ub));
+    }
+};
+
+// steepest_descent/spg.rs: new(grad_tol, x0, &mut oracle, lower_bound, upper_bound) -- the constructor calls the oracle for lambda0 (:40-46)
+class SpectralProjectedGradient : public ProjectedSolver<QN_SPG> {
+  public:
+    template <class Oracle>
+    SpectralProjectedGradient(Floating grad_tol, const DVector& x0, Oracle&& oracle, DVector lower_bound, DVector upper_bound,
+                              Context& ctx = Context::default_context())
+        : ProjectedSolver<QN_SPG>(grad_tol, x0, std::move(lower_bound), std::move(upper_bound), ctx) {
+        GLLQuadratic ls(1e-4, 1);
+        Result r = this->minimize(ls, oracle, 0, 0); // no iteration: the constructor's evaluation only
+        if (r.is_err() && r.unwrap_err().kind != SolverError::MaxIterReached) r.unwrap();
+    }
+    template <class Oracle>
+    static SpectralProjectedGradient new_(Floating grad_tol, const DVector& x0, Oracle&& oracle, DVector lb, DVector ub) {
+        return SpectralProjectedGradient(grad_tol, x0, oracle, std::move(lb), std::move(ub));
+    }
+    SpectralProjectedGradient with_lambdas(Floating lambda_min, Floating lambda_max) && { // spg.rs:23-27
+        check(qn_solver_set_spg_lambdas(this->handle(), lambda_min, lambda_max));
+        return std::move(*this);
+    }
+    Floating lambda() const { Floating v = 0; int some = 0; check(qn_solver_spg_lambda(this->handle(), &v, &some)); return v; }
+};
 
 } // namespace optimization_solvers

@@ -7,9 +7,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("QN_HIP_LIB") or os.path.join(_HERE, "lib", "libqn_hip.so")  # QN_HIP_LIB: diagnostic builds
 
 OK, MAX_ITER_REACHED, OUT_OF_DOMAIN, ERROR_INPUT_PARAMS, ABNORMAL_TERMINATION = range(5)
-LS_MORETHUENTE, LS_BACKTRACKING, LS_MORETHUENTE_B, LS_BACKTRACKING_B = 0, 1, 2, 3
+LS_MORETHUENTE, LS_BACKTRACKING, LS_MORETHUENTE_B, LS_BACKTRACKING_B, LS_GLL_QUADRATIC = 0, 1, 2, 3, 4
 ORACLE_HOST, ORACLE_DEVICE_FN, ORACLE_OBJECTIVE = 0, 1, 2
-BFGS, DFP, GRADIENT_DESCENT, NEWTON, SR1 = 0, 1, 2, 3, 4
+BFGS, DFP, GRADIENT_DESCENT, NEWTON, SR1, SPG, PROJECTED_GRADIENT = 0, 1, 2, 3, 4, 5, 6
 UNIQUE_ID_BYTES = 128
 
 dp = C.POINTER(C.c_double)
@@ -57,7 +57,7 @@ class Stats(C.Structure):
                 ("t_newton_ms", C.c_double), ("n_newton_timed", C.c_uint64), ("newton_lu_sync_timeouts", C.c_uint64)]
 
 
-PATH_FUSED, PATH_SYM, PATH_SYM_GENERIC, PATH_PIPELINED, PATH_SYM2, PATH_TILES1 = 1, 2, 4, 8, 16, 32
+PATH_FUSED, PATH_SYM, PATH_SYM_GENERIC, PATH_PIPELINED, PATH_SYM2, PATH_TILES1, PATH_VECTOR = 1, 2, 4, 8, 16, 32, 64
 
 
 # every symbol include/qn_hip.h declares: (name, restype, argtypes)
@@ -94,6 +94,8 @@ SYMBOLS = [
     ("qn_backtracking_b_new", None, [C.POINTER(LineSearchStruct), C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     ("qn_linesearch_with_lower_bound", None, [C.POINTER(LineSearchStruct), C.c_void_p]),
     ("qn_linesearch_with_upper_bound", None, [C.POINTER(LineSearchStruct), C.c_void_p]),
+    ("qn_gll_quadratic_new", None, [C.POINTER(LineSearchStruct), C.c_double, C.c_size_t]),
+    ("qn_gll_quadratic_with_sigmas", None, [C.POINTER(LineSearchStruct), C.c_double, C.c_double]),
     ("qn_quadratic_create", C.c_int, [C.c_void_p, C.c_size_t, dp, dp, C.POINTER(C.c_void_p)]),
     ("qn_quadratic_create_synthetic", C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, dp, dp, C.POINTER(C.c_void_p)]),
     ("qn_logsumexp_create", C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, dp, dp, C.c_double, C.POINTER(C.c_void_p)]),
@@ -104,6 +106,8 @@ SYMBOLS = [
     ("qn_solver_destroy", None, [C.c_void_p]),
     ("qn_solver_reset", C.c_int, [C.c_void_p, dp]),
     ("qn_solver_set_bounds", C.c_int, [C.c_void_p, dp, dp]),
+    ("qn_solver_set_spg_lambdas", C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    ("qn_solver_spg_lambda", C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int)]),
     ("qn_minimize", C.c_int, [C.c_void_p, C.POINTER(LineSearchStruct), C.POINTER(OracleStruct), C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("qn_compute_step_len", C.c_int, [C.c_void_p, C.POINTER(LineSearchStruct), dp, C.c_double, dp, dp, C.c_size_t, C.POINTER(OracleStruct), C.c_size_t,
                              C.POINTER(C.c_double)]),

@@ -59,3 +59,6 @@ extern "C" const char* qn_status_string(int status) {
 #include "qn_host_newton.hip.h"
 #include "qn_host_minimize.hip.h"
 #include "qn_host_blas.hip.h"
+// the first-order family (SPG, projected gradient, GLLQuadratic): its kernels are defined behind every existing one
+#include "qn_vec.hip.h"
+#include "qn_host_vec.hip.h"

@@ -6,6 +6,7 @@
 // ------------------------------------------------------------------------------------------------
 enum { KC_HPASS = 0, KC_EVAL = 1, KC_CTL = 2, KC_COMM = 3, KC_HREDUCE = 4, KC_EREDUCE = 5, KC_NEWTON = 6 };
 struct TimedEvent { hipEvent_t a, b; int cls; };
+struct QnVecCtl; // the first-order family's control block (qn_vec.hip.h; pump and state: qn_host_vec.hip.h)
 
 struct qn_solver {
     qn_context* ctx = nullptr;
@@ -93,6 +94,8 @@ struct qn_solver {
     int newton_force_lu = 0; // diagnostics (QN_OPT_NEWTON_PIVOTED_LU): skip the Cholesky attempt
     size_t newton_n64 = 0;
     std::vector<double> newton_hhost;
+    QnVecCtl *vctl = nullptr, *hvctl = nullptr; // QN_SPG / QN_PROJECTED_GRADIENT: device control block, pinned host copy (lambda, GLL history, memo)
+    double* vpart = nullptr;                    // ... and the per-workgroup partials of their vector kernels
     double* bounds_block = nullptr; // lb, ub (solver), llb, lub (bounded line search): 4 n_pad vectors
     int bounded = 0;
     double* fused_block = nullptr; // X0[2], S0[2], G, GT, Y, UN, UP, VV (10 n_pad vectors)
@@ -358,6 +361,12 @@ static int solver_alloc_sym2(qn_solver* s) {
     return QN_OK;
 }
 
+static bool vec_method(int method);
+static int vec_state_alloc(qn_solver* s);
+static void vec_state_reset(qn_solver* s);
+static int vec_compute_direction(qn_solver* s, const double* g_host, double* d_host);
+static int bounds_alloc(qn_solver* s);
+
 static int solver_alloc_hp(qn_solver* s) {
     if (s->V.hp) { HIPCHK(hipFree(s->V.hp)); s->V.hp = nullptr; }
     if (s->V.q) { HIPCHK(hipFree(s->V.q)); s->V.q = nullptr; }
@@ -370,8 +379,9 @@ static int solver_alloc_hp(qn_solver* s) {
 
 extern "C" int qn_solver_create(qn_context* ctx, int method, double tol, const double* x0_host, size_t n, qn_solver** out) {
     if (!ctx || !x0_host || !out || n == 0) return fail(QN_ERROR_INPUT_PARAMS, "null argument or n == 0");
-    if (method != QN_BFGS && method != QN_DFP && method != QN_GRADIENT_DESCENT && method != QN_NEWTON && method != QN_SR1)
+    if (method != QN_BFGS && method != QN_DFP && method != QN_GRADIENT_DESCENT && method != QN_NEWTON && method != QN_SR1 && !vec_method(method))
         return fail(QN_ERROR_INPUT_PARAMS, "unknown method");
+    if (vec_method(method) && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient run on one rank");
     if (n > (size_t)1 << 30) return fail(QN_ERROR_INPUT_PARAMS, "n too large");
     HIPCHK(hipSetDevice(ctx->device));
     qn_solver* s = new qn_solver();
@@ -409,6 +419,7 @@ extern "C" int qn_solver_create(qn_context* ctx, int method, double tol, const d
     HIPCHK(hipHostMalloc((void**)&s->hx, n * sizeof(double), hipHostMallocDefault));
     HIPCHK(hipHostMalloc((void**)&s->hg, (n + 1) * sizeof(double), hipHostMallocDefault));
     HIPCHK(hipMemcpyAsync(s->V.x, x0_host, n * sizeof(double), hipMemcpyHostToDevice, st));
+    if (vec_method(method)) QNCHK(vec_state_alloc(s)); // O(n): no H, no n x n scratch
     HIPCHK(hipStreamSynchronize(st));
     return QN_OK;
 }
@@ -423,6 +434,7 @@ extern "C" void qn_solver_destroy(qn_solver* s) {
     (void)hipFree(s->H); (void)hipFree(s->vec_block); (void)hipFree(s->V.hp); (void)hipFree(s->V.q);
     (void)hipFree(s->newton_w); (void)hipFree(s->newton_x); (void)hipFree(s->newton_invl); (void)hipFree(s->newton_inv2); (void)hipFree(s->sym_part); (void)hipFree(s->symsh_xg); (void)hipFree(s->symsh_gath); (void)hipFree(s->newton_hsrc); (void)hipFree(s->newton_fail); (void)hipFree(s->newton_piv); (void)hipFree(s->newton_perm); (void)hipFree(s->newton_panel); (void)hipFree(s->newton_sync); (void)hipFree(s->newton_rec);
     (void)hipFree(s->bounds_block);
+    (void)hipFree(s->vctl); (void)hipFree(s->vpart); (void)hipHostFree(s->hvctl);
     (void)hipFree(s->fused_block); (void)hipFree(s->fused_evp); (void)hipFree(s->fused_hpp);
     (void)hipFree(s->s2_items); (void)hipFree(s->s2_wgS); (void)hipFree(s->s2_partE); (void)hipFree(s->s2_ctl);
     (void)hipFree(s->s2_evS); (void)hipFree(s->s2_cnt); (void)hipFree(s->s2_gws); (void)hipFree(s->s2_wgV); (void)hipFree(s->s2_sl_off); (void)hipFree(s->s2_sl_idx); (void)hipFree(s->symsh_tiles);
@@ -596,7 +608,8 @@ static int bounds_upload(qn_solver* s, double* dst, const double* src_host, doub
 
 extern "C" int qn_solver_set_bounds(qn_solver* s, const double* lb_host, const double* ub_host) { // BFGSB::new, bfgs_b.rs:43-63
     if (!s || !lb_host || !ub_host) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
-    if (s->method != QN_BFGS && s->method != QN_DFP && s->method != QN_SR1) return fail(QN_ERROR_INPUT_PARAMS, "bounds need a BFGS / DFP / SR1 solver");
+    if (s->method != QN_BFGS && s->method != QN_DFP && s->method != QN_SR1 && !vec_method(s->method))
+        return fail(QN_ERROR_INPUT_PARAMS, "bounds need a BFGS / DFP / SR1 / SPG / projected-gradient solver");
     HIPCHK(hipSetDevice(s->ctx->device));
     QNCHK(bounds_alloc(s));
     QNCHK(bounds_upload(s, s->bounds_block, lb_host, -INFINITY));
@@ -620,8 +633,21 @@ extern "C" int qn_solver_reset(qn_solver* s, const double* x0_host) {
     }
     s->fused_live = false; s->warm_obj = 0; // (whatever the fused buffers hold is dropped with the rest of the state)
     HIPCHK(hipMemsetAsync(s->vec_block, 0, 9 * (size_t)s->T.n_pad * sizeof(double), st));
-    HIPCHK(hipMemcpyAsync(s->V.x, x0_host, s->n * sizeof(double), hipMemcpyHostToDevice, st));
+    // SpectralProjectedGradient::new / ProjectedGradientDescent::new project x0 (spg.rs:35): projected on the host first, then ONE upload in
+    // stream order behind the memset (the vector outlives the upload: poke_ctl synchronises the stream before this function returns)
+    std::vector<double> xp;
+    if (vec_method(s->method) && s->bounded) {
+        const size_t n = s->n;
+        std::vector<double> lb(n), ub(n);
+        HIPCHK(hipMemcpyAsync(lb.data(), s->bounds_block, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(ub.data(), s->bounds_block + s->T.n_pad, n * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        xp.assign(x0_host, x0_host + n);
+        for (size_t i = 0; i < n; ++i) xp[i] = std::fmin(std::fmax(xp[i], lb[i]), ub[i]);
+    }
+    HIPCHK(hipMemcpyAsync(s->V.x, xp.empty() ? x0_host : xp.data(), s->n * sizeof(double), hipMemcpyHostToDevice, st));
     memset(s->hctl, 0, sizeof(QnCtl));
+    vec_state_reset(s);
     return poke_ctl(s);
 }
 
@@ -787,6 +813,7 @@ extern "C" int qn_solver_compute_direction(qn_solver* s, const double* g_host, d
     if (!s || !g_host || !d_host) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
     if (s->method == QN_NEWTON) return fail(QN_ERROR_INPUT_PARAMS, "the Newton direction needs the oracle's Hessian: use qn_minimize");
     const size_t n = s->n;
+    if (vec_method(s->method)) return vec_compute_direction(s, g_host, d_host);
     if (!s->H) { // gradient descent
         for (size_t i = 0; i < n; ++i) d_host[i] = -g_host[i];
         return QN_OK;

@@ -1,0 +1,269 @@
+// qn_host_vec.hip.h -- host side of the first-order family (QN_SPG, QN_PROJECTED_GRADIENT; kernels: qn_vec.hip.h): GLLQuadratic's builders,
+// the SPG setters, and the pump.  The pump takes no decision: it enqueues one iteration's kernels -- every one predicated on QnVecCtl.phase --
+// and reads the control block back with one small copy per batch (a 700-byte hipMemcpyAsync into pinned memory in front of the one
+// synchronisation the batch needs anyway: no second mapping to keep coherent, no fence in the one-workgroup kernels).
+#pragma once
+
+extern "C" void qn_gll_quadratic_new(qn_linesearch* ls, double c1, size_t m) { // GLLQuadratic::new, gll_quadratic.rs:13-23
+    memset(ls, 0, sizeof(*ls));
+    ls->kind = QN_LS_GLL_QUADRATIC;
+    ls->c1 = c1;
+    ls->_pad = m > (size_t)INT32_MAX ? INT32_MAX : (int32_t)m;
+    ls->delta_min = 0.1; ls->delta_max = 0.9; // sigma1, sigma2
+}
+extern "C" void qn_gll_quadratic_with_sigmas(qn_linesearch* ls, double sigma1, double sigma2) { // :24-28
+    ls->delta_min = sigma1; ls->delta_max = sigma2;
+}
+
+static bool vec_method(int method) { return method == QN_SPG || method == QN_PROJECTED_GRADIENT; }
+static int vec_grid(size_t np) { // a function of n alone: four 16-byte accesses per thread until 4 workgroups per CU are out
+    const size_t per = (size_t)QN_VEC_TPB * 2 * 4;
+    return (int)std::min<size_t>(QN_VEC_MAXG, std::max<size_t>(1, (np + per - 1) / per));
+}
+
+// O(n) only: the control block and the partials; the vectors are the solver's work vectors (no H, no n x n scratch)
+static int vec_state_alloc(qn_solver* s) {
+    if (s->vctl) return QN_OK;
+    hipStream_t st = s->ctx->stream;
+    HIPCHK(hipMalloc((void**)&s->vctl, sizeof(QnVecCtl)));
+    HIPCHK(hipMemsetAsync(s->vctl, 0, sizeof(QnVecCtl), st));
+    HIPCHK(hipHostMalloc((void**)&s->hvctl, sizeof(QnVecCtl), hipHostMallocDefault));
+    memset(s->hvctl, 0, sizeof(QnVecCtl));
+    s->hvctl->lambda_min = 1e-3; s->hvctl->lambda_max = 1e3; // spg.rs:36-37
+    QNCHK(dev_alloc_zero(&s->vpart, (size_t)QN_VEC_NPART * QN_VEC_MAXG, st));
+    QNCHK(bounds_alloc(s)); // the box is (-inf, +inf) until qn_solver_set_bounds
+    return QN_OK;
+}
+static void vec_state_reset(qn_solver* s) { // back to the state right after ::new: no lambda, an empty f_previous, no memo
+    if (!s->hvctl) return;
+    QnVecCtl* h = s->hvctl;
+    h->has_lambda = 0; h->lambda = 0.0; h->have_eval = 0; h->ring_len = 0; h->k = 0; h->n_iter = 0;
+}
+
+extern "C" int qn_solver_set_spg_lambdas(qn_solver* s, double lambda_min, double lambda_max) { // with_lambdas, spg.rs:23-27
+    if (!s) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
+    if (s->method != QN_SPG) return fail(QN_ERROR_INPUT_PARAMS, "lambda bounds belong to a SpectralProjectedGradient solver");
+    s->hvctl->lambda_min = lambda_min; s->hvctl->lambda_max = lambda_max; // (the current lambda is not clamped again, as in the reference)
+    return QN_OK;
+}
+extern "C" int qn_solver_spg_lambda(qn_solver* s, double* out, int* is_some) {
+    if (!s) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
+    if (s->method != QN_SPG) return fail(QN_ERROR_INPUT_PARAMS, "lambda belongs to a SpectralProjectedGradient solver");
+    if (is_some) *is_some = s->hvctl->has_lambda;
+    if (out) *out = s->hvctl->lambda;
+    return QN_OK;
+}
+
+// ComputeDirection::compute_direction on its own: P(x - lambda g) - x (spg.rs:76-86), P(x - g) - x (projected_gradient_descent.rs:51-60)
+static int vec_compute_direction(qn_solver* s, const double* g_host, double* d_host) {
+    const size_t n = s->n, np = s->T.n_pad;
+    if (s->method == QN_SPG && !s->hvctl->has_lambda) return fail(QN_ERROR_INPUT_PARAMS, "lambda0 needs the oracle: the first qn_minimize evaluates it");
+    std::vector<double> x(n), lb(n), ub(n);
+    QNCHK(qn_solver_get_x(s, x.data()));
+    HIPCHK(hipMemcpy(lb.data(), s->bounds_block, n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ub.data(), s->bounds_block + np, n * sizeof(double), hipMemcpyDeviceToHost));
+    const double lam = s->hvctl->lambda;
+    for (size_t i = 0; i < n; ++i) {
+        const double step = s->method == QN_SPG ? lam * g_host[i] : g_host[i];
+        const double u = x[i] - step;
+        d_host[i] = std::fmin(std::fmax(u, lb[i]), ub[i]) - x[i];
+    }
+    return QN_OK;
+}
+
+struct VecRun {
+    qn_solver* s;
+    const qn_oracle* o;
+    qn_objective* obj;
+    QnVecArgs a;
+};
+
+static int vec_peek(VecRun& r, bool with_xt) { // the one small copy, and the batch's synchronisation
+    qn_solver* s = r.s;
+    hipStream_t st = s->ctx->stream;
+    if (with_xt) HIPCHK(hipMemcpyAsync(s->hx, s->V.xt, s->n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(s->hvctl, s->vctl, sizeof(QnVecCtl), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    s->stats.host_syncs++;
+    return QN_OK;
+}
+
+// the oracle at V.xt -> (f_dev, V.gt); unconditional (a closure cannot be predicated): the kernels behind it are
+static int vec_enqueue_eval(VecRun& r) {
+    qn_solver* s = r.s;
+    qn_context* c = s->ctx;
+    hipStream_t st = c->stream;
+    ProfScope ps(s, KC_EVAL);
+    if (r.o->kind == QN_ORACLE_HOST) { // s->hx holds xt (vec_peek)
+        double f = NAN;
+        if (r.o->host_fn(r.o->host_user, s->hx, s->n, &f, s->hg) != 0) return fail(QN_ABNORMAL_TERMINATION, "host oracle returned non-zero");
+        s->hg[s->n] = f;
+        HIPCHK(hipMemcpyAsync(s->V.gt, s->hg, s->n * sizeof(double), hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s->f_dev, s->hg + s->n, sizeof(double), hipMemcpyHostToDevice, st));
+        return QN_OK;
+    }
+    if (r.o->kind == QN_ORACLE_DEVICE_FN) {
+        if (r.o->device_fn(r.o->device_user, (void*)st, s->V.xt, s->n, s->f_dev, s->V.gt) != 0)
+            return fail(QN_ABNORMAL_TERMINATION, "device oracle returned non-zero");
+        return QN_OK;
+    }
+    if (r.obj->kind == OBJ_LOGSUMEXP) return lse_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt);
+    // quadratic: the unconditional launches of qn_objective_eval -- Q xt by the row kernel, then f and g = Q xt - b
+    QnQuadArgs q{};
+    q.Q = r.obj->Q; q.T = r.obj->T; q.T.cs = 1; q.x = s->V.xt; q.d = s->V.xt; q.xt = s->V.s; // (row-block 0 stores its copy of the point: V.s is free here)
+    q.out = s->V.q; q.ctl = nullptr; q.expect_phase = -1; q.force_kind = QN_REQ_X; q.force_t = 0.0;
+    QNCHK(launch_quad_R(8, st, q));
+    QnVecs V{};
+    V.q = s->V.q; V.xt = s->V.xt; V.b = r.obj->b; V.n = (int)s->n; V.n_pad = s->T.n_pad; V.rpr = s->T.rpr; V.world = 1; V.qcs = 1; V.hcs = 1;
+    hipLaunchKernelGGL(quad_finish_kernel, dim3(1), dim3(QN_CTL_TPB), 0, st, V, s->f_dev, s->V.gt);
+    HIPCHK(hipGetLastError());
+    s->stats.launches += 2;
+    return QN_OK;
+}
+
+#define VEC_LAUNCH(kernel, grid)                                                                    \
+    do {                                                                                            \
+        ProfScope ps(s, KC_CTL);                                                                    \
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(QN_VEC_TPB), 0, st, r.a);                       \
+        s->stats.launches++;                                                                        \
+        HIPCHK(hipGetLastError());                                                                  \
+    } while (0)
+
+static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, size_t max_iter_solver, size_t max_iter_line_search,
+                        qn_callback_fn callback, void* callback_user, int ls_only, double ls_f0) {
+    qn_context* c = s->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    if (c->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient run on one rank");
+    VecRun r{s, o, nullptr, {}};
+    if (o->kind == QN_ORACLE_OBJECTIVE) {
+        if (!o->objective) return fail(QN_ERROR_INPUT_PARAMS, "objective is null");
+        if (o->objective->ctx != c || o->objective->n != s->n) return fail(QN_ERROR_INPUT_PARAMS, "objective does not match the solver");
+        r.obj = o->objective;
+        if (r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_LOGSUMEXP) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
+    } else if (o->kind == QN_ORACLE_HOST) {
+        if (!o->host_fn) return fail(QN_ERROR_INPUT_PARAMS, "host oracle is null");
+    } else if (o->kind == QN_ORACLE_DEVICE_FN) {
+        if (!o->device_fn) return fail(QN_ERROR_INPUT_PARAMS, "device oracle is null");
+    } else return fail(QN_ERROR_INPUT_PARAMS, "unknown oracle kind");
+    if (ls->kind == QN_LS_MORETHUENTE || ls->kind == QN_LS_MORETHUENTE_B)
+        return fail(QN_ERROR_INPUT_PARAMS, "More-Thuente with SPG / projected gradient is out of scope: use GLLQuadratic, BackTracking or BackTrackingB");
+    if (ls->kind != QN_LS_GLL_QUADRATIC && ls->kind != QN_LS_BACKTRACKING && ls->kind != QN_LS_BACKTRACKING_B)
+        return fail(QN_ERROR_INPUT_PARAMS, "unknown line search");
+    if (ls->kind == QN_LS_GLL_QUADRATIC && (ls->_pad < 1 || ls->_pad > QN_GLL_MAX_M))
+        return fail(QN_ERROR_INPUT_PARAMS, "GLLQuadratic: the look-back m must be 1 .. 64 (the history is a fixed device ring)");
+    QNCHK(vec_state_alloc(s));
+    hipStream_t st = c->stream;
+    const size_t np = s->T.n_pad;
+    if (ls->kind == QN_LS_BACKTRACKING_B) {
+        QNCHK(bounds_upload(s, s->bounds_block + 2 * np, ls->lower_bound_host, -INFINITY));
+        QNCHK(bounds_upload(s, s->bounds_block + 3 * np, ls->upper_bound_host, INFINITY));
+    }
+
+    QnVecCtl* h = s->hvctl;
+    h->tol = s->tol;
+    h->max_iter = (int64_t)std::min<size_t>(max_iter_solver, (size_t)1 << 62);
+    h->max_iter_ls = (int64_t)std::min<size_t>(max_iter_line_search, (size_t)1 << 62);
+    h->method = s->method; h->ls_kind = ls->kind; h->memoize = o->memoize ? 1 : 0; h->ls_only = ls_only;
+    if (ls->kind == QN_LS_GLL_QUADRATIC) { h->c1 = ls->c1; h->m = ls->_pad; h->sigma1 = ls->delta_min; h->sigma2 = ls->delta_max; h->beta = 0.0; }
+    else { h->c1 = ls->bt_c1; h->beta = ls->bt_beta; h->m = 0; }
+    h->trace_cap = (int64_t)s->trace_cap; h->trace_x = s->trace_x;
+    h->k = 0; h->ls_i = 0; h->status = -1; // ls_solver.rs:74
+    h->n_calls = 0; h->n_evals = 0; h->n_iter = 0; h->tr_n_evals = 0; h->tr_ls_iters = 0;
+    // the memo of the evaluation at x survives a call only on the same device objective, with nothing having touched x in between
+    const uint64_t serial = r.obj ? r.obj->serial : 0;
+    if (!(h->have_eval && h->memoize && s->hctl->have_cur_eval && serial != 0 && s->warm_obj == serial)) h->have_eval = 0;
+    s->warm_obj = 0;
+    bool done = false;
+    if (ls_only) { h->f_cur = ls_f0; h->have_eval = 1; h->phase = QN_VP_LS_ONLY; }
+    else if (s->method == QN_SPG && !h->has_lambda) h->phase = h->have_eval ? QN_VP_DIR : QN_VP_EVAL_X; // spg.rs:40-46, whatever the cap
+    else if (h->max_iter <= 0) { h->status = QN_MAX_ITER_REACHED; h->phase = QN_VP_DONE; done = true; }  // ls_solver.rs:78
+    else h->phase = h->have_eval ? QN_VP_DIR : QN_VP_EVAL_X;
+    HIPCHK(hipMemcpyAsync(s->vctl, h, sizeof(QnVecCtl), hipMemcpyHostToDevice, st));
+    if (done) HIPCHK(hipStreamSynchronize(st)); // (nothing else will wait for the upload: the host copy may be written again)
+
+    QnVecArgs& a = r.a;
+    a.x = s->V.x; a.g = s->V.g; a.d = s->V.d; a.xt = s->V.xt; a.gt = s->V.gt;
+    a.lb = s->V.lb; a.ub = s->V.ub; a.llb = s->V.llb; a.lub = s->V.lub;
+    a.part = s->vpart; a.ctl = s->vctl; a.f_dev = s->f_dev; a.trace = s->V.trace; a.xtrace = s->V.xtrace;
+    a.n = (int)s->n; a.np = (int)np; a.G = vec_grid(np);
+    const int G = a.G;
+    const bool host_oracle = o->kind == QN_ORACLE_HOST;
+    const size_t vb = np * sizeof(double);
+    int64_t k_seen = 0;
+
+    while (!done) {
+        int ph = h->phase;
+        if (ph == QN_VP_EVAL_X) { // the oracle at x itself: through xt / gt like every evaluation
+            HIPCHK(hipMemcpyAsync(s->V.xt, s->V.x, vb, hipMemcpyDeviceToDevice, st));
+            if (host_oracle) {
+                HIPCHK(hipMemcpyAsync(s->hx, s->V.x, s->n * sizeof(double), hipMemcpyDeviceToHost, st));
+                HIPCHK(hipStreamSynchronize(st));
+                s->stats.host_syncs++;
+            }
+            QNCHK(vec_enqueue_eval(r));
+            HIPCHK(hipMemcpyAsync(s->V.g, s->V.gt, vb, hipMemcpyDeviceToDevice, st));
+        }
+        if (ph == QN_VP_EVAL_X || ph == QN_VP_DIR || ph == QN_VP_LS_ONLY) {
+            VEC_LAUNCH(vec_dir_kernel, G);
+            VEC_LAUNCH(vec_top_kernel, 1);
+            if (s->method == QN_SPG && !h->has_lambda && !ls_only) { // the constructor's batch (spg.rs:40-46) ends here: no trial is wanted yet
+                QNCHK(vec_peek(r, false));
+                done = h->phase == QN_VP_DONE;
+                continue;
+            }
+        } else if (ph != QN_VP_TRIAL && ph != QN_VP_REEVAL) {
+            return fail(QN_ABNORMAL_TERMINATION, "vector pump: control block in an unexpected phase");
+        }
+        VEC_LAUNCH(vec_trial_kernel, G);
+        if (host_oracle) { // a host closure is called only for a point the machine asked for
+            QNCHK(vec_peek(r, true));
+            ph = h->phase;
+            if (ph == QN_VP_TRIAL || ph == QN_VP_REEVAL) QNCHK(vec_enqueue_eval(r));
+        } else {
+            QNCHK(vec_enqueue_eval(r));
+        }
+        VEC_LAUNCH(vec_decide_kernel, 1);
+        VEC_LAUNCH(vec_accept_kernel, G);
+        VEC_LAUNCH(vec_post_kernel, 1);
+        QNCHK(vec_peek(r, false));
+        if (callback && h->k != k_seen) { // ls_solver.rs:105-107: after k += 1 (one iteration per batch at most)
+            k_seen = h->k;
+            s->hctl->k = h->k; s->hctl->n_iterations = h->n_iter;
+            callback(callback_user, s);
+        }
+        done = h->phase == QN_VP_DONE;
+    }
+    const int status = h->status;
+    s->hctl->k = h->k; s->hctl->n_iterations = h->n_iter; s->hctl->ls_result = h->ls_result;
+    s->hctl->have_cur_eval = h->have_eval;
+    s->warm_obj = (h->have_eval && h->memoize && serial != 0 && !ls_only) ? serial : 0;
+    s->stats.iterations = h->n_iter;
+    s->stats.oracle_calls = h->n_calls;
+    s->stats.oracle_evals = h->n_evals;
+    s->stats.h_passes = 0; s->stats.h_bytes = 0; s->stats.matrix_bytes_per_pass = 0;
+    s->stats.obj_bytes = 0;
+    if (r.obj && r.obj->kind == OBJ_QUADRATIC) s->stats.obj_bytes = h->n_evals * (uint64_t)r.obj->T.rpr * (uint64_t)r.obj->T.n_pad * 8ull;
+    s->stats.total_minimize_calls++;
+    s->stats.total_iterations += s->stats.iterations;
+    s->stats.total_oracle_calls += s->stats.oracle_calls;
+    s->stats.total_oracle_evals += s->stats.oracle_evals;
+    s->stats.total_obj_bytes += s->stats.obj_bytes;
+    s->stats.path = QN_PATH_VECTOR;
+    if (status < 0 || status == QN_ABNORMAL_TERMINATION) return fail(QN_ABNORMAL_TERMINATION, "vector pump: the machine stopped without a status");
+    return status;
+}
+
+// qn_compute_step_len for GLLQuadratic: one compute_step_len on an empty f_previous (f_max = f_k)
+static int vec_compute_step_len(qn_context* ctx, qn_linesearch* ls, const double* x_k_host, double f_k, const double* g_k_host,
+                                const double* direction_host, size_t n, const qn_oracle* oracle, size_t max_iter, double* step_out) {
+    qn_solver* s = nullptr;
+    QNCHK(qn_solver_create(ctx, QN_PROJECTED_GRADIENT, 0.0, x_k_host, n, &s));
+    int st = QN_OK;
+    hipError_t e = hipMemcpyAsync(s->V.g, g_k_host, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->V.d, direction_host, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) st = fail(QN_ABNORMAL_TERMINATION, std::string("compute_step_len upload: ") + hipGetErrorString(e));
+    if (st == QN_OK) st = vec_minimize(s, ls, oracle, 1, max_iter, nullptr, nullptr, 1, f_k);
+    if (st == QN_OK) *step_out = s->hvctl->ls_result;
+    qn_solver_destroy(s);
+    return st;
+}

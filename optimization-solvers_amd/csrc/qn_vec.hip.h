@@ -1,0 +1,335 @@
+// qn_vec.hip.h -- the first-order family: SpectralProjectedGradient (steepest_descent/spg.rs), ProjectedGradientDescent
+// (steepest_descent/projected_gradient_descent.rs) and the GLLQuadratic line search (line_search/gll_quadratic.rs), with BackTracking and
+// BackTrackingB beside it.  These solvers keep O(n) state, so the vectors ARE the problem: every O(n) operation runs on a device-wide grid
+// with 16-byte accesses, and every decision is taken by a one-workgroup kernel from per-workgroup partials.
+//
+//   vec_dir_kernel     x, g, lb, ub, lambda -> d = P(x - lambda g) - x; partials ||pg||_inf, g.d, ||d||_inf
+//   vec_top_kernel     (1 workgroup) loop top of ls_solver.rs:78-90: lambda0, out-of-domain, convergence, opens the line search
+//   vec_trial_kernel   xt = x + t d (projected onto the line search's box for BackTrackingB: partials ||xt - x||^2, "projection moved it")
+//   [the oracle at xt, enqueued by the host pump]
+//   vec_decide_kernel  (1 workgroup) the line search's decision: accept, or the next t
+//   vec_accept_kernel  predicated on the accept: x_next = x + t d, s, y, partials s.y, s.s; x <- x_next, g <- gt
+//   vec_post_kernel    (1 workgroup) the Barzilai-Borwein scalar, the trace record, k += 1, the iteration cap
+//
+// REDUCTIONS are two-stage and fixed: workgroup b leaves its share in part[q * QN_VEC_MAXG + b]; the one-workgroup kernels add the G
+// shares in index order (thread j takes b = j, j + 256, ..., then the block sum in wave order).  The grid is a function of n alone, no
+// floating-point atomic is used, and no kernel waits for another workgroup: the same bits from run to run.
+// Every kernel is predicated on QnVecCtl.phase, so the host enqueues a whole iteration without reading a decision.
+// The dot products multiply and add with two roundings, as the reference does (no FMA: these kernels are bound by memory, and at n = 2 --
+// the reference's own tests -- the sums then ARE the reference's, bit for bit).
+#pragma once
+
+#define QN_VEC_TPB 256
+#define QN_VEC_MAXG 1024 // 4 workgroups per CU on 256 CUs
+#define QN_VEC_NPART 4
+#define QN_GLL_MAX_M 64
+
+enum QnVecPhase : int32_t {
+    QN_VP_IDLE = 0,
+    QN_VP_EVAL_X = 1, // the oracle at x (loop top, ls_solver.rs:79; SPG's constructor, spg.rs:40), then as QN_VP_DIR
+    QN_VP_DIR = 2,    // (f_cur, g) hold the evaluation at x: direction, loop top, first trial
+    QN_VP_TRIAL = 3,  // the line search wants the oracle at x + t d
+    QN_VP_REEVAL = 4, // SPG's update wants the oracle at x_next = x + t d, which no trial evaluated (spg.rs:130)
+    QN_VP_ACCEPT = 5, // the step is decided: accept and post kernels
+    QN_VP_LS_ONLY = 6, // qn_compute_step_len: g.d for the caller's direction, then the line search alone
+    QN_VP_DONE = 7
+};
+
+struct QnVecCtl {
+    // ---- configuration (host, per call) ----
+    double tol;
+    int64_t max_iter, max_iter_ls;
+    int32_t method, ls_kind, memoize, ls_only;
+    double c1, beta, sigma1, sigma2;
+    int32_t m, trace_x;
+    int64_t trace_cap;
+    double lambda_min, lambda_max;
+    // ---- state that survives calls ----
+    double lambda;
+    int32_t has_lambda, have_eval; // have_eval: (f_cur, g) are the evaluation at x
+    double f_cur;
+    double ring[QN_GLL_MAX_M]; // GLLQuadratic.f_previous (gll_quadratic.rs:7), oldest first
+    int32_t ring_len, _pad0;
+    // ---- run state ----
+    int32_t phase, status;
+    int64_t k, ls_i;
+    double gd, pgnorm, t, f_max, f_t, ls_result;
+    int32_t gt_valid, _pad1; // (f_t, gt) are the evaluation at x + t d exactly
+    // ---- per-iteration trace scratch ----
+    double tr_f, tr_gnorm;
+    int32_t tr_n_evals, tr_ls_iters;
+    // ---- counters of this call ----
+    uint64_t n_calls, n_evals, n_iter;
+};
+
+struct QnVecArgs {
+    double *x, *g, *d, *xt, *gt;
+    const double *lb, *ub, *llb, *lub;
+    double* part; // [QN_VEC_NPART][QN_VEC_MAXG]
+    QnVecCtl* ctl;
+    const double* f_dev;
+    QnTraceRec* trace;
+    double* xtrace;
+    int n, np, G;
+};
+
+__device__ __forceinline__ double vec_block_max(double v, double* lds) { return ctl_block_fmax(v, lds); }
+
+// d = P(x - lambda g) - x, three roundings per element in that order (spg.rs:81-83); PGD: x - g (projected_gradient_descent.rs:56-58).
+// Before SPG has its lambda the same kernel forms P(x0 - g0) - x0, whose infinity norm gives lambda0 (spg.rs:41-46).
+__global__ __launch_bounds__(QN_VEC_TPB) void vec_dir_kernel(const QnVecArgs a) {
+    __shared__ double lds[64];
+    const QnVecCtl* c = a.ctl;
+    const int ph = c->phase;
+    if (ph != QN_VP_EVAL_X && ph != QN_VP_DIR && ph != QN_VP_LS_ONLY) return;
+    const bool scaled = c->method == QN_SPG && c->has_lambda;
+    const double lam = c->lambda;
+    double pg = 0.0, dm = 0.0, gd[1] = {0.0};
+    const int nv = a.np >> 1;
+    for (int j = blockIdx.x * QN_VEC_TPB + threadIdx.x; j < nv; j += a.G * QN_VEC_TPB) {
+        const v2d g = ld2(a.g + 2 * j);
+        v2d d;
+        if (ph == QN_VP_LS_ONLY) {
+            d = ld2(a.d + 2 * j);
+        } else {
+            const v2d x = ld2(a.x + 2 * j), lo = ld2(a.lb + 2 * j), hi = ld2(a.ub + 2 * j);
+            const double s0 = scaled ? lam * g.x : g.x, s1 = scaled ? lam * g.y : g.y;
+            const double u0 = x.x - s0, u1 = x.y - s1;
+            d.x = fmin(fmax(u0, lo.x), hi.x) - x.x;
+            d.y = fmin(fmax(u1, lo.y), hi.y) - x.y;
+            st2(a.d + 2 * j, d);
+            // projected gradient with the exact comparisons of ls_solver.rs:124-129
+            const double p0 = ((x.x == lo.x && g.x > 0.0) || (x.x == hi.x && g.x < 0.0)) ? 0.0 : g.x;
+            const double p1 = ((x.y == lo.y && g.y > 0.0) || (x.y == hi.y && g.y < 0.0)) ? 0.0 : g.y;
+            pg = fmax(pg, fmax(fabs(p0), fabs(p1)));
+            dm = fmax(dm, fmax(fabs(d.x), fabs(d.y)));
+        }
+        gd[0] = gd[0] + g.x * d.x;
+        gd[0] = gd[0] + g.y * d.y;
+    }
+    pg = vec_block_max(pg, lds);
+    __syncthreads();
+    dm = vec_block_max(dm, lds);
+    __syncthreads();
+    ctl_block_sum<1>(gd, lds);
+    if (threadIdx.x == 0) {
+        a.part[0 * QN_VEC_MAXG + blockIdx.x] = pg;
+        a.part[1 * QN_VEC_MAXG + blockIdx.x] = gd[0];
+        a.part[2 * QN_VEC_MAXG + blockIdx.x] = dm;
+    }
+}
+
+// the G shares of quantity q, added (or maximised) in index order by one workgroup of QN_VEC_TPB threads
+__device__ __forceinline__ double vec_sum_parts(const double* part, int q, int G, double* lds) {
+    double v[1] = {0.0};
+    for (int b = threadIdx.x; b < G; b += QN_VEC_TPB) v[0] = v[0] + part[q * QN_VEC_MAXG + b];
+    __syncthreads();
+    ctl_block_sum<1>(v, lds);
+    return v[0];
+}
+__device__ __forceinline__ double vec_max_parts(const double* part, int q, int G, double* lds) {
+    double v = 0.0;
+    for (int b = threadIdx.x; b < G; b += QN_VEC_TPB) v = fmax(v, part[q * QN_VEC_MAXG + b]);
+    __syncthreads();
+    return vec_block_max(v, lds);
+}
+
+// the line search has returned ctl->t: decide what the update step needs (thread 0)
+__device__ __forceinline__ void vec_ls_return(QnVecCtl* c, bool evaluated) {
+    c->ls_result = c->t;
+    if (c->ls_only) { c->status = QN_OK; c->phase = QN_VP_DONE; return; }
+    c->gt_valid = evaluated ? 1 : 0;
+    if (c->method == QN_SPG) {
+        if (evaluated && c->memoize) { c->n_calls++; c->tr_n_evals++; c->phase = QN_VP_ACCEPT; } // spg.rs:130 at the point the search accepted
+        else { c->gt_valid = 0; c->phase = QN_VP_REEVAL; }
+    } else {
+        if (!c->memoize) c->gt_valid = 0; // the loop top evaluates x_next itself
+        c->phase = QN_VP_ACCEPT;
+    }
+}
+
+__global__ __launch_bounds__(QN_VEC_TPB) void vec_top_kernel(const QnVecArgs a) {
+    __shared__ double lds[64];
+    QnVecCtl* c = a.ctl;
+    const int ph = c->phase;
+    if (ph != QN_VP_EVAL_X && ph != QN_VP_DIR && ph != QN_VP_LS_ONLY) return;
+    const double pg = vec_max_parts(a.part, 0, a.G, lds);
+    const double gd = vec_sum_parts(a.part, 1, a.G, lds);
+    const double dm = vec_max_parts(a.part, 2, a.G, lds);
+    if (threadIdx.x != 0) return;
+    if (ph == QN_VP_EVAL_X) { c->f_cur = *a.f_dev; c->have_eval = 1; c->n_evals++; }
+    if (ph != QN_VP_LS_ONLY) {
+        c->n_calls++;
+        if (c->method == QN_SPG && !c->has_lambda) { // spg.rs:40-46: the constructor's call; d was formed with lambda = 1
+            c->lambda = fmax(fmin(1.0 / dm, c->lambda_max), c->lambda_min);
+            c->has_lambda = 1;
+            if (c->max_iter <= 0) { c->status = QN_MAX_ITER_REACHED; c->phase = QN_VP_DONE; return; }
+            c->phase = c->memoize ? QN_VP_DIR : QN_VP_EVAL_X;
+            return;
+        }
+        c->tr_n_evals++;
+        if (isnan(c->f_cur) || isinf(c->f_cur)) { c->status = QN_OUT_OF_DOMAIN; c->phase = QN_VP_DONE; return; } // ls_solver.rs:37-40
+        c->pgnorm = pg;
+        if (pg < c->tol) { c->status = QN_OK; c->phase = QN_VP_DONE; return; } // spg.rs:89-92
+        c->tr_f = c->f_cur; c->tr_gnorm = pg;
+    }
+    c->gd = gd;
+    if (c->ls_kind == QN_LS_GLL_QUADRATIC) { // gll_quadratic.rs:62-64: append_new_f, then f_max once
+        if (c->ring_len == c->m) {
+            for (int i = 1; i < c->ring_len; ++i) c->ring[i - 1] = c->ring[i];
+            c->ring_len--;
+        }
+        c->ring[c->ring_len++] = c->f_cur;
+        double fm = -INFINITY;
+        for (int i = 0; i < c->ring_len; ++i) fm = fmax(c->ring[i], fm);
+        c->f_max = fm;
+    }
+    c->t = 1.0;
+    c->ls_i = 0;
+    if (c->max_iter_ls <= 0) vec_ls_return(c, false);
+    else c->phase = QN_VP_TRIAL;
+}
+
+__global__ __launch_bounds__(QN_VEC_TPB) void vec_trial_kernel(const QnVecArgs a) {
+    __shared__ double lds[64];
+    const QnVecCtl* c = a.ctl;
+    const int ph = c->phase;
+    if (ph != QN_VP_TRIAL && ph != QN_VP_REEVAL) return;
+    const bool project = ph == QN_VP_TRIAL && c->ls_kind == QN_LS_BACKTRACKING_B; // backtracking_b.rs:65-67
+    const double t = c->t;
+    double diff2[1] = {0.0}, moved = 0.0;
+    const int nv = a.np >> 1;
+    for (int j = blockIdx.x * QN_VEC_TPB + threadIdx.x; j < nv; j += a.G * QN_VEC_TPB) {
+        const v2d x = ld2(a.x + 2 * j), d = ld2(a.d + 2 * j);
+        const double td0 = t * d.x, td1 = t * d.y; // `t * direction_k` rounds first
+        v2d u;
+        u.x = x.x + td0;
+        u.y = x.y + td1;
+        if (project) {
+            const v2d lo = ld2(a.llb + 2 * j), hi = ld2(a.lub + 2 * j);
+            v2d p;
+            p.x = fmin(fmax(u.x, lo.x), hi.x);
+            p.y = fmin(fmax(u.y, lo.y), hi.y);
+            if (p.x != u.x || p.y != u.y) moved = 1.0;
+            const double e0 = p.x - x.x, e1 = p.y - x.y;
+            diff2[0] = diff2[0] + e0 * e0;
+            diff2[0] = diff2[0] + e1 * e1;
+            u = p;
+        }
+        st2(a.xt + 2 * j, u);
+    }
+    if (!project) return;
+    moved = vec_block_max(moved, lds);
+    __syncthreads();
+    ctl_block_sum<1>(diff2, lds);
+    if (threadIdx.x == 0) {
+        a.part[0 * QN_VEC_MAXG + blockIdx.x] = diff2[0];
+        a.part[1 * QN_VEC_MAXG + blockIdx.x] = moved;
+    }
+}
+
+__global__ __launch_bounds__(QN_VEC_TPB) void vec_decide_kernel(const QnVecArgs a) {
+    __shared__ double lds[64];
+    QnVecCtl* c = a.ctl;
+    const int ph = c->phase;
+    if (ph != QN_VP_TRIAL && ph != QN_VP_REEVAL) return;
+    double diff2 = 0.0, moved = 0.0;
+    if (ph == QN_VP_TRIAL && c->ls_kind == QN_LS_BACKTRACKING_B) {
+        diff2 = vec_sum_parts(a.part, 0, a.G, lds);
+        moved = vec_max_parts(a.part, 1, a.G, lds);
+    }
+    if (threadIdx.x != 0) return;
+    const double ft = *a.f_dev;
+    c->f_t = ft;
+    c->n_calls++; c->n_evals++; c->tr_n_evals++;
+    if (ph == QN_VP_REEVAL) { c->gt_valid = 1; c->phase = QN_VP_ACCEPT; return; }
+    c->tr_ls_iters++;
+    const double t = c->t, gd = c->gd, fk = c->f_cur;
+    if (c->ls_kind == QN_LS_GLL_QUADRATIC) {
+        if (ft - c->f_max <= c->c1 * t * gd) { vec_ls_return(c, true); return; } // gll_quadratic.rs:73, mod.rs:35
+        if (t <= 0.1) {
+            c->t = t * 0.5; // :78-80
+        } else {
+            const double t_tmp = -0.5 * t * t * gd / (ft - fk - t * gd); // :83-84
+            if (t_tmp > c->sigma1 && t_tmp < c->sigma2 * t) c->t = t_tmp; // :85-87
+            else c->t = t_tmp * 0.5;                                       // :91
+        }
+        c->ls_i++;
+    } else {
+        if (isnan(ft) || isinf(ft)) { // backtracking.rs:37-41, backtracking_b.rs:70-74: `continue` without i += 1
+            c->t = t * c->beta;
+            return;
+        }
+        const bool ok = c->ls_kind == QN_LS_BACKTRACKING_B ? (ft - fk <= (-c->c1 / t) * diff2) // backtracking_b.rs:32-33
+                                                           : (ft - fk <= c->c1 * t * gd);      // mod.rs:35
+        if (ok) { vec_ls_return(c, moved == 0.0); return; } // (a projected trial that moved is not x + t d: next_iterate is, projected_gradient_descent.rs:103)
+        c->t = t * c->beta;
+        c->ls_i++;
+    }
+    if (c->ls_i >= c->max_iter_ls) vec_ls_return(c, false); // "Max iter reached. Early stopping.": t was never evaluated
+}
+
+// x_next = x + t d (spg.rs:126), s = x_next - x, y = g(x_next) - g(x) (:129-130); x <- x_next, g <- g(x_next) where it is known
+__global__ __launch_bounds__(QN_VEC_TPB) void vec_accept_kernel(const QnVecArgs a) {
+    __shared__ double lds[64];
+    const QnVecCtl* c = a.ctl;
+    if (c->phase != QN_VP_ACCEPT) return;
+    const bool have_gt = c->gt_valid != 0;
+    const double t = c->t;
+    const int64_t row = (int64_t)c->n_iter;
+    const bool xtr = c->trace_x && a.xtrace && row < c->trace_cap;
+    double acc[2] = {0.0, 0.0};
+    const int nv = a.np >> 1;
+    for (int j = blockIdx.x * QN_VEC_TPB + threadIdx.x; j < nv; j += a.G * QN_VEC_TPB) {
+        const v2d x = ld2(a.x + 2 * j), d = ld2(a.d + 2 * j);
+        const double td0 = t * d.x, td1 = t * d.y;
+        v2d xn;
+        xn.x = x.x + td0;
+        xn.y = x.y + td1;
+        const double s0 = xn.x - x.x, s1 = xn.y - x.y;
+        acc[1] = acc[1] + s0 * s0;
+        acc[1] = acc[1] + s1 * s1;
+        if (have_gt) {
+            const v2d g = ld2(a.g + 2 * j), gt = ld2(a.gt + 2 * j);
+            const double y0 = gt.x - g.x, y1 = gt.y - g.y;
+            acc[0] = acc[0] + s0 * y0;
+            acc[0] = acc[0] + s1 * y1;
+            st2(a.g + 2 * j, gt);
+        }
+        st2(a.x + 2 * j, xn);
+        if (xtr) {
+            if (2 * j < a.n) a.xtrace[(size_t)row * a.n + 2 * j] = xn.x;
+            if (2 * j + 1 < a.n) a.xtrace[(size_t)row * a.n + 2 * j + 1] = xn.y;
+        }
+    }
+    ctl_block_sum<2>(acc, lds);
+    if (threadIdx.x == 0) {
+        a.part[2 * QN_VEC_MAXG + blockIdx.x] = acc[0];
+        a.part[3 * QN_VEC_MAXG + blockIdx.x] = acc[1];
+    }
+}
+
+__global__ __launch_bounds__(QN_VEC_TPB) void vec_post_kernel(const QnVecArgs a) {
+    __shared__ double lds[64];
+    QnVecCtl* c = a.ctl;
+    if (c->phase != QN_VP_ACCEPT) return;
+    const double sy = vec_sum_parts(a.part, 2, a.G, lds);
+    const double ss = vec_sum_parts(a.part, 3, a.G, lds);
+    if (threadIdx.x != 0) return;
+    if (c->method == QN_SPG) { // spg.rs:135-143
+        if (sy <= 0.0) c->lambda = c->lambda_max;
+        else c->lambda = fmax(fmin(ss / sy, c->lambda_max), c->lambda_min);
+    }
+    if (a.trace && (int64_t)c->n_iter < c->trace_cap) {
+        QnTraceRec r;
+        r.f = c->tr_f; r.gnorm = c->tr_gnorm; r.t = c->t; r.s_norm = c->method == QN_SPG ? sqrt(ss) : 0.0; r.y_norm = 0.0;
+        r.n_evals = c->tr_n_evals; r.ls_iters = c->tr_ls_iters; r.ls_cases = 0; r.updated = 0;
+        a.trace[c->n_iter] = r;
+    }
+    c->have_eval = c->gt_valid;
+    if (c->gt_valid) c->f_cur = c->f_t;
+    c->tr_n_evals = 0; c->tr_ls_iters = 0;
+    c->k++; c->n_iter++; // ls_solver.rs:104
+    if (c->k >= c->max_iter) { c->status = QN_MAX_ITER_REACHED; c->phase = QN_VP_DONE; return; } // :78, :110
+    c->phase = (c->have_eval && c->memoize) ? QN_VP_DIR : QN_VP_EVAL_X;
+}

@@ -424,6 +424,30 @@ class BackTrackingB(_LineSearch):
         return cls(c1, beta, lower_bound, upper_bound)
 
 
+class GLLQuadratic(_LineSearch):
+    """gll_quadratic.rs: the non-monotone line search of Grippo, Lampariello and Lucidi with a safeguarded quadratic interpolation, for
+    SpectralProjectedGradient / ProjectedGradientDescent.  m is the look-back (1: monotone Armijo), at most 64.  The history `f_previous`
+    lives in the SOLVER on the device (this object is plain data): it survives successive minimize calls on one solver, `reset` empties it."""
+
+    def __init__(self, c1, m):
+        self.s = A.LineSearchStruct()
+        A.lib().qn_gll_quadratic_new(C.byref(self.s), float(c1), int(m))
+
+    @classmethod
+    def new(cls, c1, m):
+        return cls(c1, m)
+
+    def with_sigmas(self, sigma1, sigma2):
+        A.lib().qn_gll_quadratic_with_sigmas(C.byref(self.s), float(sigma1), float(sigma2))
+        return self
+
+    def c1(self):
+        return self.s.c1
+
+    def m(self):
+        return self.s._pad
+
+
 class Objective:
     """A device-resident objective owned by the library."""
 
@@ -776,6 +800,60 @@ class DFPB(_BoundedBase):
 
 class SR1B(_BoundedBase):
     METHOD = A.SR1
+
+
+class _ProjectedBase(_BoundedBase):
+    """The first-order family (steepest_descent/spg.rs, projected_gradient_descent.rs): O(n) state, no inverse Hessian."""
+
+    def grad_tol(self):
+        return self.tol()
+
+    def approx_inv_hessian(self, all_ranks=True):  # there is none: the library says so (no n x n buffer is made to find out)
+        _check(A.lib().qn_solver_get_inv_hessian(self.h, None, 0))
+
+    def set_approx_inv_hessian(self, h):
+        _check(A.lib().qn_solver_set_inv_hessian(self.h, None))
+
+    def has_converged(self, eval_x_k):  # spg.rs:89-92, projected_gradient_descent.rs:76-83
+        return float(np.max(np.abs(self.projected_gradient(eval_x_k)))) < self.tol()
+
+
+class ProjectedGradientDescent(_ProjectedBase):
+    """steepest_descent/projected_gradient_descent.rs: `new(grad_tol, x0, lower_bound, upper_bound)`; d = P(x - g) - x."""
+    METHOD = A.PROJECTED_GRADIENT
+
+
+class SpectralProjectedGradient(_ProjectedBase):
+    """steepest_descent/spg.rs: `new(grad_tol, x0, oracle, lower_bound, upper_bound)`; d = P(x - lambda g) - x with the safeguarded
+    Barzilai-Borwein scalar.  As in the reference the constructor calls the oracle once, for lambda0 (spg.rs:40-46)."""
+    METHOD = A.SPG
+
+    def __init__(self, grad_tol, x0, oracle, lower_bound, upper_bound, ctx=None, memoize=None):
+        super().__init__(grad_tol, x0, lower_bound, upper_bound, ctx)
+        self.memoize = memoize
+        try:  # a call with no iterations: the constructor's evaluation only
+            self.minimize(GLLQuadratic(1e-4, 1), oracle, 0, 0)
+        except MaxIterReached:
+            pass
+
+    @classmethod
+    def new(cls, grad_tol, x0, oracle, lower_bound, upper_bound, ctx=None, memoize=None):
+        return cls(grad_tol, x0, oracle, lower_bound, upper_bound, ctx, memoize)
+
+    def with_lambdas(self, lambda_min, lambda_max):  # spg.rs:23-27
+        _check(A.lib().qn_solver_set_spg_lambdas(self.h, float(lambda_min), float(lambda_max)))
+        self._lmin, self._lmax = float(lambda_min), float(lambda_max)
+        return self
+
+    def lambda_(self):
+        return self._opt(A.lib().qn_solver_spg_lambda)
+
+    # (the ABI has a setter for the two bounds and no getter: these return what this object last set, or spg.rs:36-37's defaults)
+    def lambda_min(self):
+        return getattr(self, "_lmin", 1e-3)
+
+    def lambda_max(self):
+        return getattr(self, "_lmax", 1e3)
 
 
 class Newton(_SolverBase):

@@ -17,6 +17,7 @@ pub const QN_LS_MORETHUENTE: i32 = 0;
 pub const QN_LS_BACKTRACKING: i32 = 1;
 pub const QN_LS_MORETHUENTE_B: i32 = 2;
 pub const QN_LS_BACKTRACKING_B: i32 = 3;
+pub const QN_LS_GLL_QUADRATIC: i32 = 4;
 
 pub const QN_ORACLE_HOST: i32 = 0;
 pub const QN_ORACLE_DEVICE_FN: i32 = 1;
@@ -27,6 +28,8 @@ pub const QN_DFP: c_int = 1;
 pub const QN_GRADIENT_DESCENT: c_int = 2;
 pub const QN_NEWTON: c_int = 3;
 pub const QN_SR1: c_int = 4;
+pub const QN_SPG: c_int = 5;
+pub const QN_PROJECTED_GRADIENT: c_int = 6;
 
 // qn_option (ABI 5): what rounds 1-5 selected through negative codes of qn_solver_set_tiling; value != 0 on, 0 off
 pub const QN_OPT_GENERIC_KERNELS: c_int = 1;
@@ -60,6 +63,7 @@ pub const QN_PATH_SYM_GENERIC: u32 = 4;
 pub const QN_PATH_PIPELINED: u32 = 8;
 pub const QN_PATH_SYM2: u32 = 16;
 pub const QN_PATH_TILES1: u32 = 32;
+pub const QN_PATH_VECTOR: u32 = 64;
 
 #[repr(C)] pub struct qn_context { _p: [u8; 0] }
 #[repr(C)] pub struct qn_solver { _p: [u8; 0] }
@@ -193,6 +197,8 @@ extern "C" {
     pub fn qn_backtracking_b_new(ls: *mut qn_linesearch, c1: f64, beta: f64, lower_bound_host: *const f64, upper_bound_host: *const f64);
     pub fn qn_linesearch_with_lower_bound(ls: *mut qn_linesearch, lower_bound_host: *const f64);
     pub fn qn_linesearch_with_upper_bound(ls: *mut qn_linesearch, upper_bound_host: *const f64);
+    pub fn qn_gll_quadratic_new(ls: *mut qn_linesearch, c1: f64, m: usize);
+    pub fn qn_gll_quadratic_with_sigmas(ls: *mut qn_linesearch, sigma1: f64, sigma2: f64);
 
     // ---- device-resident objectives ----
     pub fn qn_quadratic_create(ctx: *mut qn_context, n: usize, q_rowmajor_host: *const f64, b_host: *const f64, out: *mut *mut qn_objective) -> c_int;
@@ -206,6 +212,8 @@ extern "C" {
     pub fn qn_solver_create(ctx: *mut qn_context, method: c_int, tol: f64, x0_host: *const f64, n: usize, out: *mut *mut qn_solver) -> c_int;
     pub fn qn_solver_destroy(s: *mut qn_solver);
     pub fn qn_solver_set_bounds(s: *mut qn_solver, lower_bound_host: *const f64, upper_bound_host: *const f64) -> c_int;
+    pub fn qn_solver_set_spg_lambdas(s: *mut qn_solver, lambda_min: f64, lambda_max: f64) -> c_int;
+    pub fn qn_solver_spg_lambda(s: *mut qn_solver, out: *mut f64, is_some: *mut c_int) -> c_int;
     pub fn qn_solver_reset(s: *mut qn_solver, x0_host: *const f64) -> c_int;
     pub fn qn_minimize(s: *mut qn_solver, ls: *mut qn_linesearch, oracle: *const qn_oracle, max_iter_solver: usize, max_iter_line_search: usize, callback: qn_callback_fn, callback_user: *mut c_void) -> c_int;
     pub fn qn_compute_step_len(ctx: *mut qn_context, ls: *mut qn_linesearch, x_k_host: *const f64, f_k: f64, g_k_host: *const f64, direction_host: *const f64, n: usize, oracle: *const qn_oracle, max_iter: usize, step_out: *mut f64) -> c_int;

@@ -23,8 +23,8 @@ pub mod ffi;
 use ffi::*;
 use nalgebra::{DMatrix, DVector};
 use optimization_solvers::{
-    ComputeDirection, CurvatureCondition, Floating, FuncEvalMultivariate, LineSearch, LineSearchSolver, MoreThuente, SolverError,
-    SufficientDecreaseCondition,
+    ComputeDirection, CurvatureCondition, Floating, FuncEvalMultivariate, HasBounds, LineSearch, LineSearchSolver, MoreThuente,
+    SolverError, SufficientDecreaseCondition,
 };
 use std::ffi::CStr;
 use std::os::raw::{c_int, c_void};
@@ -234,6 +234,31 @@ macro_rules! impl_line_search {
 impl_line_search!(GpuMoreThuente);
 impl_line_search!(GpuBackTracking);
 
+/// `GLLQuadratic` (gll_quadratic.rs): the reference keeps its fields private without getters, so this is constructed from the
+/// same numbers.  The history `f_previous` is kept by the SOLVER on the device (qn_hip.h), not by this value.
+#[derive(Clone, Debug)]
+pub struct GpuGLLQuadratic {
+    ls: qn_linesearch,
+}
+
+impl GpuGLLQuadratic {
+    pub fn new(c1: Floating, m: usize) -> Self {
+        let mut ls = unsafe { std::mem::zeroed::<qn_linesearch>() };
+        unsafe { qn_gll_quadratic_new(&mut ls, c1, m) };
+        GpuGLLQuadratic { ls }
+    }
+    pub fn with_sigmas(mut self, sigma1: Floating, sigma2: Floating) -> Self {
+        unsafe { qn_gll_quadratic_with_sigmas(&mut self.ls, sigma1, sigma2) };
+        self
+    }
+}
+impl_line_search!(GpuGLLQuadratic);
+impl SufficientDecreaseCondition for GpuGLLQuadratic {
+    fn c1(&self) -> Floating {
+        self.ls.c1
+    }
+}
+
 // The condition traits of line_search/mod.rs:25-83, as the reference implements them for its own structs (morethuente.rs,
 // backtracking.rs:13-18): only the sensitivities are supplied, the tests themselves are the traits' default methods (and
 // `WolfeConditions` follows from the blanket impl, mod.rs:85-86).
@@ -311,6 +336,9 @@ struct Core {
     tol: Floating,
     x: DVector<Floating>,
     k: usize,
+    // the box of the bounded first-order solvers (spg.rs:15-16); (-inf, +inf) for every other solver
+    lb: DVector<Floating>,
+    ub: DVector<Floating>,
 }
 
 impl Core {
@@ -318,7 +346,30 @@ impl Core {
         let mut h = std::ptr::null_mut();
         let code = unsafe { qn_solver_create(default_context(), method, tol, x0.as_ptr(), x0.len(), &mut h) };
         assert_eq!(code, QN_OK, "qn_solver_create: {}", last_error());
-        Core { h, n: x0.len(), tol, x: x0, k: 0 }
+        let n = x0.len();
+        Core { h, n, tol, x: x0, k: 0, lb: DVector::from_element(n, Floating::NEG_INFINITY), ub: DVector::from_element(n, Floating::INFINITY) }
+    }
+    /// `qn_solver_set_bounds`: stores the box, projects x on the device (spg.rs:35) and mirrors the projected x
+    fn set_bounds(&mut self, lb: DVector<Floating>, ub: DVector<Floating>) -> Result<(), SolverError> {
+        if lb.len() != self.n || ub.len() != self.n {
+            return Err(SolverError::ErrorInputParams);
+        }
+        status_to_result(unsafe { qn_solver_set_x(self.h, self.x.as_ptr()) })?;
+        status_to_result(unsafe { qn_solver_set_bounds(self.h, lb.as_ptr(), ub.as_ptr()) })?;
+        self.lb = lb;
+        self.ub = ub;
+        unsafe { qn_solver_get_x(self.h, self.x.as_mut_ptr()) };
+        Ok(())
+    }
+    /// ls_solver.rs:121-133 with the exact comparisons; the gradient itself where the box is infinite
+    fn projected_gradient(&self, eval: &FuncEvalMultivariate) -> DVector<Floating> {
+        let mut pg = eval.g().clone();
+        for (i, x) in self.x.iter().enumerate() {
+            if (x == &self.lb[i] && pg[i] > 0.0) || (x == &self.ub[i] && pg[i] < 0.0) {
+                pg[i] = 0.0;
+            }
+        }
+        pg
     }
     fn option(&self, f: unsafe extern "C" fn(*mut qn_solver, *mut f64, *mut c_int) -> c_int) -> Option<Floating> {
         let (mut v, mut some) = (0.0, 0);
@@ -492,8 +543,9 @@ macro_rules! gpu_solver {
                         || self.core.flag(qn_solver_gradient_next_iterate_too_close)
                         || eval.g().norm() < self.core.tol
                 } else {
-                    // gradient_descent.rs:46-53: infinity norm
-                    eval.g().iter().fold(Floating::NEG_INFINITY, |acc, x| x.abs().max(acc)) < self.core.tol
+                    // gradient_descent.rs:46-53: infinity norm; spg.rs:89-92, projected_gradient_descent.rs:76-83: of the projected
+                    // gradient (the gradient itself while the box is infinite, as for GradientDescent)
+                    self.core.projected_gradient(eval).iter().fold(Floating::NEG_INFINITY, |acc, x| x.abs().max(acc)) < self.core.tol
                 }
             }
 
@@ -508,6 +560,11 @@ macro_rules! gpu_solver {
                 direction: &DVector<Floating>,
                 max_iter_line_search: usize,
             ) -> Result<(), SolverError> {
+                if $method == QN_SPG {
+                    // spg.rs:126-143 updates lambda here; it lives on the device and only qn_minimize updates it.  Refuse rather than run
+                    // a fixed-lambda projected gradient under SPG's name: use `minimize_on_device` / `minimize_objective`.
+                    return Err(SolverError::ErrorInputParams);
+                }
                 let step = line_search.compute_step_len(self.xk(), eval_x_k, direction, oracle, max_iter_line_search);
                 let next_iterate = self.xk() + step * direction;
                 if $quasi_newton {
@@ -538,6 +595,64 @@ gpu_solver!(
     /// Drop-in for `GradientDescent` (steepest_descent/gradient_descent.rs:7-82); `tol` is its `grad_tol`.
     GpuGradientDescent, QN_GRADIENT_DESCENT, false
 );
+
+gpu_solver!(
+    /// Drop-in for `ProjectedGradientDescent` (steepest_descent/projected_gradient_descent.rs): `new(grad_tol, x0).with_bounds(lb, ub)`
+    /// stands for `new(grad_tol, x0, lb, ub)`.  O(n) device memory, the device-wide vector kernels (QN_PATH_VECTOR).
+    GpuProjectedGradientDescent, QN_PROJECTED_GRADIENT, false
+);
+gpu_solver!(
+    /// Drop-in for `SpectralProjectedGradient` (steepest_descent/spg.rs).  `new(grad_tol, x0).with_bounds(lb, ub)`; the
+    /// constructor's oracle call (spg.rs:40-46, lambda0) is made by the first `minimize_on_device` / `minimize_objective`.
+    /// The Barzilai-Borwein scalar lives on the device and is updated by `qn_minimize` only: drive this solver with
+    /// `minimize_on_device`, not hook by hook through the trait's default `minimize`: its `update_next_iterate` returns
+    /// `ErrorInputParams` (and `compute_direction` does before the first device call has formed lambda0).
+    GpuSpectralProjectedGradient, QN_SPG, false
+);
+
+macro_rules! bounded_first_order {
+    ($name:ident) => {
+        impl $name {
+            pub fn with_bounds(mut self, lower_bound: DVector<Floating>, upper_bound: DVector<Floating>) -> Self {
+                self.core.set_bounds(lower_bound, upper_bound).expect("qn_solver_set_bounds");
+                self
+            }
+            pub fn grad_tol(&self) -> &Floating {
+                &self.core.tol
+            }
+        }
+        impl HasBounds for $name {
+            fn lower_bound(&self) -> &DVector<Floating> {
+                &self.core.lb
+            }
+            fn upper_bound(&self) -> &DVector<Floating> {
+                &self.core.ub
+            }
+            fn set_lower_bound(&mut self, lower_bound: DVector<Floating>) {
+                let ub = self.core.ub.clone();
+                self.core.set_bounds(lower_bound, ub).expect("qn_solver_set_bounds");
+            }
+            fn set_upper_bound(&mut self, upper_bound: DVector<Floating>) {
+                let lb = self.core.lb.clone();
+                self.core.set_bounds(lb, upper_bound).expect("qn_solver_set_bounds");
+            }
+        }
+    };
+}
+bounded_first_order!(GpuProjectedGradientDescent);
+bounded_first_order!(GpuSpectralProjectedGradient);
+
+impl GpuSpectralProjectedGradient {
+    /// spg.rs:23-27
+    pub fn with_lambdas(self, lambda_min: Floating, lambda_max: Floating) -> Self {
+        assert_eq!(unsafe { qn_solver_set_spg_lambdas(self.core.h, lambda_min, lambda_max) }, QN_OK, "{}", last_error());
+        self
+    }
+    /// `lambda()`: None until the first minimize call has made the constructor's evaluation
+    pub fn lambda(&self) -> Option<Floating> {
+        self.core.option(qn_solver_spg_lambda)
+    }
+}
 
 macro_rules! quasi_newton_getters {
     ($name:ident) => {
