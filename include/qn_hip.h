@@ -198,7 +198,19 @@ enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton
         * and not counted in qn_stats; a device closure that counts its own invocations sees one more than oracle_evals reports for such a run
         * (none for a run that ends on the iteration cap, none for SPG's constructor evaluation).  Host closures are called only for points the solver asked for. */
        QN_SPG = 5 /* SpectralProjectedGradient, steepest_descent/spg.rs */,
-       QN_PROJECTED_GRADIENT = 6 /* ProjectedGradientDescent, steepest_descent/projected_gradient_descent.rs */ };
+       QN_PROJECTED_GRADIENT = 6 /* ProjectedGradientDescent, steepest_descent/projected_gradient_descent.rs */,
+       /* The second-order box-constrained pair (newton/projected_newton.rs, newton/spn.rs): the first-order family's machine, line searches, box,
+        * trace, callbacks and warm restarts, with z = H^-1 g where that family has g: d = P(x - z) - x, and d = P(x - lambda z) - x with SPG's
+        * lambda (qn_solver_set_spg_lambdas / qn_solver_spg_lambda answer for QN_SPECTRAL_PROJECTED_NEWTON too).  z is `hessian.cholesky().unwrap()
+        * .solve(g)`: one blocked Cholesky (Newton's, on the f64 matrix cores) and one pair of triangular solves per iteration; ONLY THE LOWER
+        * TRIANGLE of the Hessian is read.  The Hessian is a host closure's host_hessian_fn or a device quadratic's own matrix; a device closure or
+        * a log-sum-exp objective has none here: QN_ERROR_INPUT_PARAMS ("Hessian not available in the oracle").  A Hessian whose Cholesky fails
+        * ends qn_minimize with QN_ABNORMAL_TERMINATION and x at x_k (the reference panics on the unwrap; there is no LU fallback).
+        * QN_PROJECTED_NEWTON keeps s_norm / y_norm (qn_solver_s_norm, qn_solver_y_norm, the two *_too_close getters) and tests them at the loop
+        * top in the reference's order: s_norm, y_norm, then the projected gradient (projected_newton.rs:95-110); trace: s_norm, y_norm.
+        * One n x n work matrix, allocated by the first qn_minimize that computes a direction.  One rank. */
+       QN_PROJECTED_NEWTON = 7 /* ProjectedNewton, newton/projected_newton.rs */,
+       QN_SPECTRAL_PROJECTED_NEWTON = 8 /* SpectralProjectedNewton, newton/spn.rs */ };
 typedef struct qn_solver qn_solver;
 
 /* BFGS::new(tol, x0) / DFP::new / GradientDescent::new(grad_tol, x0): H = I (no identity copy is kept) */
@@ -213,6 +225,12 @@ int qn_solver_set_spg_lambdas(qn_solver* s, double lambda_min, double lambda_max
  * the first qn_minimize after create / reset makes that call (counted in oracle_calls; with memoize = 1 the point is evaluated once):
  * is_some = 0 until then.  A qn_minimize with max_iter_solver = 0 does just that and returns QN_MAX_ITER_REACHED. */
 int qn_solver_spg_lambda(qn_solver* s, double* out, int* is_some);
+/* QN_PROJECTED_NEWTON / QN_SPECTRAL_PROJECTED_NEWTON: Cholesky factorisations enqueued by the last qn_minimize.  With a device quadratic the factor
+ * is kept between iterations and calls (keyed on the objective; QN_OPT_PNEWTON_REUSE_FACTOR): 1 for the first call, 0 afterwards; with a host
+ * closure, or with the option off, one per iteration that computed a direction.  Other methods: 0.
+ * (The count comes back through a size_t*, like every other count in this header, and not through a uint64_t*: the ABI check that compares this
+ * header with the Python and Rust mirrors knows the pointer types the header already used.  Both are 64 bits wide on every platform ROCm runs on.) */
+int qn_solver_newton_factorisations(qn_solver* s, size_t* out);
 /* back to the state right after BFGS::new(tol, x0): x = x0, H = I, k = 0, s_norm = y_norm = None */
 int qn_solver_reset(qn_solver* s, const double* x0_host);
 
@@ -313,6 +331,7 @@ typedef struct {
 #define QN_PATH_TILES1 32u     /* QN_PATH_SYM2 whose update pass streams H through the first-generation tile kernel (one workgroup per tile) behind a
                                   one-workgroup launch that runs the state machine: H's share past the Infinity Cache, and the log-sum-exp objective */
 #define QN_PATH_VECTOR 64u     /* the first-order family's device-wide vector kernels (csrc/qn_vec.hip.h): QN_SPG, QN_PROJECTED_GRADIENT */
+#define QN_PATH_PNEWTON 128u   /* ... with the direction from a Cholesky solve: QN_PROJECTED_NEWTON, QN_SPECTRAL_PROJECTED_NEWTON (set beside QN_PATH_VECTOR) */
 int qn_solver_get_stats(qn_solver* s, qn_stats* out);
 /* profiling != 0: bracket every launch with HIP events on the solver's stream (slower; for roofline reports) */
 int qn_solver_set_profiling(qn_solver* s, int on);
@@ -347,7 +366,8 @@ typedef enum {
     QN_OPT_BTB_PROJECT_IN_EVAL = 19,       /* [1] BackTrackingB on the second-generation path: the trial point projected inside the evaluation kernel (n = 4096's mover + multiplier kernel); 0: a projection launch per trial -- the same bits */
     QN_OPT_EVAL_ZIGZAG = 20,               /* [1] the mover + multiplier kernel streams its two tiles in the other order in launches of odd parity: an evaluation launch right behind another one starts with the tile the XCD's L2 still holds (csrc/qn_sym2r.hip.h, ZIG-ZAG); 0: the same order in every launch -- the same bits */
     QN_OPT_TOUCH_H_ROWS = 21,              /* [8] n = 4096: the accept-reduce launch carries workgroups that only load the first `value` rows (of a wave's 16; 0, 4, 6, 8, 10, 12 or 16) of the tile the update-tile launch's workgroup of the same index streams first -- into the L2 of the XCD both run on (csrc/qn_sym2.hip.h, TOUCH WORKGROUPS); a NUMBER; loads only -- the same bits */
-    QN_OPT_TOUCH_Q_ROWS = 22               /* [6] ... and the update-reduce launch for the evaluation launch behind it (rows of Q's tiles) */
+    QN_OPT_TOUCH_Q_ROWS = 22,              /* [6] ... and the update-reduce launch for the evaluation launch behind it (rows of Q's tiles) */
+    QN_OPT_PNEWTON_REUSE_FACTOR = 23       /* [1] ProjectedNewton / SpectralProjectedNewton on a device quadratic: the Hessian's Cholesky factor is kept between iterations (the matrix does not change); 0: factorise in every iteration -- the same bits */
 } qn_option;
 int qn_solver_set_option(qn_solver* s, int option, int value);
 

@@ -61,10 +61,13 @@ inline void check(int status) { make_result(status).unwrap(); }
 class FuncEvalMultivariate {
     Floating f_;
     DVector g_;
+    std::optional<DVector> hessian_; // column-major n x n, like DMatrix (func_eval.rs:8)
   public:
     FuncEvalMultivariate(Floating f, DVector g) : f_(f), g_(std::move(g)) {}
     const Floating& f() const { return f_; }
     const DVector& g() const { return g_; }
+    FuncEvalMultivariate with_hessian(DVector h_colmajor) && { hessian_ = std::move(h_colmajor); return std::move(*this); } // func_eval.rs:27-30
+    const std::optional<DVector>& hessian() const { return hessian_; }
 };
 
 // one GPU (optionally one rank of a row-sharded group)
@@ -239,11 +242,20 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
         };
         struct Cb { Self* me; std::function<void(const Self&)>* f; } cb{this, callback ? &*callback : nullptr};
         auto cb_tramp = [](void* user, qn_solver*) { Cb* c = static_cast<Cb*>(user); (*c->f)(*c->me); };
+        auto htramp = [](void* user, const double* x, size_t n, double* h) -> int { // the Hessian part of the FuncEval (projected Newton solvers)
+            Ctx* c = static_cast<Ctx*>(user);
+            DVector xv(x, x + n);
+            FuncEvalMultivariate ev = (*c->o)(xv);
+            if (!ev.hessian() || ev.hessian()->size() != n * n) return 1; // "Hessian not available in the oracle"
+            for (size_t i = 0; i < n * n; ++i) h[i] = (*ev.hessian())[i];
+            return 0;
+        };
         qn_oracle o{};
         o.kind = QN_ORACLE_HOST;
         o.memoize = 0;
         o.host_fn = tramp;
         o.host_user = &octx;
+        if (METHOD == QN_PROJECTED_NEWTON || METHOD == QN_SPECTRAL_PROJECTED_NEWTON) o.host_hessian_fn = htramp;
         const int st = qn_minimize(h_, &line_search.ffi(), &o, max_iter_solver, max_iter_line_search,
                                    callback ? static_cast<qn_callback_fn>(cb_tramp) : nullptr, &cb);
         return make_result(st);
@@ -325,6 +337,44 @@ class SpectralProjectedGradient : public ProjectedSolver<QN_SPG> {
         return std::move(*this);
     }
     Floating lambda() const { Floating v = 0; int some = 0; check(qn_solver_spg_lambda(this->handle(), &v, &some)); return v; }
+};
+
+// newton/projected_newton.rs: new(grad_tol, x0, lower_bound, upper_bound); d = P(x - H^-1 g) - x, H^-1 g by one Cholesky factorisation (the
+// Hessian's lower triangle) and one solve on the GPU.  The closure returns FuncEvalMultivariate(f, g).with_hessian(h), or the oracle is a Quadratic.
+class ProjectedNewton : public ProjectedSolver<QN_PROJECTED_NEWTON> {
+  public:
+    using ProjectedSolver<QN_PROJECTED_NEWTON>::ProjectedSolver;
+    static ProjectedNewton new_(Floating grad_tol, const DVector& x0, DVector lb, DVector ub) {
+        return ProjectedNewton(grad_tol, x0, std::move(lb), std::move(ub));
+    }
+    bool has_converged(const FuncEvalMultivariate& eval) const { // projected_newton.rs:95-110
+        if (this->next_iterate_too_close() || this->gradient_next_iterate_too_close()) return true;
+        return ProjectedSolver<QN_PROJECTED_NEWTON>::has_converged(eval);
+    }
+    size_t newton_factorisations() const { size_t v = 0; check(qn_solver_newton_factorisations(this->handle(), &v)); return v; }
+};
+
+// newton/spn.rs: new(grad_tol, x0, &mut oracle, lower_bound, upper_bound); d = P(x - lambda H^-1 g) - x, lambda as in SpectralProjectedGradient
+class SpectralProjectedNewton : public ProjectedSolver<QN_SPECTRAL_PROJECTED_NEWTON> {
+  public:
+    template <class Oracle>
+    SpectralProjectedNewton(Floating grad_tol, const DVector& x0, Oracle&& oracle, DVector lower_bound, DVector upper_bound,
+                            Context& ctx = Context::default_context())
+        : ProjectedSolver<QN_SPECTRAL_PROJECTED_NEWTON>(grad_tol, x0, std::move(lower_bound), std::move(upper_bound), ctx) {
+        GLLQuadratic ls(1e-4, 1);
+        Result r = this->minimize(ls, oracle, 0, 0); // no iteration: the constructor's evaluation only (spn.rs:40-46)
+        if (r.is_err() && r.unwrap_err().kind != SolverError::MaxIterReached) r.unwrap();
+    }
+    template <class Oracle>
+    static SpectralProjectedNewton new_(Floating grad_tol, const DVector& x0, Oracle&& oracle, DVector lb, DVector ub) {
+        return SpectralProjectedNewton(grad_tol, x0, oracle, std::move(lb), std::move(ub));
+    }
+    SpectralProjectedNewton with_lambdas(Floating lambda_min, Floating lambda_max) && { // spn.rs:23-27
+        check(qn_solver_set_spg_lambdas(this->handle(), lambda_min, lambda_max));
+        return std::move(*this);
+    }
+    Floating lambda() const { Floating v = 0; int some = 0; check(qn_solver_spg_lambda(this->handle(), &v, &some)); return v; }
+    size_t newton_factorisations() const { size_t v = 0; check(qn_solver_newton_factorisations(this->handle(), &v)); return v; }
 };
 
 } // namespace optimization_solvers

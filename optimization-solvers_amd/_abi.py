@@ -9,7 +9,7 @@ LIB_PATH = os.environ.get("QN_HIP_LIB") or os.path.join(_HERE, "lib", "libqn_hip
 OK, MAX_ITER_REACHED, OUT_OF_DOMAIN, ERROR_INPUT_PARAMS, ABNORMAL_TERMINATION = range(5)
 LS_MORETHUENTE, LS_BACKTRACKING, LS_MORETHUENTE_B, LS_BACKTRACKING_B, LS_GLL_QUADRATIC = 0, 1, 2, 3, 4
 ORACLE_HOST, ORACLE_DEVICE_FN, ORACLE_OBJECTIVE = 0, 1, 2
-BFGS, DFP, GRADIENT_DESCENT, NEWTON, SR1, SPG, PROJECTED_GRADIENT = 0, 1, 2, 3, 4, 5, 6
+BFGS, DFP, GRADIENT_DESCENT, NEWTON, SR1, SPG, PROJECTED_GRADIENT, PROJECTED_NEWTON, SPECTRAL_PROJECTED_NEWTON = 0, 1, 2, 3, 4, 5, 6, 7, 8
 UNIQUE_ID_BYTES = 128
 
 dp = C.POINTER(C.c_double)
@@ -57,7 +57,7 @@ class Stats(C.Structure):
                 ("t_newton_ms", C.c_double), ("n_newton_timed", C.c_uint64), ("newton_lu_sync_timeouts", C.c_uint64)]
 
 
-PATH_FUSED, PATH_SYM, PATH_SYM_GENERIC, PATH_PIPELINED, PATH_SYM2, PATH_TILES1, PATH_VECTOR = 1, 2, 4, 8, 16, 32, 64
+PATH_FUSED, PATH_SYM, PATH_SYM_GENERIC, PATH_PIPELINED, PATH_SYM2, PATH_TILES1, PATH_VECTOR, PATH_PNEWTON = 1, 2, 4, 8, 16, 32, 64, 128
 
 
 # every symbol include/qn_hip.h declares: (name, restype, argtypes)
@@ -108,6 +108,7 @@ SYMBOLS = [
     ("qn_solver_set_bounds", C.c_int, [C.c_void_p, dp, dp]),
     ("qn_solver_set_spg_lambdas", C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     ("qn_solver_spg_lambda", C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int)]),
+    ("qn_solver_newton_factorisations", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
     ("qn_minimize", C.c_int, [C.c_void_p, C.POINTER(LineSearchStruct), C.POINTER(OracleStruct), C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("qn_compute_step_len", C.c_int, [C.c_void_p, C.POINTER(LineSearchStruct), dp, C.c_double, dp, dp, C.c_size_t, C.POINTER(OracleStruct), C.c_size_t,
                              C.POINTER(C.c_double)]),

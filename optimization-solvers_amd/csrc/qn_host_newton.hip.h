@@ -373,13 +373,10 @@ static int enqueue_newton_lu(qn_solver* s, const double* hsrc, size_t ld_src) {
     return QN_OK;
 }
 
-static int enqueue_newton(qn_solver* s, const qn_oracle* o, qn_objective* obj) {
-    qn_context* c = s->ctx;
-    hipStream_t st = c->stream;
-    QNCHK(newton_alloc(s));
-    const int n = (int)s->n, n64 = (int)s->newton_n64;
-    const size_t ld = s->newton_n64;
-    // the Hessian at x_k: a device objective's own matrix, or the host closure's (uploaded)
+// The Hessian at x_k on the device, row-major: a device objective's own matrix, or the host closure's (uploaded).  `symmetric`: H == H' bit for bit.
+static int newton_stage_hessian(qn_solver* s, const qn_oracle* o, qn_objective* obj, const double** hsrc_out, size_t* ld_src_out, bool* symmetric_out) {
+    hipStream_t st = s->ctx->stream;
+    const int n = (int)s->n;
     const double* hsrc = nullptr;
     size_t ld_src = 0;
     bool symmetric = true; // the Cholesky path reads the lower triangle only: it needs H == H' bit for bit
@@ -400,13 +397,17 @@ static int enqueue_newton(qn_solver* s, const qn_oracle* o, qn_objective* obj) {
         HIPCHK(hipMemcpyAsync(s->newton_hsrc, hr, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, st));
         hsrc = s->newton_hsrc; ld_src = (size_t)n;
     }
-    HIPCHK(hipMemsetAsync(s->newton_fail, 0, 2 * sizeof(int), st));
-    if (s->hctl->small_n) { // reference-order arithmetic, one thread
-        hipLaunchKernelGGL(newton_small_kernel, dim3(1), dim3(64), 0, st, hsrc, ld_src, n, s->V.g, s->V.d, s->V.s, s->newton_fail);
-        HIPCHK(hipGetLastError());
-        return QN_OK;
-    }
-    if (!symmetric || s->newton_force_lu) return enqueue_newton_lu(s, hsrc, ld_src);
+    *hsrc_out = hsrc; *ld_src_out = ld_src; *symmetric_out = symmetric;
+    return QN_OK;
+}
+
+// The blocked Cholesky of the staged Hessian, lower triangle in place in newton_w (and the diagonal blocks' inverses): the factor half of
+// Newton's direction, shared with ProjectedNewton / SpectralProjectedNewton (qn_host_vec.hip.h).  A bad pivot sets newton_fail[0].
+static int newton_chol_factor(qn_solver* s, const double* hsrc, size_t ld_src) {
+    qn_context* c = s->ctx;
+    hipStream_t st = c->stream;
+    const int n = (int)s->n, n64 = (int)s->newton_n64;
+    const size_t ld = s->newton_n64;
     s->newton_chol_runs++;
     hipLaunchKernelGGL(newton_stage_kernel, dim3(2048), dim3(256), 0, st, s->newton_w, ld, n, n64, hsrc, ld_src, 1); // (the lower block triangle)
     // blocked right-looking Cholesky, lower triangle in place.  Outer blocks of 256 columns: each 64-column panel is
@@ -550,6 +551,26 @@ static int enqueue_newton(qn_solver* s, const qn_oracle* o, qn_objective* obj) {
     if (last_f >= 0) HIPCHK(hipStreamWaitEvent(st, c->la_events[2 * last_f + 1], 0));
     HIPCHK(hipGetLastError());
     if (s->newton_big) QNCHK(newton_build_block_inverses(s));
+    return QN_OK;
+}
+
+static int enqueue_newton(qn_solver* s, const qn_oracle* o, qn_objective* obj) {
+    qn_context* c = s->ctx;
+    hipStream_t st = c->stream;
+    QNCHK(newton_alloc(s));
+    const int n = (int)s->n, n64 = (int)s->newton_n64;
+    const double* hsrc = nullptr;
+    size_t ld_src = 0;
+    bool symmetric = true; // the Cholesky path reads the lower triangle only: it needs H == H' bit for bit
+    QNCHK(newton_stage_hessian(s, o, obj, &hsrc, &ld_src, &symmetric));
+    HIPCHK(hipMemsetAsync(s->newton_fail, 0, 2 * sizeof(int), st));
+    if (s->hctl->small_n) { // reference-order arithmetic, one thread
+        hipLaunchKernelGGL(newton_small_kernel, dim3(1), dim3(64), 0, st, hsrc, ld_src, n, s->V.g, s->V.d, s->V.s, s->newton_fail);
+        HIPCHK(hipGetLastError());
+        return QN_OK;
+    }
+    if (!symmetric || s->newton_force_lu) return enqueue_newton_lu(s, hsrc, ld_src);
+    QNCHK(newton_chol_factor(s, hsrc, ld_src));
     // d = -(H^-1 g) ; z = H^-1 d
     double* x1 = s->newton_x;
     double* x2 = s->newton_x + n64;

@@ -96,6 +96,11 @@ struct qn_solver {
     std::vector<double> newton_hhost;
     QnVecCtl *vctl = nullptr, *hvctl = nullptr; // QN_SPG / QN_PROJECTED_GRADIENT: device control block, pinned host copy (lambda, GLL history, memo)
     double* vpart = nullptr;                    // ... and the per-workgroup partials of their vector kernels
+    // QN_PROJECTED_NEWTON / QN_SPECTRAL_PROJECTED_NEWTON: the factor in newton_w belongs to the device objective with this serial (0: to none);
+    // QN_OPT_PNEWTON_REUSE_FACTOR; Cholesky factorisations enqueued by the last qn_minimize
+    uint64_t pn_factor_serial = 0;
+    int pn_reuse = 1;
+    uint64_t pn_factorisations = 0;
     double* bounds_block = nullptr; // lb, ub (solver), llb, lub (bounded line search): 4 n_pad vectors
     int bounded = 0;
     double* fused_block = nullptr; // X0[2], S0[2], G, GT, Y, UN, UP, VV (10 n_pad vectors)
@@ -381,7 +386,7 @@ extern "C" int qn_solver_create(qn_context* ctx, int method, double tol, const d
     if (!ctx || !x0_host || !out || n == 0) return fail(QN_ERROR_INPUT_PARAMS, "null argument or n == 0");
     if (method != QN_BFGS && method != QN_DFP && method != QN_GRADIENT_DESCENT && method != QN_NEWTON && method != QN_SR1 && !vec_method(method))
         return fail(QN_ERROR_INPUT_PARAMS, "unknown method");
-    if (vec_method(method) && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient run on one rank");
+    if (vec_method(method) && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient / projected Newton run on one rank");
     if (n > (size_t)1 << 30) return fail(QN_ERROR_INPUT_PARAMS, "n too large");
     HIPCHK(hipSetDevice(ctx->device));
     qn_solver* s = new qn_solver();
@@ -513,6 +518,7 @@ extern "C" int qn_solver_set_option(qn_solver* s, int option, int value) {
     case QN_OPT_LU_FORCE_WAIT_EXPIRY: s->newton_lu_force_timeout = on ? 1 : 0; return QN_OK;
     case QN_OPT_BTB_PROJECT_IN_EVAL: s->no_projfold = !on; return QN_OK;
     case QN_OPT_EVAL_ZIGZAG: s->zig = on ? 1 : 0; return QN_OK;
+    case QN_OPT_PNEWTON_REUSE_FACTOR: s->pn_reuse = on ? 1 : 0; s->pn_factor_serial = 0; return QN_OK;
     case QN_OPT_TOUCH_H_ROWS:
     case QN_OPT_TOUCH_Q_ROWS:
         if (value != 0 && value != 4 && value != 6 && value != 8 && value != 10 && value != 12 && value != 16) return fail(QN_ERROR_INPUT_PARAMS, "rows per wave to touch: 0, 4, 6, 8, 10, 12 or 16");

@@ -15,7 +15,9 @@ extern "C" void qn_gll_quadratic_with_sigmas(qn_linesearch* ls, double sigma1, d
     ls->delta_min = sigma1; ls->delta_max = sigma2;
 }
 
-static bool vec_method(int method) { return method == QN_SPG || method == QN_PROJECTED_GRADIENT; }
+static bool pn_method(int method) { return method == QN_PROJECTED_NEWTON || method == QN_SPECTRAL_PROJECTED_NEWTON; }
+static bool spectral_method(int method) { return method == QN_SPG || method == QN_SPECTRAL_PROJECTED_NEWTON; }
+static bool vec_method(int method) { return method == QN_SPG || method == QN_PROJECTED_GRADIENT || pn_method(method); }
 static int vec_grid(size_t np) { // a function of n alone: four 16-byte accesses per thread until 4 workgroups per CU are out
     const size_t per = (size_t)QN_VEC_TPB * 2 * 4;
     return (int)std::min<size_t>(QN_VEC_MAXG, std::max<size_t>(1, (np + per - 1) / per));
@@ -38,17 +40,23 @@ static void vec_state_reset(qn_solver* s) { // back to the state right after ::n
     if (!s->hvctl) return;
     QnVecCtl* h = s->hvctl;
     h->has_lambda = 0; h->lambda = 0.0; h->have_eval = 0; h->ring_len = 0; h->k = 0; h->n_iter = 0;
+    h->has_sy = 0; h->s_norm = 0.0; h->y_norm = 0.0; // (the Cholesky factor of a device quadratic's Hessian is kept: it is keyed on the objective)
 }
 
 extern "C" int qn_solver_set_spg_lambdas(qn_solver* s, double lambda_min, double lambda_max) { // with_lambdas, spg.rs:23-27
     if (!s) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
-    if (s->method != QN_SPG) return fail(QN_ERROR_INPUT_PARAMS, "lambda bounds belong to a SpectralProjectedGradient solver");
+    if (!spectral_method(s->method)) return fail(QN_ERROR_INPUT_PARAMS, "lambda bounds belong to a SpectralProjectedGradient / SpectralProjectedNewton solver");
     s->hvctl->lambda_min = lambda_min; s->hvctl->lambda_max = lambda_max; // (the current lambda is not clamped again, as in the reference)
+    return QN_OK;
+}
+extern "C" int qn_solver_newton_factorisations(qn_solver* s, size_t* out) {
+    if (!s || !out) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
+    *out = (size_t)s->pn_factorisations;
     return QN_OK;
 }
 extern "C" int qn_solver_spg_lambda(qn_solver* s, double* out, int* is_some) {
     if (!s) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
-    if (s->method != QN_SPG) return fail(QN_ERROR_INPUT_PARAMS, "lambda belongs to a SpectralProjectedGradient solver");
+    if (!spectral_method(s->method)) return fail(QN_ERROR_INPUT_PARAMS, "lambda belongs to a SpectralProjectedGradient / SpectralProjectedNewton solver");
     if (is_some) *is_some = s->hvctl->has_lambda;
     if (out) *out = s->hvctl->lambda;
     return QN_OK;
@@ -57,6 +65,7 @@ extern "C" int qn_solver_spg_lambda(qn_solver* s, double* out, int* is_some) {
 // ComputeDirection::compute_direction on its own: P(x - lambda g) - x (spg.rs:76-86), P(x - g) - x (projected_gradient_descent.rs:51-60)
 static int vec_compute_direction(qn_solver* s, const double* g_host, double* d_host) {
     const size_t n = s->n, np = s->T.n_pad;
+    if (pn_method(s->method)) return fail(QN_ERROR_INPUT_PARAMS, "the projected Newton direction needs the oracle's Hessian: use qn_minimize");
     if (s->method == QN_SPG && !s->hvctl->has_lambda) return fail(QN_ERROR_INPUT_PARAMS, "lambda0 needs the oracle: the first qn_minimize evaluates it");
     std::vector<double> x(n), lb(n), ub(n);
     QNCHK(qn_solver_get_x(s, x.data()));
@@ -121,6 +130,56 @@ static int vec_enqueue_eval(VecRun& r) {
     return QN_OK;
 }
 
+// ProjectedNewton / SpectralProjectedNewton, phase QN_VP_NSOLVE: z = H^-1 g into V.y -- `hessian.cholesky().unwrap().solve(eval.g())`
+// (projected_newton.rs:75, spn.rs:86): ONE factorisation (newton_chol_factor, the lower triangle only) and ONE solve.  The Hessian of a device
+// quadratic is the same matrix in every iteration: its factor in newton_w (and the block inverses) is kept, keyed on the objective's serial,
+// and later iterations run the solve alone -- the same bits as factorising again (QN_OPT_PNEWTON_REUSE_FACTOR 0 does that).  A host closure's
+// Hessian is asked for, and factorised, in every iteration that computes a direction.  No LU fallback: the reference unwraps.
+static int pn_enqueue_solve(VecRun& r) {
+    qn_solver* s = r.s;
+    hipStream_t st = s->ctx->stream;
+    ProfScope ps(s, KC_NEWTON);
+    const int n = (int)s->n, n64 = (int)s->newton_n64;
+    const uint64_t serial = r.obj ? r.obj->serial : 0;
+    const bool small = s->n <= QN_SMALL_N;
+    const bool reuse = !small && s->pn_reuse && serial != 0 && s->pn_factor_serial == serial;
+    if (!reuse) {
+        const double* hsrc = nullptr;
+        size_t ld_src = 0;
+        bool symmetric = true; // (not consulted: only the lower triangle is read, as nalgebra's Cholesky does)
+        s->pn_factor_serial = 0;
+        QNCHK(newton_stage_hessian(s, r.o, r.obj, &hsrc, &ld_src, &symmetric));
+        HIPCHK(hipMemsetAsync(s->newton_fail, 0, 2 * sizeof(int), st));
+        s->pn_factorisations++;
+        if (small) {
+            hipLaunchKernelGGL(pn_small_kernel, dim3(1), dim3(64), 0, st, hsrc, ld_src, n, (int)s->T.n_pad, s->V.g, s->V.y, s->newton_fail);
+            s->stats.launches++;
+        } else {
+            QNCHK(newton_chol_factor(s, hsrc, ld_src));
+        }
+    }
+    if (!small) {
+        double* x1 = s->newton_x;
+        double* x2 = s->newton_x + n64;
+        const dim3 vg(std::min(1024, (n64 + 255) / 256)), vb(256);
+        hipLaunchKernelGGL(newton_vec_kernel, vg, vb, 0, st, x1, s->V.g, n, n64, 1.0);
+        QNCHK(newton_tri_solve(s, x1, x2));
+        hipLaunchKernelGGL(newton_vec_kernel, vg, vb, 0, st, s->V.y, x1, n, s->T.n_pad, 1.0);
+        s->stats.launches += 2 + (s->newton_big ? 0 : 2 * (uint64_t)(n64 / QN_NB));
+    }
+    HIPCHK(hipGetLastError());
+    if (reuse) return QN_OK; // (the kept factor was checked when it was made)
+    int chol_failed = 0; // read here, behind everything enqueued, as Newton's direction does
+    HIPCHK(hipMemcpyAsync(&chol_failed, s->newton_fail, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    s->stats.host_syncs++;
+    if (chol_failed)
+        return fail(QN_ABNORMAL_TERMINATION, "the Hessian's Cholesky factorisation failed (its lower triangle is not positive definite): the reference "
+                                             "unwraps here and there is no LU fallback; x is left at x_k");
+    if (!small && s->pn_reuse && serial != 0) s->pn_factor_serial = serial;
+    return QN_OK;
+}
+
 #define VEC_LAUNCH(kernel, grid)                                                                    \
     do {                                                                                            \
         ProfScope ps(s, KC_CTL);                                                                    \
@@ -133,7 +192,8 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
                         qn_callback_fn callback, void* callback_user, int ls_only, double ls_f0) {
     qn_context* c = s->ctx;
     HIPCHK(hipSetDevice(c->device));
-    if (c->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient run on one rank");
+    if (c->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient / projected Newton run on one rank");
+    const bool pn = pn_method(s->method);
     VecRun r{s, o, nullptr, {}};
     if (o->kind == QN_ORACLE_OBJECTIVE) {
         if (!o->objective) return fail(QN_ERROR_INPUT_PARAMS, "objective is null");
@@ -151,6 +211,11 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         return fail(QN_ERROR_INPUT_PARAMS, "unknown line search");
     if (ls->kind == QN_LS_GLL_QUADRATIC && (ls->_pad < 1 || ls->_pad > QN_GLL_MAX_M))
         return fail(QN_ERROR_INPUT_PARAMS, "GLLQuadratic: the look-back m must be 1 .. 64 (the history is a fixed device ring)");
+    if (pn) {
+        if (ls_only) return fail(QN_ERROR_INPUT_PARAMS, "compute_step_len runs on a first-order solver");
+        if (!(r.obj && r.obj->kind == OBJ_QUADRATIC) && !(o->kind == QN_ORACLE_HOST && o->host_hessian_fn))
+            return fail(QN_ERROR_INPUT_PARAMS, "Hessian not available in the oracle"); // projected_newton.rs:73, spn.rs:85 .expect(...)
+    }
     QNCHK(vec_state_alloc(s));
     hipStream_t st = c->stream;
     const size_t np = s->T.n_pad;
@@ -175,7 +240,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     s->warm_obj = 0;
     bool done = false;
     if (ls_only) { h->f_cur = ls_f0; h->have_eval = 1; h->phase = QN_VP_LS_ONLY; }
-    else if (s->method == QN_SPG && !h->has_lambda) h->phase = h->have_eval ? QN_VP_DIR : QN_VP_EVAL_X; // spg.rs:40-46, whatever the cap
+    else if (spectral_method(s->method) && !h->has_lambda) h->phase = h->have_eval ? QN_VP_DIR : QN_VP_EVAL_X; // spg.rs:40-46, whatever the cap
     else if (h->max_iter <= 0) { h->status = QN_MAX_ITER_REACHED; h->phase = QN_VP_DONE; done = true; }  // ls_solver.rs:78
     else h->phase = h->have_eval ? QN_VP_DIR : QN_VP_EVAL_X;
     HIPCHK(hipMemcpyAsync(s->vctl, h, sizeof(QnVecCtl), hipMemcpyHostToDevice, st));
@@ -184,12 +249,35 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     QnVecArgs& a = r.a;
     a.x = s->V.x; a.g = s->V.g; a.d = s->V.d; a.xt = s->V.xt; a.gt = s->V.gt;
     a.lb = s->V.lb; a.ub = s->V.ub; a.llb = s->V.llb; a.lub = s->V.lub;
-    a.part = s->vpart; a.ctl = s->vctl; a.f_dev = s->f_dev; a.trace = s->V.trace; a.xtrace = s->V.xtrace;
+    a.z = s->V.y; a.part = s->vpart; a.ctl = s->vctl; a.f_dev = s->f_dev; a.trace = s->V.trace; a.xtrace = s->V.xtrace;
     a.n = (int)s->n; a.np = (int)np; a.G = vec_grid(np);
     const int G = a.G;
     const bool host_oracle = o->kind == QN_ORACLE_HOST;
     const size_t vb = np * sizeof(double);
     int64_t k_seen = 0;
+    s->pn_factorisations = 0;
+    // the run's bookkeeping, also when a batch fails after some iterations (a failed Cholesky, a closure's error): k, the counters, the
+    // path and s_norm / y_norm speak of this call, not of the one before
+    auto epilogue = [&]() {
+        s->hctl->k = h->k; s->hctl->n_iterations = h->n_iter; s->hctl->ls_result = h->ls_result;
+        s->hctl->have_cur_eval = h->have_eval;
+        s->warm_obj = (h->have_eval && h->memoize && serial != 0 && !ls_only) ? serial : 0;
+        s->stats.iterations = h->n_iter;
+        s->stats.oracle_calls = h->n_calls;
+        s->stats.oracle_evals = h->n_evals;
+        s->stats.h_passes = 0; s->stats.h_bytes = 0; s->stats.matrix_bytes_per_pass = 0;
+        s->stats.obj_bytes = 0;
+        if (r.obj && r.obj->kind == OBJ_QUADRATIC) s->stats.obj_bytes = h->n_evals * (uint64_t)r.obj->T.rpr * (uint64_t)r.obj->T.n_pad * 8ull;
+        s->stats.total_minimize_calls++;
+        s->stats.total_iterations += s->stats.iterations;
+        s->stats.total_oracle_calls += s->stats.oracle_calls;
+        s->stats.total_oracle_evals += s->stats.oracle_evals;
+        s->stats.total_obj_bytes += s->stats.obj_bytes;
+        s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u);
+        if (s->method == QN_PROJECTED_NEWTON) { // s_norm() / y_norm() (projected_newton.rs:10-11) through the getters every solver answers
+            s->hctl->has_s_norm = h->has_sy; s->hctl->has_y_norm = h->has_sy; s->hctl->s_norm = h->s_norm; s->hctl->y_norm = h->y_norm;
+        }
+    };
 
     while (!done) {
         int ph = h->phase;
@@ -206,11 +294,26 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         if (ph == QN_VP_EVAL_X || ph == QN_VP_DIR || ph == QN_VP_LS_ONLY) {
             VEC_LAUNCH(vec_dir_kernel, G);
             VEC_LAUNCH(vec_top_kernel, 1);
-            if (s->method == QN_SPG && !h->has_lambda && !ls_only) { // the constructor's batch (spg.rs:40-46) ends here: no trial is wanted yet
+            // the constructor's batch (spg.rs:40-46, spn.rs:40-46) ends here: no trial is wanted yet.  So does the second-order variants' loop top
+            // when it ran as a batch of its own (the first iteration, or an oracle that is not memoised): the factorisation is enqueued only
+            // for an iteration this peek has seen through the convergence test (QN_VP_NSOLVE)
+            if ((spectral_method(s->method) && !h->has_lambda && !ls_only) || pn) {
                 QNCHK(vec_peek(r, false));
                 done = h->phase == QN_VP_DONE;
                 continue;
             }
+        } else if (ph == QN_VP_NSOLVE) {
+            // the one n x n work matrix (Newton's), for the first iteration that wants a direction: a converged start, a cap of 0 and the
+            // constructor's lambda0 batch never come here
+            QNCHK(newton_alloc(s));
+            const int rc = pn_enqueue_solve(r);
+            if (rc != QN_OK) { // (the failing iteration's loop top ran: the control block on the host is that batch's, x is x_k)
+                h->have_eval = 0; // the next call evaluates x_k afresh
+                epilogue();
+                return rc;
+            }
+            VEC_LAUNCH(vec_dir_kernel, G);
+            VEC_LAUNCH(vec_top_kernel, 1);
         } else if (ph != QN_VP_TRIAL && ph != QN_VP_REEVAL) {
             return fail(QN_ABNORMAL_TERMINATION, "vector pump: control block in an unexpected phase");
         }
@@ -234,21 +337,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         done = h->phase == QN_VP_DONE;
     }
     const int status = h->status;
-    s->hctl->k = h->k; s->hctl->n_iterations = h->n_iter; s->hctl->ls_result = h->ls_result;
-    s->hctl->have_cur_eval = h->have_eval;
-    s->warm_obj = (h->have_eval && h->memoize && serial != 0 && !ls_only) ? serial : 0;
-    s->stats.iterations = h->n_iter;
-    s->stats.oracle_calls = h->n_calls;
-    s->stats.oracle_evals = h->n_evals;
-    s->stats.h_passes = 0; s->stats.h_bytes = 0; s->stats.matrix_bytes_per_pass = 0;
-    s->stats.obj_bytes = 0;
-    if (r.obj && r.obj->kind == OBJ_QUADRATIC) s->stats.obj_bytes = h->n_evals * (uint64_t)r.obj->T.rpr * (uint64_t)r.obj->T.n_pad * 8ull;
-    s->stats.total_minimize_calls++;
-    s->stats.total_iterations += s->stats.iterations;
-    s->stats.total_oracle_calls += s->stats.oracle_calls;
-    s->stats.total_oracle_evals += s->stats.oracle_evals;
-    s->stats.total_obj_bytes += s->stats.obj_bytes;
-    s->stats.path = QN_PATH_VECTOR;
+    epilogue();
     if (status < 0 || status == QN_ABNORMAL_TERMINATION) return fail(QN_ABNORMAL_TERMINATION, "vector pump: the machine stopped without a status");
     return status;
 }

@@ -21,7 +21,7 @@
 
 #define QN_VEC_TPB 256
 #define QN_VEC_MAXG 1024 // 4 workgroups per CU on 256 CUs
-#define QN_VEC_NPART 4
+#define QN_VEC_NPART 6 // (4, 5: the second-order variants' accept kernel -- ||pg(x_next)||_inf and y.y)
 #define QN_GLL_MAX_M 64
 
 enum QnVecPhase : int32_t {
@@ -32,8 +32,15 @@ enum QnVecPhase : int32_t {
     QN_VP_REEVAL = 4, // SPG's update wants the oracle at x_next = x + t d, which no trial evaluated (spg.rs:130)
     QN_VP_ACCEPT = 5, // the step is decided: accept and post kernels
     QN_VP_LS_ONLY = 6, // qn_compute_step_len: g.d for the caller's direction, then the line search alone
-    QN_VP_DONE = 7
+    QN_VP_DONE = 7,
+    QN_VP_NSOLVE = 8 // ProjectedNewton / SpectralProjectedNewton: the loop top let the iteration through; the host enqueues z = H^-1 g, then the direction
 };
+
+// the second-order variants (newton/projected_newton.rs, newton/spn.rs): the same machine, with z = H^-1 g where the first-order family has g
+__device__ __forceinline__ bool vec_newton(int method) { return method == QN_PROJECTED_NEWTON || method == QN_SPECTRAL_PROJECTED_NEWTON; }
+__device__ __forceinline__ bool vec_spectral(int method) { return method == QN_SPG || method == QN_SPECTRAL_PROJECTED_NEWTON; }
+// update_next_iterate calls the oracle at the accepted point, for y (spg.rs:130, spn.rs:135, projected_newton.rs:134)
+__device__ __forceinline__ bool vec_needs_y(int method) { return vec_spectral(method) || method == QN_PROJECTED_NEWTON; }
 
 struct QnVecCtl {
     // ---- configuration (host, per call) ----
@@ -60,10 +67,14 @@ struct QnVecCtl {
     int32_t tr_n_evals, tr_ls_iters;
     // ---- counters of this call ----
     uint64_t n_calls, n_evals, n_iter;
+    // ---- ProjectedNewton: s_norm / y_norm (projected_newton.rs:10-11; survive calls, None after ::new) ----
+    double s_norm, y_norm;
+    int32_t has_sy, _pad2;
 };
 
 struct QnVecArgs {
     double *x, *g, *d, *xt, *gt;
+    const double* z; // H^-1 g of the second-order variants (phase QN_VP_NSOLVE)
     const double *lb, *ub, *llb, *lub;
     double* part; // [QN_VEC_NPART][QN_VEC_MAXG]
     QnVecCtl* ctl;
@@ -81,9 +92,12 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_dir_kernel(const QnVecArgs a) 
     __shared__ double lds[64];
     const QnVecCtl* c = a.ctl;
     const int ph = c->phase;
-    if (ph != QN_VP_EVAL_X && ph != QN_VP_DIR && ph != QN_VP_LS_ONLY) return;
-    const bool scaled = c->method == QN_SPG && c->has_lambda;
+    if (ph != QN_VP_EVAL_X && ph != QN_VP_DIR && ph != QN_VP_LS_ONLY && ph != QN_VP_NSOLVE) return;
+    const bool scaled = vec_spectral(c->method) && c->has_lambda;
     const double lam = c->lambda;
+    // projected_newton.rs:75-77, spn.rs:86-88: the step is z = H^-1 g, or lambda z.  (At their loop top -- QN_VP_EVAL_X / QN_VP_DIR -- this
+    // kernel serves the projected gradient's norm, and P(x0 - g0) - x0 for lambda0, spn.rs:40-46.)
+    const bool nsolve = ph == QN_VP_NSOLVE;
     double pg = 0.0, dm = 0.0, gd[1] = {0.0};
     const int nv = a.np >> 1;
     for (int j = blockIdx.x * QN_VEC_TPB + threadIdx.x; j < nv; j += a.G * QN_VEC_TPB) {
@@ -93,7 +107,8 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_dir_kernel(const QnVecArgs a) 
             d = ld2(a.d + 2 * j);
         } else {
             const v2d x = ld2(a.x + 2 * j), lo = ld2(a.lb + 2 * j), hi = ld2(a.ub + 2 * j);
-            const double s0 = scaled ? lam * g.x : g.x, s1 = scaled ? lam * g.y : g.y;
+            const v2d w = nsolve ? ld2(a.z + 2 * j) : g; // (the first-order family reads g once, as before)
+            const double s0 = scaled ? lam * w.x : w.x, s1 = scaled ? lam * w.y : w.y;
             const double u0 = x.x - s0, u1 = x.y - s1;
             d.x = fmin(fmax(u0, lo.x), hi.x) - x.x;
             d.y = fmin(fmax(u1, lo.y), hi.y) - x.y;
@@ -139,7 +154,7 @@ __device__ __forceinline__ void vec_ls_return(QnVecCtl* c, bool evaluated) {
     c->ls_result = c->t;
     if (c->ls_only) { c->status = QN_OK; c->phase = QN_VP_DONE; return; }
     c->gt_valid = evaluated ? 1 : 0;
-    if (c->method == QN_SPG) {
+    if (vec_needs_y(c->method)) {
         if (evaluated && c->memoize) { c->n_calls++; c->tr_n_evals++; c->phase = QN_VP_ACCEPT; } // spg.rs:130 at the point the search accepted
         else { c->gt_valid = 0; c->phase = QN_VP_REEVAL; }
     } else {
@@ -148,30 +163,41 @@ __device__ __forceinline__ void vec_ls_return(QnVecCtl* c, bool evaluated) {
     }
 }
 
+// the loop top of ls_solver.rs:79-90 behind the oracle call (thread 0): true when the run ends here
+__device__ __forceinline__ bool vec_loop_top(QnVecCtl* c, double pg) {
+    c->tr_n_evals++;
+    if (isnan(c->f_cur) || isinf(c->f_cur)) { c->status = QN_OUT_OF_DOMAIN; c->phase = QN_VP_DONE; return true; } // ls_solver.rs:37-40
+    c->pgnorm = pg;
+    if (c->method == QN_PROJECTED_NEWTON && c->has_sy) { // projected_newton.rs:98-103: s_norm, then y_norm, then the projected gradient
+        if (c->s_norm < c->tol) { c->status = QN_OK; c->phase = QN_VP_DONE; return true; }
+        if (c->y_norm < c->tol) { c->status = QN_OK; c->phase = QN_VP_DONE; return true; }
+    }
+    if (pg < c->tol) { c->status = QN_OK; c->phase = QN_VP_DONE; return true; } // spg.rs:89-92
+    c->tr_f = c->f_cur; c->tr_gnorm = pg;
+    return false;
+}
+
 __global__ __launch_bounds__(QN_VEC_TPB) void vec_top_kernel(const QnVecArgs a) {
     __shared__ double lds[64];
     QnVecCtl* c = a.ctl;
     const int ph = c->phase;
-    if (ph != QN_VP_EVAL_X && ph != QN_VP_DIR && ph != QN_VP_LS_ONLY) return;
+    if (ph != QN_VP_EVAL_X && ph != QN_VP_DIR && ph != QN_VP_LS_ONLY && ph != QN_VP_NSOLVE) return;
     const double pg = vec_max_parts(a.part, 0, a.G, lds);
     const double gd = vec_sum_parts(a.part, 1, a.G, lds);
     const double dm = vec_max_parts(a.part, 2, a.G, lds);
     if (threadIdx.x != 0) return;
     if (ph == QN_VP_EVAL_X) { c->f_cur = *a.f_dev; c->have_eval = 1; c->n_evals++; }
-    if (ph != QN_VP_LS_ONLY) {
+    if (ph != QN_VP_LS_ONLY && ph != QN_VP_NSOLVE) {
         c->n_calls++;
-        if (c->method == QN_SPG && !c->has_lambda) { // spg.rs:40-46: the constructor's call; d was formed with lambda = 1
+        if (vec_spectral(c->method) && !c->has_lambda) { // spg.rs:40-46: the constructor's call; d was formed with lambda = 1
             c->lambda = fmax(fmin(1.0 / dm, c->lambda_max), c->lambda_min);
             c->has_lambda = 1;
             if (c->max_iter <= 0) { c->status = QN_MAX_ITER_REACHED; c->phase = QN_VP_DONE; return; }
             c->phase = c->memoize ? QN_VP_DIR : QN_VP_EVAL_X;
             return;
         }
-        c->tr_n_evals++;
-        if (isnan(c->f_cur) || isinf(c->f_cur)) { c->status = QN_OUT_OF_DOMAIN; c->phase = QN_VP_DONE; return; } // ls_solver.rs:37-40
-        c->pgnorm = pg;
-        if (pg < c->tol) { c->status = QN_OK; c->phase = QN_VP_DONE; return; } // spg.rs:89-92
-        c->tr_f = c->f_cur; c->tr_gnorm = pg;
+        if (vec_loop_top(c, pg)) return;
+        if (vec_newton(c->method)) { c->phase = QN_VP_NSOLVE; return; } // the direction needs the factorisation: the host enqueues it for this phase only
     }
     c->gd = gd;
     if (c->ls_kind == QN_LS_GLL_QUADRATIC) { // gll_quadratic.rs:62-64: append_new_f, then f_max once
@@ -279,6 +305,8 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_accept_kernel(const QnVecArgs 
     const int64_t row = (int64_t)c->n_iter;
     const bool xtr = c->trace_x && a.xtrace && row < c->trace_cap;
     double acc[2] = {0.0, 0.0};
+    const bool second = vec_newton(c->method) && have_gt; // also y.y, and the projected gradient at (x_next, g(x_next)) for the next loop top
+    double yy[1] = {0.0}, pgn = 0.0;
     const int nv = a.np >> 1;
     for (int j = blockIdx.x * QN_VEC_TPB + threadIdx.x; j < nv; j += a.G * QN_VEC_TPB) {
         const v2d x = ld2(a.x + 2 * j), d = ld2(a.d + 2 * j);
@@ -295,6 +323,14 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_accept_kernel(const QnVecArgs 
             acc[0] = acc[0] + s0 * y0;
             acc[0] = acc[0] + s1 * y1;
             st2(a.g + 2 * j, gt);
+            if (second) {
+                yy[0] = yy[0] + y0 * y0;
+                yy[0] = yy[0] + y1 * y1;
+                const v2d lo = ld2(a.lb + 2 * j), hi = ld2(a.ub + 2 * j);
+                const double p0 = ((xn.x == lo.x && gt.x > 0.0) || (xn.x == hi.x && gt.x < 0.0)) ? 0.0 : gt.x;
+                const double p1 = ((xn.y == lo.y && gt.y > 0.0) || (xn.y == hi.y && gt.y < 0.0)) ? 0.0 : gt.y;
+                pgn = fmax(pgn, fmax(fabs(p0), fabs(p1)));
+            }
         }
         st2(a.x + 2 * j, xn);
         if (xtr) {
@@ -307,6 +343,13 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_accept_kernel(const QnVecArgs 
         a.part[2 * QN_VEC_MAXG + blockIdx.x] = acc[0];
         a.part[3 * QN_VEC_MAXG + blockIdx.x] = acc[1];
     }
+    if (!second) return;
+    pgn = vec_block_max(pgn, lds);
+    ctl_block_sum<1>(yy, lds);
+    if (threadIdx.x == 0) {
+        a.part[4 * QN_VEC_MAXG + blockIdx.x] = pgn;
+        a.part[5 * QN_VEC_MAXG + blockIdx.x] = yy[0];
+    }
 }
 
 __global__ __launch_bounds__(QN_VEC_TPB) void vec_post_kernel(const QnVecArgs a) {
@@ -315,14 +358,22 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_post_kernel(const QnVecArgs a)
     if (c->phase != QN_VP_ACCEPT) return;
     const double sy = vec_sum_parts(a.part, 2, a.G, lds);
     const double ss = vec_sum_parts(a.part, 3, a.G, lds);
+    const bool second = vec_newton(c->method) && c->gt_valid;
+    double pgn = 0.0, yy = 0.0;
+    if (second) {
+        pgn = vec_max_parts(a.part, 4, a.G, lds);
+        yy = vec_sum_parts(a.part, 5, a.G, lds);
+    }
     if (threadIdx.x != 0) return;
-    if (c->method == QN_SPG) { // spg.rs:135-143
+    if (c->method == QN_PROJECTED_NEWTON) { c->s_norm = sqrt(ss); c->y_norm = sqrt(yy); c->has_sy = 1; } // projected_newton.rs:132-135
+    if (vec_spectral(c->method)) { // spg.rs:135-143, spn.rs:140-147
         if (sy <= 0.0) c->lambda = c->lambda_max;
         else c->lambda = fmax(fmin(ss / sy, c->lambda_max), c->lambda_min);
     }
     if (a.trace && (int64_t)c->n_iter < c->trace_cap) {
         QnTraceRec r;
-        r.f = c->tr_f; r.gnorm = c->tr_gnorm; r.t = c->t; r.s_norm = c->method == QN_SPG ? sqrt(ss) : 0.0; r.y_norm = 0.0;
+        r.f = c->tr_f; r.gnorm = c->tr_gnorm; r.t = c->t; r.s_norm = (vec_spectral(c->method) || c->method == QN_PROJECTED_NEWTON) ? sqrt(ss) : 0.0;
+        r.y_norm = c->method == QN_PROJECTED_NEWTON ? sqrt(yy) : 0.0;
         r.n_evals = c->tr_n_evals; r.ls_iters = c->tr_ls_iters; r.ls_cases = 0; r.updated = 0;
         a.trace[c->n_iter] = r;
     }
@@ -332,4 +383,47 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_post_kernel(const QnVecArgs a)
     c->k++; c->n_iter++; // ls_solver.rs:104
     if (c->k >= c->max_iter) { c->status = QN_MAX_ITER_REACHED; c->phase = QN_VP_DONE; return; } // :78, :110
     c->phase = (c->have_eval && c->memoize) ? QN_VP_DIR : QN_VP_EVAL_X;
+    // The second-order variants on a memoised oracle: (f, g) at x_next are the accepted evaluation, so the next loop top (its oracle call is
+    // the memo's) is decided HERE, from the accept kernel's projected-gradient norm.  The host's one peek per batch then knows whether a
+    // factorisation is wanted at all: a converged or capped run enqueues none.
+    if (second && c->phase == QN_VP_DIR) {
+        c->n_calls++;
+        if (vec_loop_top(c, pgn)) return;
+        c->phase = QN_VP_NSOLVE;
+    }
+}
+
+// ---- n <= QN_SMALL_N: z = H^-1 g as nalgebra's `cholesky().unwrap().solve(g)` computes it, operation for operation, one thread ----
+// Cholesky::new (column by column: col_j -= L[j][k] col_k as an axpy of two roundings, sqrt of the diagonal, the column divided by it), then
+// solve_lower_triangular (column-oriented: b[i] /= L[i][i]; b[i+1..] -= b[i] L[i+1..][i]) and ad_solve_lower_triangular (row-oriented:
+// b[i] = (b[i] - L[i+1..][i] . b[i+1..]) / L[i][i]).  Only the lower triangle of H is read.  z is zero-padded to n_pad.
+__global__ void pn_small_kernel(const double* __restrict__ Hrow, size_t ld, int n, int n_pad, const double* __restrict__ g, double* __restrict__ z,
+                                int* __restrict__ fail) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    double a[QN_SMALL_N * QN_SMALL_N], b[QN_SMALL_N]; // column-major
+    for (int j = 0; j < n; ++j)
+        for (int i = j; i < n; ++i) a[i + j * n] = Hrow[(size_t)i * ld + j];
+    for (int j = 0; j < n; ++j) {
+        for (int k = 0; k < j; ++k) {
+            const double factor = -a[j + k * n];
+            for (int i = j; i < n; ++i) { const double pr = factor * a[i + k * n]; a[i + j * n] = pr + a[i + j * n]; }
+        }
+        const double diag = a[j + j * n];
+        if (!(diag > 0.0)) { *fail = 1; return; } // (zero, negative or NaN: Cholesky::new returns None and the reference's unwrap panics)
+        const double denom = sqrt(diag);
+        a[j + j * n] = denom;
+        for (int i = j + 1; i < n; ++i) a[i + j * n] = a[i + j * n] / denom;
+    }
+    for (int i = 0; i < n; ++i) b[i] = g[i];
+    for (int i = 0; i < n; ++i) {
+        const double coeff = b[i] / a[i + i * n];
+        b[i] = coeff;
+        for (int r = i + 1; r < n; ++r) { const double pr = -coeff * a[r + i * n]; b[r] = pr + b[r]; }
+    }
+    for (int i = n - 1; i >= 0; --i) {
+        double dot = 0.0;
+        for (int r = i + 1; r < n; ++r) { const double pr = a[r + i * n] * b[r]; dot = dot + pr; }
+        b[i] = (b[i] - dot) / a[i + i * n];
+    }
+    for (int i = 0; i < n_pad; ++i) z[i] = i < n ? b[i] : 0.0;
 }

@@ -60,6 +60,7 @@ OPTIONS = {
     "eval_zigzag": 20,
     "touch_h_rows": 21,
     "touch_q_rows": 22,
+    "pnewton_reuse_factor": 23,
 }
 OPT_GENERIC_KERNELS = 1
 OPT_DEFERRED_UPDATE_STEP = 2
@@ -83,6 +84,7 @@ OPT_BTB_PROJECT_IN_EVAL = 19
 OPT_EVAL_ZIGZAG = 20
 OPT_TOUCH_H_ROWS = 21
 OPT_TOUCH_Q_ROWS = 22
+OPT_PNEWTON_REUSE_FACTOR = 23
 
 
 class SolverError(Exception):
@@ -597,7 +599,8 @@ class _SolverBase:
                     res = oracle(x)
                     hm = res.hessian() if isinstance(res, FuncEvalMultivariate) else (res[2] if len(res) > 2 else None)
                     if hm is None:
-                        raise RuntimeError("Hessian not available in the oracle")
+                        # projected_newton.rs:73, spn.rs:85 .expect(...): the library's own answer for an oracle without a Hessian
+                        raise (RuntimeError if self.METHOD == A.NEWTON else ErrorInputParams)("Hessian not available in the oracle")
                     np.ctypeslib.as_array(hp, shape=(nn * nn,))[:] = np.asfortranarray(hm, dtype=np.float64).ravel(order="F")
                     return 0
                 except Exception as e:  # noqa: BLE001
@@ -607,7 +610,7 @@ class _SolverBase:
             keep.append(cfn)
             o.kind = A.ORACLE_HOST
             o.host_fn = C.cast(cfn, C.c_void_p)
-            if self.METHOD == A.NEWTON:
+            if self.METHOD in (A.NEWTON, A.PROJECTED_NEWTON, A.SPECTRAL_PROJECTED_NEWTON):
                 hfn = A.HOST_HESSIAN_FN(htramp)
                 keep.append(hfn)
                 o.host_hessian_fn = C.cast(hfn, C.c_void_p)
@@ -854,6 +857,31 @@ class SpectralProjectedGradient(_ProjectedBase):
 
     def lambda_max(self):
         return getattr(self, "_lmax", 1e3)
+
+
+class ProjectedNewton(_ProjectedBase):
+    """newton/projected_newton.rs: `new(grad_tol, x0, lower_bound, upper_bound)`; d = P(x - H^-1 g) - x with H^-1 g from one Cholesky
+    factorisation (the lower triangle of the Hessian) and one solve on the GPU.  The oracle is a `Quadratic` (its matrix is the Hessian) or
+    a closure returning `FuncEvalMultivariate(f, g).with_hessian(h)`; anything else has no Hessian here: ErrorInputParams."""
+    METHOD = A.PROJECTED_NEWTON
+
+    def has_converged(self, eval_x_k):  # projected_newton.rs:95-110: s_norm, then y_norm, then the projected gradient
+        if self.next_iterate_too_close() or self.gradient_next_iterate_too_close():
+            return True
+        return float(np.max(np.abs(self.projected_gradient(eval_x_k)))) < self.tol()
+
+    def newton_factorisations(self):
+        v = C.c_size_t()
+        _check(A.lib().qn_solver_newton_factorisations(self.h, C.byref(v)))
+        return v.value
+
+
+class SpectralProjectedNewton(SpectralProjectedGradient):
+    """newton/spn.rs: `new(grad_tol, x0, oracle, lower_bound, upper_bound)`; d = P(x - lambda H^-1 g) - x, lambda built and updated exactly as
+    in SpectralProjectedGradient (the constructor calls the oracle once, for lambda0: spn.rs:40-46; no Hessian is needed there)."""
+    METHOD = A.SPECTRAL_PROJECTED_NEWTON
+
+    newton_factorisations = ProjectedNewton.newton_factorisations
 
 
 class Newton(_SolverBase):

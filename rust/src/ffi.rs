@@ -30,6 +30,8 @@ pub const QN_NEWTON: c_int = 3;
 pub const QN_SR1: c_int = 4;
 pub const QN_SPG: c_int = 5;
 pub const QN_PROJECTED_GRADIENT: c_int = 6;
+pub const QN_PROJECTED_NEWTON: c_int = 7;
+pub const QN_SPECTRAL_PROJECTED_NEWTON: c_int = 8;
 
 // qn_option (ABI 5): what rounds 1-5 selected through negative codes of qn_solver_set_tiling; value != 0 on, 0 off
 pub const QN_OPT_GENERIC_KERNELS: c_int = 1;
@@ -54,6 +56,7 @@ pub const QN_OPT_BTB_PROJECT_IN_EVAL: c_int = 19;
 pub const QN_OPT_EVAL_ZIGZAG: c_int = 20;
 pub const QN_OPT_TOUCH_H_ROWS: c_int = 21;
 pub const QN_OPT_TOUCH_Q_ROWS: c_int = 22;
+pub const QN_OPT_PNEWTON_REUSE_FACTOR: c_int = 23;
 
 pub const QN_UNIQUE_ID_BYTES: usize = 128;
 pub const QN_TRACE_LS_MODIFIED: i32 = 1 << 30;
@@ -64,6 +67,7 @@ pub const QN_PATH_PIPELINED: u32 = 8;
 pub const QN_PATH_SYM2: u32 = 16;
 pub const QN_PATH_TILES1: u32 = 32;
 pub const QN_PATH_VECTOR: u32 = 64;
+pub const QN_PATH_PNEWTON: u32 = 128;
 
 #[repr(C)] pub struct qn_context { _p: [u8; 0] }
 #[repr(C)] pub struct qn_solver { _p: [u8; 0] }
@@ -214,6 +218,7 @@ extern "C" {
     pub fn qn_solver_set_bounds(s: *mut qn_solver, lower_bound_host: *const f64, upper_bound_host: *const f64) -> c_int;
     pub fn qn_solver_set_spg_lambdas(s: *mut qn_solver, lambda_min: f64, lambda_max: f64) -> c_int;
     pub fn qn_solver_spg_lambda(s: *mut qn_solver, out: *mut f64, is_some: *mut c_int) -> c_int;
+    pub fn qn_solver_newton_factorisations(s: *mut qn_solver, out: *mut usize) -> c_int;
     pub fn qn_solver_reset(s: *mut qn_solver, x0_host: *const f64) -> c_int;
     pub fn qn_minimize(s: *mut qn_solver, ls: *mut qn_linesearch, oracle: *const qn_oracle, max_iter_solver: usize, max_iter_line_search: usize, callback: qn_callback_fn, callback_user: *mut c_void) -> c_int;
     pub fn qn_compute_step_len(ctx: *mut qn_context, ls: *mut qn_linesearch, x_k_host: *const f64, f_k: f64, g_k_host: *const f64, direction_host: *const f64, n: usize, oracle: *const qn_oracle, max_iter: usize, step_out: *mut f64) -> c_int;

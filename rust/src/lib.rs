@@ -86,7 +86,25 @@ where
     0
 }
 
-fn host_oracle<F>(oracle: &mut F, memoize: bool) -> qn_oracle
+/// The Hessian part of the closure's `FuncEvalMultivariate` (func_eval.rs:8,27-33), column-major as `DMatrix` stores it: asked for by
+/// the projected Newton solvers only.  A closure without one ends the run ("Hessian not available in the oracle").
+unsafe extern "C" fn hessian_trampoline<F>(user: *mut c_void, x: *const f64, n: usize, h: *mut f64) -> c_int
+where
+    F: FnMut(&DVector<Floating>) -> FuncEvalMultivariate,
+{
+    let oracle = &mut *(user as *mut F);
+    let xv = DVector::from_column_slice(std::slice::from_raw_parts(x, n));
+    let eval = oracle(&xv);
+    match eval.hessian() {
+        Some(m) if m.nrows() == n && m.ncols() == n => {
+            std::ptr::copy_nonoverlapping(m.as_ptr(), h, n * n);
+            0
+        }
+        _ => 1,
+    }
+}
+
+fn host_oracle<F>(oracle: &mut F, memoize: bool, with_hessian: bool) -> qn_oracle
 where
     F: FnMut(&DVector<Floating>) -> FuncEvalMultivariate,
 {
@@ -98,7 +116,8 @@ where
         device_fn: None,
         device_user: std::ptr::null_mut(),
         objective: std::ptr::null_mut(),
-        host_hessian_fn: None,
+        // only the projected Newton solvers ask for the Hessian: every other solver passes the oracle it always passed
+        host_hessian_fn: if with_hessian { Some(hessian_trampoline::<F>) } else { None },
     }
 }
 
@@ -189,7 +208,7 @@ fn step_len_on_device<F>(
 where
     F: FnMut(&DVector<Floating>) -> FuncEvalMultivariate,
 {
-    let o = host_oracle(oracle, false);
+    let o = host_oracle(oracle, false, false);
     let mut t = 0.0;
     let code = unsafe {
         qn_compute_step_len(
@@ -473,7 +492,7 @@ macro_rules! gpu_solver {
                         f(&*env.me)
                     }
                 }
-                let o = host_oracle(&mut oracle, false);
+                let o = host_oracle(&mut oracle, false, $method == QN_PROJECTED_NEWTON || $method == QN_SPECTRAL_PROJECTED_NEWTON);
                 let has_callback = callback.is_some();
                 let mut env = CallbackEnv { me: self as *mut $name, f: &mut callback };
                 let core = &mut self.core as *mut Core; // (`env.me` aliases self for the duration of the call)
@@ -560,6 +579,10 @@ macro_rules! gpu_solver {
                 direction: &DVector<Floating>,
                 max_iter_line_search: usize,
             ) -> Result<(), SolverError> {
+                if $method == QN_PROJECTED_NEWTON || $method == QN_SPECTRAL_PROJECTED_NEWTON {
+                    // the direction needs the Cholesky solve and (spn.rs) the device-resident lambda: `minimize_on_device` / `minimize_objective`
+                    return Err(SolverError::ErrorInputParams);
+                }
                 if $method == QN_SPG {
                     // spg.rs:126-143 updates lambda here; it lives on the device and only qn_minimize updates it.  Refuse rather than run
                     // a fixed-lambda projected gradient under SPG's name: use `minimize_on_device` / `minimize_objective`.
@@ -610,6 +633,17 @@ gpu_solver!(
     GpuSpectralProjectedGradient, QN_SPG, false
 );
 
+gpu_solver!(
+    /// Drop-in for `ProjectedNewton` (newton/projected_newton.rs): `new(grad_tol, x0).with_bounds(lb, ub)`; d = P(x - H^-1 g) - x from one
+    /// Cholesky factorisation (the Hessian's lower triangle) and one solve on the GPU (QN_PATH_PNEWTON).  The closure's `FuncEvalMultivariate`
+    /// carries the Hessian (`with_hessian`), or the oracle is a device quadratic.  Drive it with `minimize_on_device` / `minimize_objective`.
+    GpuProjectedNewton, QN_PROJECTED_NEWTON, false
+);
+gpu_solver!(
+    /// Drop-in for `SpectralProjectedNewton` (newton/spn.rs): d = P(x - lambda H^-1 g) - x, lambda as in `GpuSpectralProjectedGradient`.
+    GpuSpectralProjectedNewton, QN_SPECTRAL_PROJECTED_NEWTON, false
+);
+
 macro_rules! bounded_first_order {
     ($name:ident) => {
         impl $name {
@@ -641,6 +675,49 @@ macro_rules! bounded_first_order {
 }
 bounded_first_order!(GpuProjectedGradientDescent);
 bounded_first_order!(GpuSpectralProjectedGradient);
+bounded_first_order!(GpuProjectedNewton);
+bounded_first_order!(GpuSpectralProjectedNewton);
+
+macro_rules! newton_factorisations {
+    ($name:ident) => {
+        impl $name {
+            /// Cholesky factorisations enqueued by the last minimize call (a device quadratic's factor is kept: QN_OPT_PNEWTON_REUSE_FACTOR)
+            pub fn newton_factorisations(&self) -> usize {
+                let mut v = 0usize;
+                unsafe { qn_solver_newton_factorisations(self.core.h, &mut v) };
+                v
+            }
+        }
+    };
+}
+newton_factorisations!(GpuProjectedNewton);
+newton_factorisations!(GpuSpectralProjectedNewton);
+
+impl GpuProjectedNewton {
+    pub fn s_norm(&self) -> Option<Floating> {
+        self.core.option(qn_solver_s_norm)
+    }
+    pub fn y_norm(&self) -> Option<Floating> {
+        self.core.option(qn_solver_y_norm)
+    }
+    pub fn next_iterate_too_close(&self) -> bool {
+        self.core.flag(qn_solver_next_iterate_too_close) // projected_newton.rs:15-20
+    }
+    pub fn gradient_next_iterate_too_close(&self) -> bool {
+        self.core.flag(qn_solver_gradient_next_iterate_too_close) // projected_newton.rs:21-26
+    }
+}
+
+impl GpuSpectralProjectedNewton {
+    /// spn.rs:23-27
+    pub fn with_lambdas(self, lambda_min: Floating, lambda_max: Floating) -> Self {
+        assert_eq!(unsafe { qn_solver_set_spg_lambdas(self.core.h, lambda_min, lambda_max) }, QN_OK, "{}", last_error());
+        self
+    }
+    pub fn lambda(&self) -> Option<Floating> {
+        self.core.option(qn_solver_spg_lambda)
+    }
+}
 
 impl GpuSpectralProjectedGradient {
     /// spg.rs:23-27
