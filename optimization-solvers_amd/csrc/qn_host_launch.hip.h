@@ -1,8 +1,29 @@
-// qn_host_launch.hip.h -- host side, part 5 of 7: one qn_minimize call's `Run`, the launches of every path (second-generation machine, generic
-// objectives on it, fused rows, generic control step), the placement probe of H.
+// qn_host_launch.hip.h -- host side, part 5 of 7: one qn_minimize call's `Run` (the plan that qn_host_minimize.hip.h fills and pumps), what
+// minimize_impl and vec_minimize share (check_oracle, stats_add_totals), the launches of every path (second-generation machine, generic objectives
+// on it, fused rows, generic control step), the placement probe of H.
 #pragma once
 struct Run;
 static int enqueue_newton(qn_solver* s, const qn_oracle* o, qn_objective* obj);
+
+// the oracle of a minimize call, validated; *obj: its device objective, if it is one (whether the solver family runs that objective is the caller's test)
+static int check_oracle(qn_context* c, size_t n, const qn_oracle* o, qn_objective** obj) {
+    *obj = nullptr;
+    if (o->kind == QN_ORACLE_HOST) return o->host_fn ? QN_OK : fail(QN_ERROR_INPUT_PARAMS, "host oracle is null");
+    if (o->kind == QN_ORACLE_DEVICE_FN) return o->device_fn ? QN_OK : fail(QN_ERROR_INPUT_PARAMS, "device oracle is null");
+    if (o->kind != QN_ORACLE_OBJECTIVE) return fail(QN_ERROR_INPUT_PARAMS, "unknown oracle kind");
+    if (!o->objective) return fail(QN_ERROR_INPUT_PARAMS, "objective is null");
+    if (o->objective->ctx != c || o->objective->n != n) return fail(QN_ERROR_INPUT_PARAMS, "objective does not match the solver");
+    *obj = o->objective;
+    return QN_OK;
+}
+// qn_stats: the call just accounted joins the solver's running totals
+static void stats_add_totals(qn_solver* s) {
+    s->stats.total_minimize_calls++;
+    s->stats.total_iterations += s->stats.iterations; s->stats.total_oracle_calls += s->stats.oracle_calls; s->stats.total_oracle_evals += s->stats.oracle_evals;
+    s->stats.total_h_passes += s->stats.h_passes; s->stats.total_h_bytes += s->stats.h_bytes; s->stats.total_obj_bytes += s->stats.obj_bytes;
+}
+// the ranks' partial sums of one buffer: added in place (all-reduce) or gathered, for the kernel behind to add them in rank order
+static int xchg_sum_or_gather(qn_context* c, double* buf, size_t cnt) { return c->use_allreduce ? exchange_sum(c, buf, cnt) : exchange(c, buf, cnt); }
 
 // ---- the pump ----
 struct Run {
@@ -20,10 +41,18 @@ struct Run {
     bool btb = false;         // ... BackTrackingB on this path at all (proj: with the projection as a launch of its own; QnS2Args.projfold: inside the evaluation kernel)
     bool bnd = false;         // ... a bounded run on it (BFGSB / DFPB, MoreThuenteB): one more launch per iteration, s2_dir_kernel (qn_sym2.hip.h)
     bool tiles1 = false;      // the update pass's tiles through the first-generation tile kernel (one workgroup per tile, two per CU) behind a
-                              // one-workgroup launch that runs the machine: H's share past the Infinity Cache (see minimize_impl)
+                              // one-workgroup launch that runs the machine: H's share past the Infinity Cache (see plan_run)
     QnS2Args s2{};
     uint64_t s2_launches = 0; // parity of the control-block double buffer = launches so far & 1
     unsigned long long report_seq = 0; // != 0: the next launch reports its control block to the host (s2_wait_report)
+    // the rest of the plan (plan_run): what the pumps and finish_stats are told
+    qn_linesearch* ls = nullptr;
+    qn_callback_fn callback = nullptr; void* callback_user = nullptr;
+    int ls_only = 0;
+    bool ls_bounded = false;          // the line search brings a box of its own (MoreThuenteB, BackTrackingB)
+    bool sync = false;                // the synchronous pump: one request at a time, the host reads the control block in between
+    int status = QN_ABNORMAL_TERMINATION; // the machine's final status, left by the pump
+    uint64_t xv0 = 0, xs0 = 0;        // the context's collectives before this call (qn_stats counts the call's own)
 };
 
 // ---- generic objectives on the second-generation structure (qn_sym2g.hip.h) ----
@@ -102,6 +131,14 @@ static int s2g_enqueue_tiles(Run& r) {
     return QN_OK;
 }
 
+// the evaluation tiles of an unbounded run on one rank: mover + multiplier waves, the pair instance, the general body with Q streamed or kept
+static void s2_launch_eval_plain(hipStream_t st, const QnS2Args& a) {
+    if (a.pair && a.ring) hipLaunchKernelGGL(s2_evalr_kernel<false>, dim3(a.G), dim3(QN_S2R_TPB), 0, st, a);
+    else if (a.pair) hipLaunchKernelGGL(s2_eval_kernel<true>, dim3(a.G), dim3(QN_S2_TPB), 0, st, a);
+    else if (a.ntq) hipLaunchKernelGGL((s2_eval_kernel<false, false, true>), dim3(a.G), dim3(QN_S2_TPB), 0, st, a);
+    else hipLaunchKernelGGL(s2_eval_kernel<false>, dim3(a.G), dim3(QN_S2_TPB), 0, st, a);
+}
+
 static int s2_launch(Run& r, int kind) {
     qn_solver* s = r.s;
     hipStream_t st = s->ctx->stream;
@@ -129,10 +166,7 @@ static int s2_launch(Run& r, int kind) {
             else if (a.pair) hipLaunchKernelGGL((s2_eval_kernel<true, false, false, true>), dim3(a.G), dim3(QN_S2_TPB), 0, st, a);
             else if (a.ntq) hipLaunchKernelGGL((s2_eval_kernel<false, false, true, true>), dim3(a.G), dim3(QN_S2_TPB), 0, st, a);
             else hipLaunchKernelGGL((s2_eval_kernel<false, false, false, true>), dim3(a.G), dim3(QN_S2_TPB), 0, st, a);
-        } else if (a.pair && a.ring) hipLaunchKernelGGL(s2_evalr_kernel<false>, dim3(a.G), dim3(QN_S2R_TPB), 0, st, a);
-        else if (a.pair) hipLaunchKernelGGL(s2_eval_kernel<true>, dim3(a.G), dim3(QN_S2_TPB), 0, st, a);
-        else if (a.ntq) hipLaunchKernelGGL((s2_eval_kernel<false, false, true>), dim3(a.G), dim3(QN_S2_TPB), 0, st, a);
-        else hipLaunchKernelGGL(s2_eval_kernel<false>, dim3(a.G), dim3(QN_S2_TPB), 0, st, a);
+        } else s2_launch_eval_plain(st, a);
         break;
     case QN_S2_DIR: hipLaunchKernelGGL(s2_dir_kernel, dim3(a.nb), dim3(QN_TB), 0, st, a); break;
     case QN_S2_PROJ: hipLaunchKernelGGL(s2_proj_kernel, dim3(a.nb), dim3(QN_TB), 0, st, a); break;
@@ -149,7 +183,7 @@ static int s2_launch(Run& r, int kind) {
         break;
     case QN_S2_VECD: hipLaunchKernelGGL((s2_vec_kernel<true, true>), dim3(a.nb), dim3(QN_S2_TPB), 0, st, a); break; // (row-sharded, trial-vector exchange)
     case QN_S2_HTILE:
-        if (s->method == QN_SR1) { // (one rank, no fold, no tail reduce: minimize_impl)
+        if (s->method == QN_SR1) { // (one rank, no fold, no tail reduce: plan_s2_args)
             if (a.nt) hipLaunchKernelGGL((s2_hpass_kernel<true, false, false, false, false, true>), dim3(a.G), dim3(QN_S2_TPB), 0, st, a);
             else hipLaunchKernelGGL((s2_hpass_kernel<false, false, false, false, false, true>), dim3(a.G), dim3(QN_S2_TPB), 0, st, a);
         } else if (sh) {
@@ -269,8 +303,7 @@ static int s2_do_eval(Run& r, unsigned long long report_seq = 0) {
         }
         ProfScope ps(s, KC_COMM);
         c->n_xchg_scalar++;
-        if (c->use_allreduce) QNCHK(exchange_sum(c, half, cnt));
-        else QNCHK(exchange(c, half, cnt));
+        QNCHK(xchg_sum_or_gather(c, half, cnt));
     }
     return QN_OK;
 }
@@ -285,8 +318,7 @@ static int s2_do_vec(Run& r) {
             ProfScope ps(s, KC_COMM);
             c->n_xchg_vector++;
             if (r.gobj) QNCHK(exchange(c, r.obj->lgall, (size_t)s->T.n_pad)); // the ranks' G_r of the accepted point (weighed and added in rank order by s2g_vec_kernel)
-            else if (c->use_allreduce) QNCHK(exchange_sum(c, s->symsh_xg, (size_t)s->T.n_pad));
-            else QNCHK(exchange(c, s->symsh_xg, (size_t)s->T.n_pad));
+            else QNCHK(xchg_sum_or_gather(c, s->symsh_xg, (size_t)s->T.n_pad));
         }
         return s2_launch(r, QN_S2_VEC);
     }
@@ -311,8 +343,7 @@ static int s2_do_hpass(Run& r, bool tiles) {
         QNCHK(s2_launch(r, QN_S2_HSUM));
         ProfScope ps(s, KC_COMM);
         c->n_xchg_vector++;
-        if (c->use_allreduce) QNCHK(exchange_sum(c, s->symsh_xg, 2 * (size_t)s->T.n_pad));
-        else QNCHK(exchange(c, s->symsh_xg, 2 * (size_t)s->T.n_pad));
+        QNCHK(xchg_sum_or_gather(c, s->symsh_xg, 2 * (size_t)s->T.n_pad));
     }
     return s2_launch(r, QN_S2_HREDUCE);
 }
@@ -385,12 +416,7 @@ static int place_h(Run& r) {
             if (pe) {
                 QnS2Args ae = a;
                 ae.ctl_first = pe;
-                for (int e = 0; e < 2; ++e) {
-                    if (ae.pair && ae.ring) hipLaunchKernelGGL(s2_evalr_kernel<false>, dim3(ae.G), dim3(QN_S2R_TPB), 0, st, ae);
-                    else if (ae.pair) hipLaunchKernelGGL(s2_eval_kernel<true>, dim3(ae.G), dim3(QN_S2_TPB), 0, st, ae);
-                    else if (ae.ntq) hipLaunchKernelGGL((s2_eval_kernel<false, false, true>), dim3(ae.G), dim3(QN_S2_TPB), 0, st, ae);
-                    else hipLaunchKernelGGL(s2_eval_kernel<false>, dim3(ae.G), dim3(QN_S2_TPB), 0, st, ae);
-                }
+                for (int e = 0; e < 2; ++e) s2_launch_eval_plain(st, ae);
             }
             HIPCHK(hipEventRecord(e0, st));
             if (s->method == QN_BFGS) hipLaunchKernelGGL((s2_hpass_kernel<false, true, false>), dim3(a.G), dim3(QN_S2_TPB), 0, st, a);
@@ -498,8 +524,7 @@ static int enqueue_eval_fused(Run& r, int after_h) {
             {
                 ProfScope ps(s, KC_COMM);
                 c->n_xchg_vector++;
-                if (c->use_allreduce) QNCHK(exchange_sum(c, s->symsh_xg, (size_t)s->T.n_pad));
-                else QNCHK(exchange(c, s->symsh_xg, (size_t)s->T.n_pad));
+                QNCHK(xchg_sum_or_gather(c, s->symsh_xg, (size_t)s->T.n_pad));
             }
             {
                 ProfScope ps(s, KC_EREDUCE);
@@ -536,53 +561,44 @@ static int enqueue_eval_fused(Run& r, int after_h) {
     return QN_OK;
 }
 
+// The first-generation symmetric update pass (qn_sym.hip.h), for the fused path and for the generic path's H pass alone: `y` comes with what
+// differs between the two (F, or the generic path's vectors).  One rank: the tiles, their reduce.  Row-sharded: the circulant half of this rank's
+// block-rows, its partial sums, the exchange of [u, v], the epilogue -- the totals -- on every rank.
+static int enqueue_sym1_hpass(qn_solver* s, QnSymHPassArgs& y, bool generic) {
+    qn_context* c = s->ctx;
+    const bool sh = c->world > 1;
+    y.H = s->H; y.T = s->T; y.T.cs = 1; y.ctl = s->ctl; y.expect_phase = QN_PH_REQ_HPASS; y.nb = s->sym_nb; y.part = s->sym_part;
+    y.nt = s->T.n_pad >= 8192; // past the Infinity Cache (same-box A/B: +7 % at n = 32768, +3 % at 8192, -1 % at 4096)
+    s->h_lower_stale = true;
+    if (sh) y.sh = sym_shard(s);
+    const int grid = sh ? qn_symsh_ntiles(y.nb, y.sh.nbl, y.sh.ioff) : y.nb * (y.nb + 1) / 2;
+    { ProfScope ps(s, KC_HPASS); hipLaunchKernelGGL(sym_hpass_tile_kernel, dim3(grid), dim3(QN_SYM_TPB), 0, c->stream, y); }
+    if (!sh) {
+        ProfScope ps(s, KC_HREDUCE);
+        hipLaunchKernelGGL(sym_hpass_reduce_kernel, dim3(y.nb), dim3(256), 0, c->stream, y);
+    } else {
+        { ProfScope ps(s, KC_HREDUCE); hipLaunchKernelGGL(symsh_hpass_sum_kernel, dim3(y.nb), dim3(256), 0, c->stream, y); }
+        HIPCHK(hipGetLastError());
+        { ProfScope ps(s, KC_COMM); c->n_xchg_vector++; QNCHK(xchg_sum_or_gather(c, s->symsh_xg, 2 * (size_t)s->T.n_pad)); }
+        ProfScope ps(s, KC_HREDUCE);
+        if (generic) hipLaunchKernelGGL(symsh_hpass_epi_generic_kernel, dim3(y.nb), dim3(256), 0, c->stream, y);
+        else hipLaunchKernelGGL(symsh_hpass_epi_kernel, dim3(y.nb), dim3(256), 0, c->stream, y);
+    }
+    s->stats.launches += sh ? 3 : 2;
+    HIPCHK(hipGetLastError());
+    return QN_OK;
+}
+
 static int enqueue_hpass_fused(Run& r) {
     qn_solver* s = r.s;
     qn_context* c = s->ctx;
-    QnHPassFusedArgs a{};
-    a.H = s->H; a.T = s->T; a.T.cs = 1; a.F = s->V.F; a.ctl = s->ctl; a.expect_phase = QN_PH_REQ_HPASS;
     if (r.sym) {
         QnSymHPassArgs y{};
-        y.H = s->H; y.T = a.T; y.F = a.F; y.ctl = s->ctl; y.expect_phase = QN_PH_REQ_HPASS; y.nb = s->sym_nb; y.part = s->sym_part;
-        y.nt = s->T.n_pad >= 8192; // past the Infinity Cache (same-box A/B: +7 % at n = 32768, +3 % at 8192, -1 % at 4096)
-        s->h_lower_stale = true;
-        if (c->world > 1) {
-            y.sh = sym_shard(s);
-            {
-                ProfScope ps(s, KC_HPASS);
-                hipLaunchKernelGGL(sym_hpass_tile_kernel, dim3(qn_symsh_ntiles(y.nb, y.sh.nbl, y.sh.ioff)), dim3(QN_SYM_TPB), 0, c->stream, y);
-            }
-            {
-                ProfScope ps(s, KC_HREDUCE);
-                hipLaunchKernelGGL(symsh_hpass_sum_kernel, dim3(y.nb), dim3(256), 0, c->stream, y);
-            }
-            HIPCHK(hipGetLastError());
-            {
-                ProfScope ps(s, KC_COMM);
-                c->n_xchg_vector++;
-                if (c->use_allreduce) QNCHK(exchange_sum(c, s->symsh_xg, 2 * (size_t)s->T.n_pad));
-                else QNCHK(exchange(c, s->symsh_xg, 2 * (size_t)s->T.n_pad));
-            }
-            {
-                ProfScope ps(s, KC_HREDUCE);
-                hipLaunchKernelGGL(symsh_hpass_epi_kernel, dim3(y.nb), dim3(256), 0, c->stream, y);
-            }
-            s->stats.launches += 3;
-            HIPCHK(hipGetLastError());
-            return QN_OK;
-        }
-        {
-            ProfScope ps(s, KC_HPASS);
-            hipLaunchKernelGGL(sym_hpass_tile_kernel, dim3(y.nb * (y.nb + 1) / 2), dim3(QN_SYM_TPB), 0, c->stream, y);
-        }
-        {
-            ProfScope ps(s, KC_HREDUCE);
-            hipLaunchKernelGGL(sym_hpass_reduce_kernel, dim3(y.nb), dim3(256), 0, c->stream, y);
-        }
-        s->stats.launches += 2;
-        HIPCHK(hipGetLastError());
-        return QN_OK;
+        y.F = s->V.F;
+        return enqueue_sym1_hpass(s, y, false);
     }
+    QnHPassFusedArgs a{};
+    a.H = s->H; a.T = s->T; a.T.cs = 1; a.F = s->V.F; a.ctl = s->ctl; a.expect_phase = QN_PH_REQ_HPASS;
     {
         ProfScope ps(s, KC_HPASS);
         QN_DISPATCH_RU(launch_hpass_fused, s->R, s->U, c->stream, a);
@@ -651,46 +667,8 @@ static int enqueue_hpass_req(Run& r) {
     if (r.fused) return enqueue_hpass_fused(r);
     if (r.sym_generic) {
         QnSymHPassArgs y{};
-        y.H = s->H; y.T = s->T; y.T.cs = 1; y.ctl = s->ctl; y.expect_phase = QN_PH_REQ_HPASS; y.nb = s->sym_nb; y.part = s->sym_part;
         y.generic = 1; y.gsp = s->V.sp; y.gup = s->V.up; y.gvy = s->V.y; y.gvg = s->V.g; y.ghp = s->V.hp;
-        y.nt = s->T.n_pad >= 8192; // past the Infinity Cache (same-box A/B: +7 % at n = 32768, +3 % at 8192, -1 % at 4096)
-        s->h_lower_stale = true;
-        if (c->world > 1) { // row-sharded: the circulant half of this rank's block-rows; partial sums gathered, totals on every rank
-            y.sh = sym_shard(s);
-            {
-                ProfScope ps(s, KC_HPASS);
-                hipLaunchKernelGGL(sym_hpass_tile_kernel, dim3(qn_symsh_ntiles(y.nb, y.sh.nbl, y.sh.ioff)), dim3(QN_SYM_TPB), 0, c->stream, y);
-            }
-            {
-                ProfScope ps(s, KC_HREDUCE);
-                hipLaunchKernelGGL(symsh_hpass_sum_kernel, dim3(y.nb), dim3(256), 0, c->stream, y);
-            }
-            HIPCHK(hipGetLastError());
-            {
-                ProfScope ps(s, KC_COMM);
-                c->n_xchg_vector++;
-                if (c->use_allreduce) QNCHK(exchange_sum(c, s->symsh_xg, 2 * (size_t)s->T.n_pad));
-                else QNCHK(exchange(c, s->symsh_xg, 2 * (size_t)s->T.n_pad));
-            }
-            {
-                ProfScope ps(s, KC_HREDUCE);
-                hipLaunchKernelGGL(symsh_hpass_epi_generic_kernel, dim3(y.nb), dim3(256), 0, c->stream, y);
-            }
-            s->stats.launches += 3;
-            HIPCHK(hipGetLastError());
-            return QN_OK;
-        }
-        {
-            ProfScope ps(s, KC_HPASS);
-            hipLaunchKernelGGL(sym_hpass_tile_kernel, dim3(y.nb * (y.nb + 1) / 2), dim3(QN_SYM_TPB), 0, c->stream, y);
-        }
-        {
-            ProfScope ps(s, KC_HREDUCE);
-            hipLaunchKernelGGL(sym_hpass_reduce_kernel, dim3(y.nb), dim3(256), 0, c->stream, y);
-        }
-        s->stats.launches += 2;
-        HIPCHK(hipGetLastError());
-        return QN_OK;
+        return enqueue_sym1_hpass(s, y, true);
     }
     QnHPassArgs a = hpass_args(s, QN_PH_REQ_HPASS);
     {

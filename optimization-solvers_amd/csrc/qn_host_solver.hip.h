@@ -48,7 +48,7 @@ struct qn_solver {
     double* s2_wgV = nullptr;  // generic objectives: the second table of per-workgroup sums (QnS2Args.wgV)
     hipGraphExec_t s2_graph_exec = nullptr; // measurement (QN_S2_GRAPH): two periods of the pipelined pattern as one graph, and what it was captured for
     QnS2Args s2_graph_args{}; int s2_graph_slots = 0, s2_graph_bnd = 0; uint64_t s2_graph_len = 0, s2_graph_stat = 0;
-    int last_ls_kind = -1; std::vector<double> last_ls_box; bool ls_box_changed = false; // the line search (kind, box) of the last qn_minimize call: see minimize_impl
+    int last_ls_kind = -1; std::vector<double> last_ls_box; bool ls_box_changed = false; // the line search (kind, box) of the last qn_minimize call: see plan_run
     double mtb_cand_keep = INFINITY; // bounded second-generation runs: the step to the box of the direction a warm call continues with
     bool no_s2bnd = false;     // tests: bounded runs keep the generic path (QN_OPT_BOUNDED_SECOND_GENERATION 0)
     bool h_sliver_whole = false; // the diagonal tiles that sliver rows read are complete (both triangles): kept so by sliver-mode update passes

@@ -195,16 +195,8 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     if (c->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient / projected Newton run on one rank");
     const bool pn = pn_method(s->method);
     VecRun r{s, o, nullptr, {}};
-    if (o->kind == QN_ORACLE_OBJECTIVE) {
-        if (!o->objective) return fail(QN_ERROR_INPUT_PARAMS, "objective is null");
-        if (o->objective->ctx != c || o->objective->n != s->n) return fail(QN_ERROR_INPUT_PARAMS, "objective does not match the solver");
-        r.obj = o->objective;
-        if (r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_LOGSUMEXP) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
-    } else if (o->kind == QN_ORACLE_HOST) {
-        if (!o->host_fn) return fail(QN_ERROR_INPUT_PARAMS, "host oracle is null");
-    } else if (o->kind == QN_ORACLE_DEVICE_FN) {
-        if (!o->device_fn) return fail(QN_ERROR_INPUT_PARAMS, "device oracle is null");
-    } else return fail(QN_ERROR_INPUT_PARAMS, "unknown oracle kind");
+    QNCHK(check_oracle(c, s->n, o, &r.obj));
+    if (r.obj && r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_LOGSUMEXP) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
     if (ls->kind == QN_LS_MORETHUENTE || ls->kind == QN_LS_MORETHUENTE_B)
         return fail(QN_ERROR_INPUT_PARAMS, "More-Thuente with SPG / projected gradient is out of scope: use GLLQuadratic, BackTracking or BackTrackingB");
     if (ls->kind != QN_LS_GLL_QUADRATIC && ls->kind != QN_LS_BACKTRACKING && ls->kind != QN_LS_BACKTRACKING_B)
@@ -268,11 +260,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         s->stats.h_passes = 0; s->stats.h_bytes = 0; s->stats.matrix_bytes_per_pass = 0;
         s->stats.obj_bytes = 0;
         if (r.obj && r.obj->kind == OBJ_QUADRATIC) s->stats.obj_bytes = h->n_evals * (uint64_t)r.obj->T.rpr * (uint64_t)r.obj->T.n_pad * 8ull;
-        s->stats.total_minimize_calls++;
-        s->stats.total_iterations += s->stats.iterations;
-        s->stats.total_oracle_calls += s->stats.oracle_calls;
-        s->stats.total_oracle_evals += s->stats.oracle_evals;
-        s->stats.total_obj_bytes += s->stats.obj_bytes;
+        stats_add_totals(s); // (no update passes, one rank: total_h_* and total_xchg_* stay)
         s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u);
         if (s->method == QN_PROJECTED_NEWTON) { // s_norm() / y_norm() (projected_newton.rs:10-11) through the getters every solver answers
             s->hctl->has_s_norm = h->has_sy; s->hctl->has_y_norm = h->has_sy; s->hctl->s_norm = h->s_norm; s->hctl->y_norm = h->y_norm;
