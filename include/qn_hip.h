@@ -184,7 +184,7 @@ int qn_objective_eval(qn_objective* obj, const double* x_host, double* f, double
 int qn_objective_get_rows(qn_objective* obj, size_t row0, size_t nrows, double* out_host);
 
 /* ---------------------------------------------------------------------------------------------
- * Solvers: BFGS (bfgs.rs:4-127), DFP (dfp.rs), GradientDescent (gradient_descent.rs:7-82), Newton (newton/mod.rs).
+ * Solvers: BFGS (bfgs.rs:4-127), DFP (dfp.rs), Broyden (broyden.rs), GradientDescent (gradient_descent.rs:7-82), Newton (newton/mod.rs).
  * ------------------------------------------------------------------------------------------- */
 enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton/mod.rs:8-69, SURVEY.md 8(f) row f2 */,
        QN_SR1 = 4 /* sr1_b.rs (row f4; SR1B once qn_solver_set_bounds is called) */,
@@ -210,13 +210,20 @@ enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton
         * top in the reference's order: s_norm, y_norm, then the projected gradient (projected_newton.rs:95-110); trace: s_norm, y_norm.
         * One n x n work matrix, allocated by the first qn_minimize that computes a direction.  One rank. */
        QN_PROJECTED_NEWTON = 7 /* ProjectedNewton, newton/projected_newton.rs */,
-       QN_SPECTRAL_PROJECTED_NEWTON = 8 /* SpectralProjectedNewton, newton/spn.rs */ };
+       QN_SPECTRAL_PROJECTED_NEWTON = 8 /* SpectralProjectedNewton, newton/spn.rs */,
+       /* Broyden (quasi_newton/broyden.rs; BroydenB, broyden_b.rs, once qn_solver_set_bounds is called): BFGS's skeleton -- d = -H g (P(x - H g) - x
+        * when bounded), s_norm / y_norm tests and skip rule, the oracle call sequence -- with the update H += ((s - H y) s') H / (s . y) AS WRITTEN
+        * (broyden.rs:115-118): rank-1, H + c a w' with a = s - H y, w = H' s, c = 1 / s.y.  H is NOT symmetric after the first update, and the secant
+        * equation does not hold.  Line searches: every one but QN_LS_GLL_QUADRATIC.  Every oracle kind; one rank (a row-sharded context:
+        * QN_ERROR_INPUT_PARAMS); synchronous requests; the full row-major H streamed once per iteration by csrc/qn_rank1.hip.h (QN_PATH_RANK1).
+        * qn_solver_set_inv_hessian accepts any matrix. */
+       QN_BROYDEN = 9 /* Broyden, quasi_newton/broyden.rs */ };
 typedef struct qn_solver qn_solver;
 
 /* BFGS::new(tol, x0) / DFP::new / GradientDescent::new(grad_tol, x0): H = I (no identity copy is kept) */
 int qn_solver_create(qn_context* ctx, int method, double tol, const double* x0_host, size_t n, qn_solver** out);
 void qn_solver_destroy(qn_solver* s);
-/* Row f4: BFGSB / DFPB / SR1B (bfgs_b.rs:43-77, dfp_b.rs, sr1_b.rs): box bounds on a BFGS / DFP / SR1 solver.  The current x
+/* Row f4: BFGSB / DFPB / SR1B / BroydenB (bfgs_b.rs:43-77, dfp_b.rs, sr1_b.rs, broyden_b.rs): box bounds on a BFGS / DFP / SR1 / Broyden solver.  The current x
  * is projected (bfgs_b.rs:49) and every direction becomes P(x - H g) - x (bfgs_b.rs:72-75). */
 int qn_solver_set_bounds(qn_solver* s, const double* lower_bound_host, const double* upper_bound_host);
 /* QN_SPG: with_lambdas (spg.rs:23-27; defaults 1e-3 / 1e3, :36-37; the current lambda is not clamped again).  Other methods: QN_ERROR_INPUT_PARAMS. */
@@ -270,7 +277,7 @@ int qn_solver_set_inv_hessian(qn_solver* s, const double* h_colmajor_host);
 int qn_solver_compute_direction(qn_solver* s, const double* g_host, double* d_host);
 /* The inverse-Hessian half of the `update_next_iterate` hook on its own (bfgs.rs:92-130, dfp.rs:92-118), again for a binding
  * that implements LineSearchSolver hook by hook: records s_norm / y_norm, skips the update when either is below tol
- * (bfgs.rs:103-109), else applies the BFGS / DFP secant update to the device-resident matrix. */
+ * (bfgs.rs:103-109), else applies the BFGS / DFP / Broyden update to the device-resident matrix (Broyden: also when bounded). */
 int qn_solver_secant_update(qn_solver* s, const double* s_host, const double* y_host);
 
 /* ---- build-side instrumentation (not in the reference) ---- */
@@ -332,6 +339,7 @@ typedef struct {
                                   one-workgroup launch that runs the state machine: H's share past the Infinity Cache, and the log-sum-exp objective */
 #define QN_PATH_VECTOR 64u     /* the first-order family's device-wide vector kernels (csrc/qn_vec.hip.h): QN_SPG, QN_PROJECTED_GRADIENT */
 #define QN_PATH_PNEWTON 128u   /* ... with the direction from a Cholesky solve: QN_PROJECTED_NEWTON, QN_SPECTRAL_PROJECTED_NEWTON (set beside QN_PATH_VECTOR) */
+#define QN_PATH_RANK1 256u     /* QN_BROYDEN's H passes: the square-tile kernel of csrc/qn_rank1.hip.h (non-symmetric rank-1 update, row AND column sums in one stream of H) */
 int qn_solver_get_stats(qn_solver* s, qn_stats* out);
 /* profiling != 0: bracket every launch with HIP events on the solver's stream (slower; for roofline reports) */
 int qn_solver_set_profiling(qn_solver* s, int on);

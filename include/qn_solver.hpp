@@ -275,6 +275,20 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
 using BFGS = LineSearchSolver<QN_BFGS>;                       // quasi_newton/bfgs.rs
 using DFP = LineSearchSolver<QN_DFP>;                         // quasi_newton/dfp.rs
 using GradientDescent = LineSearchSolver<QN_GRADIENT_DESCENT>; // steepest_descent/gradient_descent.rs
+using Broyden = LineSearchSolver<QN_BROYDEN>;                 // quasi_newton/broyden.rs
+
+// quasi_newton/broyden_b.rs: new(tol, x0, lower_bound, upper_bound); x0 is projected (:51), d = P(x - H g) - x (:73-77); everything else is Broyden's
+class BroydenB : public LineSearchSolver<QN_BROYDEN> {
+    DVector lb_, ub_;
+  public:
+    BroydenB(Floating tol, const DVector& x0, DVector lower_bound, DVector upper_bound, Context& ctx = Context::default_context())
+        : LineSearchSolver<QN_BROYDEN>(tol, x0, ctx), lb_(std::move(lower_bound)), ub_(std::move(upper_bound)) {
+        check(qn_solver_set_bounds(this->handle(), lb_.data(), ub_.data()));
+    }
+    static BroydenB new_(Floating tol, const DVector& x0, DVector lb, DVector ub) { return BroydenB(tol, x0, std::move(lb), std::move(ub)); }
+    const DVector& lower_bound() const { return lb_; }
+    const DVector& upper_bound() const { return ub_; }
+};
 
 // The bounded first-order solvers (O(n) device memory): the box, projected_gradient (ls_solver.rs:121-133), has_converged on its
 // infinity norm (spg.rs:89-92, projected_gradient_descent.rs:76-83).

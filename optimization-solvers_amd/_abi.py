@@ -10,6 +10,7 @@ OK, MAX_ITER_REACHED, OUT_OF_DOMAIN, ERROR_INPUT_PARAMS, ABNORMAL_TERMINATION = 
 LS_MORETHUENTE, LS_BACKTRACKING, LS_MORETHUENTE_B, LS_BACKTRACKING_B, LS_GLL_QUADRATIC = 0, 1, 2, 3, 4
 ORACLE_HOST, ORACLE_DEVICE_FN, ORACLE_OBJECTIVE = 0, 1, 2
 BFGS, DFP, GRADIENT_DESCENT, NEWTON, SR1, SPG, PROJECTED_GRADIENT, PROJECTED_NEWTON, SPECTRAL_PROJECTED_NEWTON = 0, 1, 2, 3, 4, 5, 6, 7, 8
+BROYDEN = 9  # quasi_newton/broyden.rs (BroydenB once bounds are set)
 UNIQUE_ID_BYTES = 128
 
 dp = C.POINTER(C.c_double)
@@ -58,6 +59,7 @@ class Stats(C.Structure):
 
 
 PATH_FUSED, PATH_SYM, PATH_SYM_GENERIC, PATH_PIPELINED, PATH_SYM2, PATH_TILES1, PATH_VECTOR, PATH_PNEWTON = 1, 2, 4, 8, 16, 32, 64, 128
+PATH_RANK1 = 256
 
 
 # every symbol include/qn_hip.h declares: (name, restype, argtypes)

@@ -47,6 +47,7 @@ enum QnState : int32_t {
     QN_ST_LS_ONLY // qn_compute_step_len: g.d for the caller's direction, then the line search alone
 };
 
+#define QN_METHOD_BROYDEN 9 // == QN_BROYDEN (include/qn_hip.h): the one method whose pending update is rank-1 and not symmetric (qn_rank1.hip.h)
 #define QN_LS_MODIFIED_BIT (1 << 30) // trace: ls_cases bit 30 = the modified-updating switch of morethuente.rs:212-215 was thrown
 
 struct QnTraceRec { // == qn_trace_rec (include/qn_hip.h)
@@ -113,6 +114,7 @@ struct QnCtl {
     int32_t hp_nrhs, hp_lazy;
 
     // ---- pending symmetric rank-2 update: H_true = H_stored + c_su (sp up' + up sp') + c_ss sp sp' + c_uu up up'
+    //      (QN_METHOD_BROYDEN: the rank-1, non-symmetric H_true = H_stored + c_ss sp up' with sp = a = s - H y, up = w = H' s, c_ss = 1 / s.y)
     int32_t pending;
     int32_t spec_tiles; // sym2, folded accept-reduce: the launch that formed the vectors of the accepted point ran the update tiles of the
                         // pass the machine is about to ask for (qn_sym2.hip.h, s2_hpass_kernel); cleared when that request is met

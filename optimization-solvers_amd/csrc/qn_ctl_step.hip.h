@@ -852,18 +852,23 @@ __global__ __launch_bounds__(QN_CTL_TPB) void ctl_step_kernel(QnCtl* __restrict_
             const bool lazy = c.hp_lazy != 0;
             const int method = c.method;
             const double ys = c.ys;
+            // Broyden (broyden.rs:115-118) in rank-1 form H + c a w': w = H' s is already in `up` (r1_reduce_kernel's column totals), a = s - u goes
+            // where the rank-2 methods keep s, and the lazy direction below is theirs with c_ss = c = 1 / s.y and (w . g+) in the place of (s . g+)
+            const bool r1 = method == QN_METHOD_BROYDEN;
             double p[4] = {0.0, 0.0, 0.0, 0.0};
             for (int base = 0; base < n_pad; base += 4 * tpb) {
                 QN_TILE_IDX(base)
-                double uv[4], sv[4], yv[4], gv[4];
+                double uv[4], sv[4], yv[4], gv[4], wv[4];
 #pragma unroll
                 for (int u = 0; u < 4; ++u) {
                     uv[u] = hp_val(V, nrhs, 0, idx[u]); sv[u] = vs[idx[u]]; yv[u] = vy[idx[u]]; gv[u] = vg[idx[u]];
+                    wv[u] = r1 ? vup[idx[u]] : 0.0;
                     if (lazy) qn_keepalive(hp_val(V, nrhs, 1, idx[u])); // warm v for the second sweep
                 }
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
                     if (ok[u]) {
+                        if (r1) { vsp[idx[u]] = sv[u] - uv[u]; p[2] = __builtin_fma(wv[u], gv[u], p[2]); continue; }
                         vup[idx[u]] = uv[u]; vsp[idx[u]] = sv[u];
                         p[0] = __builtin_fma(yv[u], uv[u], p[0]);
                         p[1] = __builtin_fma(uv[u], gv[u], p[1]);
@@ -876,6 +881,7 @@ __global__ __launch_bounds__(QN_CTL_TPB) void ctl_step_kernel(QnCtl* __restrict_
             double c_ss, c_su, c_uu;
             if (method == 0) { const double rho = 1.0 / ys; c_su = -rho; c_ss = rho * rho * yu + rho; c_uu = 0.0; }
             else if (method == 4) { c_ss = 1.0 / p[3]; c_su = -c_ss; c_uu = c_ss; } // (s-u)(s-u)'/((s-u).y) = c (ss' - (su' + us') + uu')
+            else if (r1) { c_ss = 1.0 / ys; c_su = 0.0; c_uu = 0.0; } // ((s - u) s') H / s.dot(y)
             else { c_ss = 1.0 / ys; c_su = 0.0; c_uu = -1.0 / yu; }
             double q[2] = {0.0, 0.0};
             double lazy_cand = INFINITY;

@@ -3,6 +3,7 @@
 // on it, fused rows, generic control step), the placement probe of H.
 #pragma once
 struct Run;
+static int r1_enqueue_req(qn_solver* s); // QN_BROYDEN: qn_host_rank1.hip.h
 static int enqueue_newton(qn_solver* s, const qn_oracle* o, qn_objective* obj);
 
 // the oracle of a minimize call, validated; *obj: its device objective, if it is one (whether the solver family runs that objective is the caller's test)
@@ -40,6 +41,7 @@ struct Run {
     bool proj = false;        // ... whose line search is BackTrackingB: every evaluation slot has s2_proj_kernel in front of it (projected trial points)
     bool btb = false;         // ... BackTrackingB on this path at all (proj: with the projection as a launch of its own; QnS2Args.projfold: inside the evaluation kernel)
     bool bnd = false;         // ... a bounded run on it (BFGSB / DFPB, MoreThuenteB): one more launch per iteration, s2_dir_kernel (qn_sym2.hip.h)
+    bool rank1 = false;       // Broyden: the generic machine, its H passes by the rank-1 tile kernel (qn_rank1.hip.h)
     bool tiles1 = false;      // the update pass's tiles through the first-generation tile kernel (one workgroup per tile, two per CU) behind a
                               // one-workgroup launch that runs the machine: H's share past the Infinity Cache (see plan_run)
     QnS2Args s2{};
@@ -466,10 +468,12 @@ static int launch_ctl_mask(Run& r, int expect_mask) {
     const bool hp = (expect_mask & ((1 << QN_PH_REQ_HPASS) | (1 << QN_PH_REQ_HPASS_EVAL))) != 0;
     const bool ev = (expect_mask & ((1 << QN_PH_REQ_EVAL) | (1 << QN_PH_REQ_HPASS_EVAL))) != 0;
     const dim3 blk(r.fused ? ((hp && ev) ? 768 : 576) : QN_CTL_TPB);
+    QnVecs V = s->V;
+    if (r.rank1) V.hcs = 1; // (r1_reduce_kernel leaves totals: one "column split", whatever qn_solver_set_tiling asked of the row kernels)
     if (r.oracle_tpl == QN_ORACLE_QUAD)
-        hipLaunchKernelGGL(ctl_step_kernel<QN_ORACLE_QUAD>, dim3(1), blk, 0, s->ctx->stream, s->ctl, s->V, expect_mask);
+        hipLaunchKernelGGL(ctl_step_kernel<QN_ORACLE_QUAD>, dim3(1), blk, 0, s->ctx->stream, s->ctl, V, expect_mask);
     else
-        hipLaunchKernelGGL(ctl_step_kernel<QN_ORACLE_GENERIC>, dim3(1), blk, 0, s->ctx->stream, s->ctl, s->V, expect_mask);
+        hipLaunchKernelGGL(ctl_step_kernel<QN_ORACLE_GENERIC>, dim3(1), blk, 0, s->ctx->stream, s->ctl, V, expect_mask);
     s->stats.launches++;
     HIPCHK(hipGetLastError());
     return QN_OK;
@@ -665,6 +669,7 @@ static int enqueue_hpass_req(Run& r) {
     qn_solver* s = r.s;
     qn_context* c = s->ctx;
     if (r.fused) return enqueue_hpass_fused(r);
+    if (r.rank1) return r1_enqueue_req(s);
     if (r.sym_generic) {
         QnSymHPassArgs y{};
         y.generic = 1; y.gsp = s->V.sp; y.gup = s->V.up; y.gvy = s->V.y; y.gvg = s->V.g; y.ghp = s->V.hp;

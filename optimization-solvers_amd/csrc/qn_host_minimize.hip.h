@@ -97,6 +97,11 @@ static int plan_run(Run& r, qn_solver* s, qn_linesearch* ls, const qn_oracle* o,
     r.sym = r.fused && (sym_ok || symsh_ok) && r.obj && (r.obj->q_symmetric || r.gobj);
     // the generic path's H pass alone (closures, log-sum-exp objective, SR1, bounded variants): same tiles, sums into V.hp
     r.sym_generic = !r.fused && (sym_ok || symsh_ok) && s->H && s->hcs == 1 && (s->method == QN_BFGS || s->method == QN_DFP || s->method == QN_SR1);
+    // Broyden's H is not symmetric after its first update: none of the predicates above admits the method (fused, gobj, sym, sym_generic, and sym2
+    // below all start from BFGS / DFP / SR1).  It runs the generic machine with synchronous requests, its H passes by qn_rank1.hip.h; n <= 5: the
+    // control kernel alone.
+    r.rank1 = s->method == QN_BROYDEN && !h->small_n;
+    if (s->method == QN_BROYDEN && (r.fused || r.sym || r.sym_generic)) return fail(QN_ABNORMAL_TERMINATION, "Broyden on a symmetric-storage path");
     if ((r.sym || r.sym_generic) && c->world > 1) QNCHK(solver_alloc_symsh_lists(s));
     if (r.sym_generic) {
         if (c->world > 1 && !s->symsh_xg) QNCHK(dev_alloc_zero(&s->symsh_xg, (size_t)c->world * 2 * s->T.n_pad, c->stream));
@@ -165,7 +170,7 @@ static int plan_run(Run& r, qn_solver* s, qn_linesearch* ls, const qn_oracle* o,
     h->status = -1;
     // only the quadratic objective's kernels are predicated on the control block; everything else is serviced synchronously
     const bool can_pipeline = (r.oracle_tpl == QN_ORACLE_QUAD || r.gobj) && !callback && !(c->world > 1 && !c->comm && !c->host_async);
-    r.sync = s->method == QN_NEWTON || s->sync_mode == 1 || (s->sync_mode == -1 && !(can_pipeline && o->memoize)) || !can_pipeline;
+    r.sync = s->method == QN_NEWTON || s->method == QN_BROYDEN || s->sync_mode == 1 || (s->sync_mode == -1 && !(can_pipeline && o->memoize)) || !can_pipeline;
     return QN_OK;
 }
 
@@ -485,7 +490,8 @@ static void finish_stats(Run& r) {
     s->stats.total_xchg_vector += c->n_xchg_vector - r.xv0;
     s->stats.total_xchg_scalar += c->n_xchg_scalar - r.xs0;
     s->stats.path = (r.fused ? QN_PATH_FUSED : 0u) | (r.sym ? QN_PATH_SYM : 0u) | (r.sym_generic ? QN_PATH_SYM_GENERIC : 0u) |
-                    (r.sync ? 0u : QN_PATH_PIPELINED) | (r.sym2 ? QN_PATH_SYM2 : 0u) | ((r.tiles1 || (r.gobj && c->world == 1)) ? QN_PATH_TILES1 : 0u);
+                    (r.sync ? 0u : QN_PATH_PIPELINED) | (r.sym2 ? QN_PATH_SYM2 : 0u) | ((r.tiles1 || (r.gobj && c->world == 1)) ? QN_PATH_TILES1 : 0u) |
+                    (r.rank1 ? QN_PATH_RANK1 : 0u);
 }
 
 static int minimize_impl(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, size_t max_iter_solver, size_t max_iter_line_search,

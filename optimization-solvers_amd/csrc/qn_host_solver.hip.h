@@ -25,6 +25,8 @@ struct qn_solver {
     // symmetric-storage fast path (qn_sym.hip.h): slot buffer, tile count per side, opt-out, "user installed a non-symmetric H"
     double* sym_part = nullptr;
     int sym_nb = 0;
+    double* r1_part = nullptr; // QN_BROYDEN (qn_rank1.hip.h): the tiles' row and column partials, [3][r1_nb][n_pad]
+    int r1_nb = 0;
     bool no_sym = false, h_nonsym = false;
     bool h_lower_stale = false; // a symmetric-storage run is (or was) updating the upper block triangle only
     double *symsh_xg = nullptr, *symsh_gath = nullptr; // row-sharded symmetric storage: gathered partial sums [world][2][n_pad]; mirror staging
@@ -371,6 +373,8 @@ static int vec_state_alloc(qn_solver* s);
 static void vec_state_reset(qn_solver* s);
 static int vec_compute_direction(qn_solver* s, const double* g_host, double* d_host);
 static int bounds_alloc(qn_solver* s);
+static int r1_flush(qn_solver* s); // QN_BROYDEN: qn_host_rank1.hip.h
+static int r1_secant_update(qn_solver* s, const double* s_host, const double* y_host, double ys);
 
 static int solver_alloc_hp(qn_solver* s) {
     if (s->V.hp) { HIPCHK(hipFree(s->V.hp)); s->V.hp = nullptr; }
@@ -384,8 +388,9 @@ static int solver_alloc_hp(qn_solver* s) {
 
 extern "C" int qn_solver_create(qn_context* ctx, int method, double tol, const double* x0_host, size_t n, qn_solver** out) {
     if (!ctx || !x0_host || !out || n == 0) return fail(QN_ERROR_INPUT_PARAMS, "null argument or n == 0");
-    if (method != QN_BFGS && method != QN_DFP && method != QN_GRADIENT_DESCENT && method != QN_NEWTON && method != QN_SR1 && !vec_method(method))
+    if (method != QN_BFGS && method != QN_DFP && method != QN_GRADIENT_DESCENT && method != QN_NEWTON && method != QN_SR1 && method != QN_BROYDEN && !vec_method(method))
         return fail(QN_ERROR_INPUT_PARAMS, "unknown method");
+    if (method == QN_BROYDEN && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "Broyden runs on one rank: its non-symmetric H needs column sums, which a row-sharded context (world > 1) does not have");
     if (vec_method(method) && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient / projected Newton run on one rank");
     if (n > (size_t)1 << 30) return fail(QN_ERROR_INPUT_PARAMS, "n too large");
     HIPCHK(hipSetDevice(ctx->device));
@@ -399,7 +404,7 @@ extern "C" int qn_solver_create(qn_context* ctx, int method, double tol, const d
     s->U = (n >= 16384) ? 2 : 1; // column chunks per loop trip of the fused kernels
     const size_t np = s->T.n_pad;
     hipStream_t st = ctx->stream;
-    if (method == QN_BFGS || method == QN_DFP || method == QN_SR1) {
+    if (method == QN_BFGS || method == QN_DFP || method == QN_SR1 || method == QN_BROYDEN) {
         QNCHK(dev_alloc_zero(&s->H, (size_t)s->T.rpr * np, st));
         hipLaunchKernelGGL(identity_fill_kernel, dim3(2048), dim3(256), 0, st, s->H, s->T); // bfgs.rs:27-39: H = I
         HIPCHK(hipGetLastError());
@@ -437,7 +442,7 @@ extern "C" void qn_solver_destroy(qn_solver* s) {
     for (auto& e : s->event_pool) (void)hipEventDestroy(e);
     if (s->s2_graph_exec) (void)hipGraphExecDestroy(s->s2_graph_exec);
     (void)hipFree(s->H); (void)hipFree(s->vec_block); (void)hipFree(s->V.hp); (void)hipFree(s->V.q);
-    (void)hipFree(s->newton_w); (void)hipFree(s->newton_x); (void)hipFree(s->newton_invl); (void)hipFree(s->newton_inv2); (void)hipFree(s->sym_part); (void)hipFree(s->symsh_xg); (void)hipFree(s->symsh_gath); (void)hipFree(s->newton_hsrc); (void)hipFree(s->newton_fail); (void)hipFree(s->newton_piv); (void)hipFree(s->newton_perm); (void)hipFree(s->newton_panel); (void)hipFree(s->newton_sync); (void)hipFree(s->newton_rec);
+    (void)hipFree(s->newton_w); (void)hipFree(s->newton_x); (void)hipFree(s->newton_invl); (void)hipFree(s->newton_inv2); (void)hipFree(s->sym_part); (void)hipFree(s->r1_part); (void)hipFree(s->symsh_xg); (void)hipFree(s->symsh_gath); (void)hipFree(s->newton_hsrc); (void)hipFree(s->newton_fail); (void)hipFree(s->newton_piv); (void)hipFree(s->newton_perm); (void)hipFree(s->newton_panel); (void)hipFree(s->newton_sync); (void)hipFree(s->newton_rec);
     (void)hipFree(s->bounds_block);
     (void)hipFree(s->vctl); (void)hipFree(s->vpart); (void)hipHostFree(s->hvctl);
     (void)hipFree(s->fused_block); (void)hipFree(s->fused_evp); (void)hipFree(s->fused_hpp);
@@ -614,8 +619,8 @@ static int bounds_upload(qn_solver* s, double* dst, const double* src_host, doub
 
 extern "C" int qn_solver_set_bounds(qn_solver* s, const double* lb_host, const double* ub_host) { // BFGSB::new, bfgs_b.rs:43-63
     if (!s || !lb_host || !ub_host) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
-    if (s->method != QN_BFGS && s->method != QN_DFP && s->method != QN_SR1 && !vec_method(s->method))
-        return fail(QN_ERROR_INPUT_PARAMS, "bounds need a BFGS / DFP / SR1 / SPG / projected-gradient solver");
+    if (s->method != QN_BFGS && s->method != QN_DFP && s->method != QN_SR1 && s->method != QN_BROYDEN && !vec_method(s->method))
+        return fail(QN_ERROR_INPUT_PARAMS, "bounds need a BFGS / DFP / SR1 / Broyden / SPG / projected-gradient solver");
     HIPCHK(hipSetDevice(s->ctx->device));
     QNCHK(bounds_alloc(s));
     QNCHK(bounds_upload(s, s->bounds_block, lb_host, -INFINITY));
@@ -767,6 +772,11 @@ static int flush_pending(qn_solver* s) { // H_stored <- H_true
     QNCHK(fused_export(s));  // the pending update's vectors
     QNCHK(ensure_full_h(s)); // (also from a callback in the middle of a symmetric-storage run)
     if (!s->H || !s->hctl->pending) return QN_OK;
+    if (s->method == QN_BROYDEN) { // the rank-1, non-symmetric pending update: its own pass
+        QNCHK(r1_flush(s));
+        s->hctl->pending = 0;
+        return poke_ctl(s);
+    }
     QnHPassArgs a = hpass_args(s, -1);
     a.force_nrhs = 0; a.force_pending = 1;
     a.c_ss = s->hctl->c_ss; a.c_su = s->hctl->c_su; a.c_uu = s->hctl->c_uu;
@@ -863,8 +873,9 @@ extern "C" int qn_solver_compute_direction(qn_solver* s, const double* g_host, d
 // (u = H y; BFGS: rho = 1/y's, H += -rho (su' + us') + (rho^2 y'u + rho) ss'; DFP: H += ss'/y's - uu'/y'u).
 extern "C" int qn_solver_secant_update(qn_solver* s, const double* s_host, const double* y_host) {
     if (!s || !s_host || !y_host) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
-    if ((s->method != QN_BFGS && s->method != QN_DFP) || s->bounded)
-        return fail(QN_ERROR_INPUT_PARAMS, "secant update: BFGS and DFP only");
+    // (Broyden: bounded or not -- broyden_b.rs:144-149 is broyden.rs:115-118 word for word)
+    if (s->method != QN_BROYDEN && ((s->method != QN_BFGS && s->method != QN_DFP) || s->bounded))
+        return fail(QN_ERROR_INPUT_PARAMS, "secant update: BFGS, DFP and Broyden only");
     qn_context* c = s->ctx;
     HIPCHK(hipSetDevice(c->device));
     QNCHK(flush_pending(s));
@@ -877,6 +888,7 @@ extern "C" int qn_solver_secant_update(qn_solver* s, const double* s_host, const
     h->have_dir = 0; h->have_cur_eval = 0;
     QNCHK(poke_ctl(s));
     if (h->s_norm < s->tol || h->y_norm < s->tol) return QN_OK;
+    if (s->method == QN_BROYDEN) return r1_secant_update(s, s_host, y_host, ys); // H += ((s - H y) s') H / s.y: one pass for u and w = H' s, one to apply
     double* buf = nullptr; // [s | y | u = H y], n_pad each
     HIPCHK(hipMalloc((void**)&buf, 3 * np * sizeof(double)));
     std::vector<double> u(n);

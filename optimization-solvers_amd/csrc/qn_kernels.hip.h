@@ -670,6 +670,17 @@ __device__ __forceinline__ void small_update(double* H, int ld, int n, const dou
         small_matmul(m2, m1, m3, n);
         for (int j = 0; j < n; ++j)
             for (int i = 0; i < n; ++i) H[i * ld + j] = m3[i + j * QN_SMALL_N] + (s[i] * s[j]) * rho;
+    } else if (method == QN_METHOD_BROYDEN) { // broyden.rs:115-118 as written: hy = H y ; numerator = ((s - hy) s') H -- the n x n outer product first,
+        double* hy = scratch + 5 * MM;        // then an n x n by n x n product ; H += numerator / s.dot(y)
+        for (int i = 0; i < n; ++i) hy[i] = h[i] * y[0];
+        for (int j = 1; j < n; ++j)
+            for (int i = 0; i < n; ++i) hy[i] = h[i + j * QN_SMALL_N] * y[j] + hy[i];
+        for (int k = 0; k < n; ++k)
+            for (int i = 0; i < n; ++i) m0[i + k * QN_SMALL_N] = (s[i] - hy[i]) * s[k];
+        small_matmul(m0, h, m1, n);
+        const double den = ref_dot(s, y, n);
+        for (int j = 0; j < n; ++j)
+            for (int i = 0; i < n; ++i) H[i * ld + j] = h[i + j * QN_SMALL_N] + m1[i + j * QN_SMALL_N] / den;
     } else if (method == 4) { // sr1_b.rs:143-146: hy = H y ; shy = s - hy ; H += shy shy' / shy.dot(y)
         double* w = scratch + 5 * MM;
         for (int i = 0; i < n; ++i) w[i] = h[i] * y[0];
@@ -936,6 +947,7 @@ __global__ __launch_bounds__(256) void lse_finish1_kernel(const QnLseArgs a, con
     }
 }
 
+#include "qn_rank1.hip.h"
 #include "qn_fused.hip.h"
 #include "qn_sym.hip.h"
 #include "qn_newton.hip.h"

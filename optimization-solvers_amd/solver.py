@@ -759,6 +759,11 @@ class DFP(_SolverBase):
     METHOD = A.DFP
 
 
+class Broyden(_SolverBase):
+    """quasi_newton/broyden.rs: H += ((s - H y) s') H / (s . y) as written -- H is not symmetric after the first update"""
+    METHOD = A.BROYDEN
+
+
 class GradientDescent(_SolverBase):
     """steepest_descent/gradient_descent.rs (config-1 plumbing)"""
     METHOD = A.GRADIENT_DESCENT
@@ -803,6 +808,11 @@ class DFPB(_BoundedBase):
 
 class SR1B(_BoundedBase):
     METHOD = A.SR1
+
+
+class BroydenB(_BoundedBase):
+    """quasi_newton/broyden_b.rs"""
+    METHOD = A.BROYDEN
 
 
 class _ProjectedBase(_BoundedBase):

@@ -32,6 +32,7 @@ pub const QN_SPG: c_int = 5;
 pub const QN_PROJECTED_GRADIENT: c_int = 6;
 pub const QN_PROJECTED_NEWTON: c_int = 7;
 pub const QN_SPECTRAL_PROJECTED_NEWTON: c_int = 8;
+pub const QN_BROYDEN: c_int = 9;
 
 // qn_option (ABI 5): what rounds 1-5 selected through negative codes of qn_solver_set_tiling; value != 0 on, 0 off
 pub const QN_OPT_GENERIC_KERNELS: c_int = 1;
@@ -68,6 +69,7 @@ pub const QN_PATH_SYM2: u32 = 16;
 pub const QN_PATH_TILES1: u32 = 32;
 pub const QN_PATH_VECTOR: u32 = 64;
 pub const QN_PATH_PNEWTON: u32 = 128;
+pub const QN_PATH_RANK1: u32 = 256;
 
 #[repr(C)] pub struct qn_context { _p: [u8; 0] }
 #[repr(C)] pub struct qn_solver { _p: [u8; 0] }

@@ -615,6 +615,16 @@ gpu_solver!(
     GpuDFP, QN_DFP, true
 );
 gpu_solver!(
+    /// Drop-in for `Broyden` (quasi_newton/broyden.rs): H += ((s - H y) s') H / (s . y) as written.  The inverse Hessian is not symmetric after
+    /// the first update; the GPU streams it whole, once per iteration (QN_PATH_RANK1).
+    GpuBroyden, QN_BROYDEN, true
+);
+gpu_solver!(
+    /// Drop-in for `BroydenB` (quasi_newton/broyden_b.rs): `new(tol, x0).with_bounds(lb, ub)` stands for `new(tol, x0, lb, ub)`;
+    /// x0 is projected, d = P(x - H g) - x.
+    GpuBroydenB, QN_BROYDEN, true
+);
+gpu_solver!(
     /// Drop-in for `GradientDescent` (steepest_descent/gradient_descent.rs:7-82); `tol` is its `grad_tol`.
     GpuGradientDescent, QN_GRADIENT_DESCENT, false
 );
@@ -677,6 +687,7 @@ bounded_first_order!(GpuProjectedGradientDescent);
 bounded_first_order!(GpuSpectralProjectedGradient);
 bounded_first_order!(GpuProjectedNewton);
 bounded_first_order!(GpuSpectralProjectedNewton);
+bounded_first_order!(GpuBroydenB); // (the same `with_bounds` / `HasBounds`; `grad_tol()` is its `tol`)
 
 macro_rules! newton_factorisations {
     ($name:ident) => {
