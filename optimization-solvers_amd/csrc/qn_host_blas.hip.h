@@ -6,6 +6,12 @@
 // ------------------------------------------------------------------------------------------------
 extern "C" int qn_dev_alloc(qn_context* c, size_t bytes, void** out) { HIPCHK(hipSetDevice(c->device)); HIPCHK(hipMalloc(out, bytes)); return QN_OK; }
 extern "C" int qn_dev_free(qn_context* c, void* p) { HIPCHK(hipSetDevice(c->device)); HIPCHK(hipFree(p)); return QN_OK; }
+// (those two hand memory to the caller: raw and uncounted.)  What the library's own DevBuf / PinnedBuf owners hold at this moment, process-wide --
+// diagnostics, not part of include/qn_hip.h: a test reads it before and after to see that nothing is left behind
+extern "C" int qn_debug_live_allocations(size_t* count, size_t* bytes) {
+    *count = g_live_allocations.load(std::memory_order_relaxed); *bytes = g_live_bytes.load(std::memory_order_relaxed);
+    return QN_OK;
+}
 extern "C" int qn_h2d(qn_context* c, void* dst, const void* src, size_t bytes) {
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
@@ -43,13 +49,12 @@ extern "C" int qn_axpy(qn_context* c, size_t n, const double* x, double t, const
 }
 extern "C" int qn_dot(qn_context* c, size_t n, const double* a, const double* b, double* out_host) {
     HIPCHK(hipSetDevice(c->device));
-    double* tmp = nullptr;
-    HIPCHK(hipMalloc((void**)&tmp, sizeof(double)));
+    DevBuf<double> tmp;
+    QNCHK(tmp.alloc(1));
     hipLaunchKernelGGL(prim_dot_kernel, dim3(1), dim3(QN_CTL_TPB), 0, c->stream, (int)n, a, b, tmp);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out_host, tmp, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipFree(tmp));
     return QN_OK;
 }
 extern "C" int qn_nrm2(qn_context* c, size_t n, const double* a, double* out_host) { // norm = sqrt(dot(a, a)), bfgs.rs:74,97,99

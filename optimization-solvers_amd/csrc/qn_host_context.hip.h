@@ -56,6 +56,88 @@ static int rccl_load() {
     } while (0)
 
 // ------------------------------------------------------------------------------------------------
+// owners: every device or pinned buffer the library keeps belongs to exactly one DevBuf / PinnedBuf -- a member of the object that uses it, or a
+// local of the call that needs it for a moment -- and is released when that owner goes.  A new buffer is a new owner field and nothing else.
+// Move-only; they convert to T* so that launch arguments and pointer arithmetic read as with a plain pointer.  What they hold is counted
+// (qn_debug_live_allocations).  (Pointer + bytes, not pointer + count: an owner of a forward-declared T is destroyed where sizeof(T) is unknown.)
+// ------------------------------------------------------------------------------------------------
+static std::atomic<size_t> g_live_allocations{0}, g_live_bytes{0};
+
+template <class T, bool PINNED>
+struct OwnedBuf {
+    OwnedBuf() = default;
+    OwnedBuf(const OwnedBuf&) = delete;
+    OwnedBuf& operator=(const OwnedBuf&) = delete;
+    OwnedBuf(OwnedBuf&& o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr; o.bytes_ = 0; }
+    OwnedBuf& operator=(OwnedBuf&& o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; bytes_ = o.bytes_; o.p_ = nullptr; o.bytes_ = 0; }
+        return *this;
+    }
+    ~OwnedBuf() { reset(); }
+    void reset() {
+        if (p_) {
+            (void)(PINNED ? hipHostFree(p_) : hipFree(p_));
+            g_live_allocations.fetch_sub(1, std::memory_order_relaxed); g_live_bytes.fetch_sub(bytes_, std::memory_order_relaxed);
+        }
+        p_ = nullptr; bytes_ = 0;
+    }
+    T* get() const { return p_; }
+    size_t count() const { return bytes_ / sizeof(T); }
+    operator T*() const { return p_; }
+    T* operator->() const { return p_; }
+
+protected:
+    // the result of a hipMalloc / hipHostMalloc into the (empty) owner.  A refusal is reported as HIPCHK reports ("<expr>: <hip string>") and
+    // taken off the runtime's last-error slot: the caller has the status, the next launch's hipGetLastError() must not find it
+    int took(hipError_t e, void* p, size_t bytes, const char* expr) {
+        if (e != hipSuccess) { (void)hipGetLastError(); return fail(QN_ABNORMAL_TERMINATION, std::string(expr) + ": " + hipGetErrorString(e)); }
+        if (!p) return QN_OK; // (zero bytes)
+        p_ = (T*)p; bytes_ = bytes;
+        g_live_allocations.fetch_add(1, std::memory_order_relaxed); g_live_bytes.fetch_add(bytes, std::memory_order_relaxed);
+        return QN_OK;
+    }
+    T* p_ = nullptr;
+    size_t bytes_ = 0;
+};
+
+template <class T>
+struct DevBuf : OwnedBuf<T, false> { // hipMalloc memory
+    int alloc(size_t count) { // what it held is released first; a failure leaves it empty
+        this->reset();
+        void* p = nullptr;
+        const hipError_t e = hipMalloc(&p, count * sizeof(T));
+        return this->took(e, p, count * sizeof(T), "hipMalloc(&p, count * sizeof(T))");
+    }
+    int alloc_zero(size_t count, hipStream_t st) {
+        QNCHK(alloc(count));
+        HIPCHK(hipMemsetAsync(this->p_, 0, count * sizeof(T), st));
+        return QN_OK;
+    }
+    // `count` elements: what it holds is kept when it is exactly that many, replaced otherwise (with a stream: by zeroed memory)
+    int ensure(size_t count) { return this->p_ && this->bytes_ == count * sizeof(T) ? QN_OK : alloc(count); }
+    int ensure(size_t count, hipStream_t st) { return this->p_ && this->bytes_ == count * sizeof(T) ? QN_OK : alloc_zero(count, st); }
+};
+
+template <class T>
+struct PinnedBuf : OwnedBuf<T, true> { // hipHostMalloc memory; it keeps the flags it was allocated with
+    unsigned flags = hipHostMallocDefault;
+    int alloc(size_t count, unsigned flags_ = hipHostMallocDefault) {
+        this->reset();
+        void* p = nullptr;
+        const hipError_t e = hipHostMalloc(&p, count * sizeof(T), flags_);
+        flags = flags_;
+        return this->took(e, p, count * sizeof(T), "hipHostMalloc(&p, count * sizeof(T), flags)");
+    }
+    int alloc_zero(size_t count, unsigned flags_ = hipHostMallocDefault) {
+        QNCHK(alloc(count, flags_));
+        memset((void*)this->p_, 0, count * sizeof(T));
+        return QN_OK;
+    }
+};
+
+struct ScopedEvent { hipEvent_t e = nullptr; ~ScopedEvent() { if (e) (void)hipEventDestroy(e); } }; // an event for the length of a call
+
+// ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
 struct qn_context {
@@ -78,7 +160,7 @@ struct qn_context {
     int use_allreduce = 0; // symmetric-storage sharded runs: ncclAllReduce of the partial n-vectors instead of all-gather + rank-order sum
     int trial_vector = 0;  // ... the trial's partial n-vector in ONE grouped collective with its evaluation scalars (qn_context_set_trial_vector_exchange)
     int host_async = 0;
-    double* pin = nullptr; // [send (cap) | recv (cap * world)]
+    PinnedBuf<double> pin; // [send (cap) | recv (cap * world)]
     size_t pin_cap = 0;
     int host_async_failed = 0;
 };
@@ -164,7 +246,6 @@ extern "C" void qn_context_destroy(qn_context* c) {
     if (c->stream_lu) { (void)hipStreamSynchronize(c->stream_lu); (void)hipStreamDestroy(c->stream_lu); }
     for (auto e : c->la_events) (void)hipEventDestroy(e);
     if (c->stream) { (void)hipStreamSynchronize(c->stream); (void)hipStreamDestroy(c->stream); }
-    if (c->pin) (void)hipHostFree(c->pin);
     delete c;
 }
 extern "C" int qn_context_synchronize(qn_context* c) {
@@ -212,10 +293,8 @@ static int exchange(qn_context* c, double* buf, size_t count) {
     if (c->host_async) { // stream-ordered: D2H copy, host node, H2D copy; the caller's next synchronisation covers all three
         if (count > c->pin_cap) {
             HIPCHK(hipStreamSynchronize(c->stream)); // earlier nodes may still use the old staging area
-            if (c->pin) HIPCHK(hipHostFree(c->pin));
-            c->pin = nullptr;
             c->pin_cap = std::max(count, (size_t)1 << 16);
-            HIPCHK(hipHostMalloc((void**)&c->pin, c->pin_cap * (size_t)(c->world + 1) * sizeof(double), hipHostMallocDefault));
+            QNCHK(c->pin.alloc(c->pin_cap * (size_t)(c->world + 1)));
         }
         HIPCHK(hipMemcpyAsync(c->pin, buf + (size_t)c->rank * count, count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipLaunchHostFunc(c->stream, host_xchg_node, new HostXchgNode{c, count}));
@@ -310,8 +389,8 @@ extern "C" int qn_comm_selftest(qn_context* c) {
     RcclComm comm = nullptr;
     RCCLCHK(g_rccl.CommInitRank(&comm, 1, id, 0));
     const size_t count = 1024;
-    double* buf = nullptr;
-    HIPCHK(hipMalloc((void**)&buf, count * sizeof(double)));
+    DevBuf<double> buf;
+    QNCHK(buf.alloc(count));
     std::vector<double> h(count), back(count, 0.0);
     for (size_t i = 0; i < count; ++i) h[i] = 0.5 * (double)i - 3.0;
     HIPCHK(hipMemcpyAsync(buf, h.data(), count * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -319,7 +398,6 @@ extern "C" int qn_comm_selftest(qn_context* c) {
     HIPCHK(hipMemcpyAsync(back.data(), buf, count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     g_rccl.CommDestroy(comm);
-    HIPCHK(hipFree(buf));
     if (memcmp(h.data(), back.data(), count * sizeof(double)) != 0) return fail(QN_ABNORMAL_TERMINATION, "RCCL self-test: data mismatch");
     return QN_OK;
 }
@@ -334,26 +412,19 @@ extern "C" int qn_context_exchange_probe(qn_context* c, size_t count, int reps, 
     out_us[0] = out_us[1] = out_us[2] = 0.0;
     if (c->world == 1) return QN_OK;
     HIPCHK(hipSetDevice(c->device));
-    double* buf = nullptr;
-    HIPCHK(hipMalloc((void**)&buf, count * (size_t)c->world * sizeof(double)));
-    HIPCHK(hipMemsetAsync(buf, 0, count * (size_t)c->world * sizeof(double), c->stream));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int st = QN_OK;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) st = fail(QN_ABNORMAL_TERMINATION, "exchange probe: event creation failed");
+    DevBuf<double> buf;
+    QNCHK(buf.alloc_zero(count * (size_t)c->world, c->stream));
+    ScopedEvent e0, e1;
+    if (hipEventCreate(&e0.e) != hipSuccess || hipEventCreate(&e1.e) != hipSuccess) return fail(QN_ABNORMAL_TERMINATION, "exchange probe: event creation failed");
     std::vector<float> us;
-    for (int r = 0; r < reps + 2 && st == QN_OK; ++r) { // (two untimed ones first: connection set-up, first-touch)
-        if (hipEventRecord(e0, c->stream) != hipSuccess) { st = fail(QN_ABNORMAL_TERMINATION, "exchange probe: event record"); break; }
-        st = exchange(c, buf, count);
-        if (st != QN_OK) break;
-        if (hipEventRecord(e1, c->stream) != hipSuccess || hipEventSynchronize(e1) != hipSuccess) { st = fail(QN_ABNORMAL_TERMINATION, "exchange probe: event"); break; }
+    for (int r = 0; r < reps + 2; ++r) { // (two untimed ones first: connection set-up, first-touch)
+        if (hipEventRecord(e0.e, c->stream) != hipSuccess) return fail(QN_ABNORMAL_TERMINATION, "exchange probe: event record");
+        QNCHK(exchange(c, buf, count));
+        if (hipEventRecord(e1.e, c->stream) != hipSuccess || hipEventSynchronize(e1.e) != hipSuccess) return fail(QN_ABNORMAL_TERMINATION, "exchange probe: event");
         float ms = 0.f;
-        if (hipEventElapsedTime(&ms, e0, e1) != hipSuccess) { st = fail(QN_ABNORMAL_TERMINATION, "exchange probe: elapsed time"); break; }
+        if (hipEventElapsedTime(&ms, e0.e, e1.e) != hipSuccess) return fail(QN_ABNORMAL_TERMINATION, "exchange probe: elapsed time");
         if (r >= 2) us.push_back(1e3f * ms);
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    (void)hipFree(buf);
-    if (st != QN_OK) return st;
     if (c->host_async_failed) { c->host_async_failed = 0; return fail(QN_ABNORMAL_TERMINATION, "host exchange callback failed"); }
     std::sort(us.begin(), us.end());
     out_us[0] = us[us.size() / 2]; out_us[1] = us.front(); out_us[2] = us.back();
@@ -367,20 +438,15 @@ extern "C" int qn_context_comm_check(qn_context* c) {
     if (c->world == 1) return QN_OK;
     HIPCHK(hipSetDevice(c->device));
     const size_t count = 4096, total = count * (size_t)c->world;
-    double* buf = nullptr;
-    HIPCHK(hipMalloc((void**)&buf, total * sizeof(double)));
+    DevBuf<double> buf;
+    QNCHK(buf.alloc(total));
     std::vector<double> h(total, -1.0);
     for (size_t i = 0; i < count; ++i) h[(size_t)c->rank * count + i] = 1000.0 * (double)c->rank + 0.25 * (double)i;
     HIPCHK(hipMemcpyAsync(buf, h.data(), total * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    int st = exchange(c, buf, count);
-    if (st == QN_OK) {
-        hipError_t e = hipMemcpyAsync(h.data(), buf, total * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) st = fail(QN_ABNORMAL_TERMINATION, std::string("comm check: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(buf);
-    if (st != QN_OK) return st;
+    QNCHK(exchange(c, buf, count));
+    HIPCHK(hipMemcpyAsync(h.data(), buf, total * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     for (int r = 0; r < c->world; ++r)
         for (size_t i = 0; i < count; ++i)
             if (h[(size_t)r * count + i] != 1000.0 * (double)r + 0.25 * (double)i)
@@ -388,28 +454,22 @@ extern "C" int qn_context_comm_check(qn_context* c) {
     // ... and the GROUPED path the row kernels use (three all-gathers of different sizes between ncclGroupStart / ncclGroupEnd:
     // vector slices and per-workgroup partial sums), verified the same way
     const size_t counts[3] = {1024, 1024, 9 * 32};
-    double* gb[3] = {nullptr, nullptr, nullptr};
+    DevBuf<double> gb[3];
     std::vector<double> gh[3];
-    for (int k = 0; k < 3 && st == QN_OK; ++k) {
+    for (int k = 0; k < 3; ++k) {
         const size_t tot = counts[k] * (size_t)c->world;
         gh[k].assign(tot, -1.0);
         for (size_t i = 0; i < counts[k]; ++i) gh[k][(size_t)c->rank * counts[k] + i] = 1e6 * (k + 1) + 1000.0 * (double)c->rank + 0.5 * (double)i;
-        hipError_t e = hipMalloc((void**)&gb[k], tot * sizeof(double));
-        if (e == hipSuccess) e = hipMemcpyAsync(gb[k], gh[k].data(), tot * sizeof(double), hipMemcpyHostToDevice, c->stream);
-        if (e != hipSuccess) st = fail(QN_ABNORMAL_TERMINATION, std::string("comm check: ") + hipGetErrorString(e));
+        QNCHK(gb[k].alloc(tot));
+        HIPCHK(hipMemcpyAsync(gb[k], gh[k].data(), tot * sizeof(double), hipMemcpyHostToDevice, c->stream));
     }
-    if (st == QN_OK && hipStreamSynchronize(c->stream) != hipSuccess) st = fail(QN_ABNORMAL_TERMINATION, "comm check: synchronize");
-    if (st == QN_OK) {
-        const XchgItem items[3] = {{gb[0], counts[0]}, {gb[1], counts[1]}, {gb[2], counts[2]}};
-        st = exchange_group(c, items, 3);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const XchgItem items[3] = {{gb[0], counts[0]}, {gb[1], counts[1]}, {gb[2], counts[2]}};
+    QNCHK(exchange_group(c, items, 3));
+    for (int k = 0; k < 3; ++k) {
+        HIPCHK(hipMemcpyAsync(gh[k].data(), gb[k], gh[k].size() * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
     }
-    for (int k = 0; k < 3 && st == QN_OK; ++k) {
-        hipError_t e = hipMemcpyAsync(gh[k].data(), gb[k], gh[k].size() * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) st = fail(QN_ABNORMAL_TERMINATION, std::string("comm check: ") + hipGetErrorString(e));
-    }
-    for (int k = 0; k < 3; ++k) (void)hipFree(gb[k]);
-    if (st != QN_OK) return st;
     if (c->host_async_failed) { c->host_async_failed = 0; return fail(QN_ABNORMAL_TERMINATION, "host exchange callback failed"); }
     for (int k = 0; k < 3; ++k)
         for (int r = 0; r < c->world; ++r)
@@ -423,9 +483,10 @@ __global__ void qn_empty_kernel() {}
 extern "C" int qn_context_event_bracket_overhead(qn_context* c, int reps, double* out_ms) {
     if (!c || !out_ms || reps < 1) return fail(QN_ERROR_INPUT_PARAMS, "bad arguments");
     HIPCHK(hipSetDevice(c->device));
-    hipEvent_t a = nullptr, b = nullptr;
-    HIPCHK(hipEventCreate(&a));
-    HIPCHK(hipEventCreate(&b));
+    ScopedEvent ea, eb;
+    HIPCHK(hipEventCreate(&ea.e));
+    HIPCHK(hipEventCreate(&eb.e));
+    const hipEvent_t a = ea.e, b = eb.e;
     // A bracket around k empty kernels reports fixed + k * (one empty dispatch).  The fixed part -- what a bracket adds to the
     // duration of the single kernel inside it -- is 2 * bracket(1) - bracket(2).
     double total[2] = {0.0, 0.0};
@@ -441,15 +502,7 @@ extern "C" int qn_context_event_bracket_overhead(qn_context* c, int reps, double
             if (i >= 5) total[k - 1] += ms; // the first few carry one-off costs
         }
     }
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
     const double b1 = total[0] / reps, b2 = total[1] / reps;
     *out_ms = std::max(0.0, 2.0 * b1 - b2);
-    return QN_OK;
-}
-
-static int dev_alloc_zero(double** p, size_t count, hipStream_t st) {
-    HIPCHK(hipMalloc((void**)p, count * sizeof(double)));
-    HIPCHK(hipMemsetAsync(*p, 0, count * sizeof(double), st));
     return QN_OK;
 }

@@ -393,22 +393,15 @@ static int place_h(Run& r) {
     // ... and, in front of every timed pass, what an iteration has in front of it: two evaluations (Q's half streamed twice).  Timed
     // alone on H the update kernel showed the same 24.4 us on allocations where, in the run, it then took 29.6-30.3 us (2-3 processes
     // in 20, tools/modes_ab.sh): the slow mode is H sharing the Infinity Cache with Q, not H by itself.
-    QnCtl* pe = nullptr;
-    if (hipHostMalloc((void**)&pe, sizeof(QnCtl), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) { (void)hipGetLastError(); pe = nullptr; }
+    PinnedBuf<QnCtl> pe;
+    (void)pe.alloc(1, hipHostMallocMapped | hipHostMallocCoherent); // (none: the passes are timed without the evaluations)
     if (pe) {
         memcpy(pe, s->hctl, sizeof(QnCtl));
         pe->phase = QN_PH_REQ_EVAL; pe->serviced = 0; pe->sym2 = 1; pe->fused = 1; pe->sc = 0; pe->xc = 0;
         pe->ev_kind = QN_REQ_T; pe->t = 1.0; pe->status = -1;
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) { // no probe: H stays where it is, nothing is left behind
-        (void)hipGetLastError();
-        if (e0) (void)hipEventDestroy(e0);
-        if (pe) (void)hipHostFree(pe);
-        return QN_OK;
-    }
-    // (every failure below -- inside time_on too -- comes back as `status` and leaves through the one cleanup path at the end: the
-    // candidates that are not kept, the events and the pinned block are freed, H stays the solver's own)
+    ScopedEvent e0, e1;
+    if (hipEventCreate(&e0.e) != hipSuccess || hipEventCreate(&e1.e) != hipSuccess) { (void)hipGetLastError(); return QN_OK; } // no probe: H stays where it is
     auto time_on = [&](double* H, float* out_us) -> int {
         QnS2Args a = r.s2;
         a.H = H; a.parity = 0; a.ctl_first = pc; a.rep_seq = 0;
@@ -420,44 +413,43 @@ static int place_h(Run& r) {
                 ae.ctl_first = pe;
                 for (int e = 0; e < 2; ++e) s2_launch_eval_plain(st, ae);
             }
-            HIPCHK(hipEventRecord(e0, st));
+            HIPCHK(hipEventRecord(e0.e, st));
             if (s->method == QN_BFGS) hipLaunchKernelGGL((s2_hpass_kernel<false, true, false>), dim3(a.G), dim3(QN_S2_TPB), 0, st, a);
             else hipLaunchKernelGGL((s2_hpass_kernel<false, false, false>), dim3(a.G), dim3(QN_S2_TPB), 0, st, a);
-            HIPCHK(hipEventRecord(e1, st));
-            HIPCHK(hipEventSynchronize(e1));
+            HIPCHK(hipEventRecord(e1.e, st));
+            HIPCHK(hipEventSynchronize(e1.e));
             float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+            HIPCHK(hipEventElapsedTime(&ms, e0.e, e1.e));
             t[rep] = ms * 1e3f;
         }
         std::sort(t + 2, t + 6); // (the first two repetitions bring the tiles in)
         *out_us = t[3];
         return QN_OK;
     };
-    double* cand[3] = {s->H, nullptr, nullptr};
+    // The candidates beside the solver's own H.  Whatever way this function is left -- a failure inside time_on too -- the stream is idle
+    // before one of them (or the pinned block, or the H that was not kept) is released: `drained` is declared behind them, so it goes first.
+    DevBuf<double> cand[2];
+    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drained{st};
     float us[3] = {0.f, 0.f, 0.f};
     int ncand = 1, keep = 0;
-    int status = time_on(cand[0], &us[0]);
-    for (int k = 1; k < 3 && status == QN_OK; ++k) {
+    QNCHK(time_on(s->H, &us[0]));
+    for (int k = 1; k < 3; ++k) {
         if (k == 2 && std::fabs(us[0] - us[1]) <= 0.06f * std::min(us[0], us[1])) break; // the two agree: both are the common case
-        if (hipMalloc((void**)&cand[k], bytes) != hipSuccess) { (void)hipGetLastError(); cand[k] = nullptr; break; } // (no room: keep what there is)
+        if (cand[k - 1].alloc((size_t)s->T.rpr * np) != QN_OK) break; // (no room: keep what there is -- never a reason to fail the run)
         ++ncand;
-        if (hipMemcpyAsync(cand[k], s->H, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) { status = fail(QN_ABNORMAL_TERMINATION, "H placement: copy failed"); break; }
-        status = time_on(cand[k], &us[k]);
+        if (hipMemcpyAsync(cand[k - 1], s->H, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(QN_ABNORMAL_TERMINATION, "H placement: copy failed");
+        QNCHK(time_on(cand[k - 1], &us[k]));
     }
-    if (status == QN_OK)
-        for (int k = 1; k < ncand; ++k)
-            if (us[k] < 0.96f * us[keep]) keep = k; // (the one it has, unless another is clearly better)
+    for (int k = 1; k < ncand; ++k)
+        if (us[k] < 0.96f * us[keep]) keep = k; // (the one it has, unless another is clearly better)
     if (sw && atoi(sw) == 2) fprintf(stderr, "[qn] H placement: %d candidates, update kernel %.2f %.2f %.2f us, kept %d\n", ncand, us[0], us[1], us[2], keep);
-    (void)hipStreamSynchronize(st);
-    for (int k = 0; k < ncand; ++k)
-        if (k != keep && cand[k]) (void)hipFree(cand[k]);
-    s->H = cand[keep];
-    s->V.H = s->H;
-    r.s2.H = s->H;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    if (pe) (void)hipHostFree(pe);
-    return status;
+    if (keep) {
+        (void)hipStreamSynchronize(st);
+        s->H = std::move(cand[keep - 1]); // (releases the H it had)
+        s->V.H = s->H;
+        r.s2.H = s->H;
+    }
+    return QN_OK;
 }
 
 static int launch_ctl_mask(Run& r, int expect_mask) {

@@ -104,13 +104,10 @@ static int plan_run(Run& r, qn_solver* s, qn_linesearch* ls, const qn_oracle* o,
     if (s->method == QN_BROYDEN && (r.fused || r.sym || r.sym_generic)) return fail(QN_ABNORMAL_TERMINATION, "Broyden on a symmetric-storage path");
     if ((r.sym || r.sym_generic) && c->world > 1) QNCHK(solver_alloc_symsh_lists(s));
     if (r.sym_generic) {
-        if (c->world > 1 && !s->symsh_xg) QNCHK(dev_alloc_zero(&s->symsh_xg, (size_t)c->world * 2 * s->T.n_pad, c->stream));
+        if (c->world > 1) QNCHK(s->symsh_xg.ensure((size_t)c->world * 2 * s->T.n_pad, c->stream));
         const int nb = s->T.n_pad / QN_TB;
-        if (s->sym_nb != nb) {
-            if (s->sym_part) { HIPCHK(hipFree(s->sym_part)); s->sym_part = nullptr; }
-            QNCHK(dev_alloc_zero(&s->sym_part, (size_t)nb * nb * 2 * QN_TB, c->stream));
-            s->sym_nb = nb;
-        }
+        QNCHK(s->sym_part.ensure((size_t)nb * nb * 2 * QN_TB, c->stream));
+        s->sym_nb = nb;
     }
     r.sym2 = r.sym && (s2_shape || s2sh_shape);
     h->sym2 = r.sym2 ? 1 : 0;
@@ -147,7 +144,7 @@ static int plan_run(Run& r, qn_solver* s, qn_linesearch* ls, const qn_oracle* o,
     if (r.fused) {
         QNCHK(solver_alloc_fused(s, r.sym));
         s->V.F.pworld = r.sym ? 1 : c->world; // symmetric storage: every rank forms all the per-block partial sums itself
-        if (r.sym && c->world > 1 && !s->symsh_xg) QNCHK(dev_alloc_zero(&s->symsh_xg, (size_t)c->world * 2 * s->T.n_pad, c->stream));
+        if (r.sym && c->world > 1) QNCHK(s->symsh_xg.ensure((size_t)c->world * 2 * s->T.n_pad, c->stream));
         s->V.F.b = r.gobj ? nullptr : r.obj->b; // (the quadratic's linear term; the log-sum-exp path's kernels do not read it)
         if (!s->fused_live) { // import the canonical state (x, pending s and u) into the fused buffers
             const size_t vb = (size_t)s->T.n_pad * sizeof(double);
@@ -201,9 +198,9 @@ static int plan_s2_args(Run& r) {
     a.gw = r.gobj ? s->T.n_pad / 64 : 0;
     a.gmu = r.gobj ? r.obj->mu : 0.0;
     // (allocated only for the runs that use them: the tail reduce's counters, the sharded log-sum-exp path's weights)
-    if (r.gobj && c->world > 1 && !s->s2_gws) QNCHK(dev_alloc_zero(&s->s2_gws, 80, c->stream)); // the ranks' weights and S, world <= 64
+    if (r.gobj && c->world > 1) QNCHK(s->s2_gws.ensure(80, c->stream)); // the ranks' weights and S, world <= 64
     a.gws = s->s2_gws;
-    if (r.gobj && !s->s2_wgV) QNCHK(dev_alloc_zero(&s->s2_wgV, (size_t)2 * s->s2_trows * QN_S2_ROW, c->stream));
+    if (r.gobj) QNCHK(s->s2_wgV.ensure((size_t)2 * s->s2_trows * QN_S2_ROW, c->stream));
     a.wgV = s->s2_wgV;
     if (r.gobj && a.gw > s->s2_trows) return fail(QN_ABNORMAL_TERMINATION, "sym2 (generic objective): more combine workgroups than table rows");
     // folded accept-reduce (s2_hpass_kernel): every workgroup holds at most three items, so the blocks whose slots it sums fit
@@ -241,10 +238,7 @@ static int plan_s2_args(Run& r) {
     a.cnt = s->s2_cnt;
     a.cnt_stride = getenv("QN_S2_CNT_STRIDE") ? std::max(1, std::min(QN_S2_CNT_STRIDE, atoi(getenv("QN_S2_CNT_STRIDE")))) : QN_S2_CNT_STRIDE; // (diagnostics)
     const bool want_tred = getenv("QN_S2_TRED") ? atoi(getenv("QN_S2_TRED")) != 0 : s->tred;
-    if (want_tred && !s->s2_cnt) {
-        HIPCHK(hipMalloc((void**)&s->s2_cnt, (size_t)a.nb * QN_S2_CNT_STRIDE * sizeof(int)));
-        HIPCHK(hipMemsetAsync(s->s2_cnt, 0, (size_t)a.nb * QN_S2_CNT_STRIDE * sizeof(int), c->stream));
-    }
+    if (want_tred) QNCHK(s->s2_cnt.ensure((size_t)a.nb * QN_S2_CNT_STRIDE, c->stream));
     a.cnt = s->s2_cnt;
     a.tred = (c->world == 1 && !a.fold && !r.gobj && !r.tiles1 && s->s2_maxk <= QN_S2_TRED_MAXK && want_tred && s->method != QN_SR1) ? 1 : 0;
     // TOUCH workgroups (qn_s2_touch): where the two small launches are s2_vec_kernel<false> / s2_hreduce_kernel<false> in front of the pair instance's

@@ -1,26 +1,32 @@
 // qn_host_newton.hip.h -- host side, part 6 of 7: Newton's direction (row f2): blocked Cholesky and pivoted LU drivers, triangular sweeps.
 #pragma once
 // ---- Newton direction (newton/mod.rs:26-49): Cholesky factorisation + four triangular solves, or the n <= 5 kernel ----
-static int newton_alloc(qn_solver* s) {
-    if (s->newton_w) return QN_OK;
+static int newton_alloc(qn_solver* s) { // the whole group or none of it: a failure half-way leaves nothing that the next call would take for complete
+    if (s->newton_perm) return QN_OK; // (allocated last: it exists only when the whole group does)
     size_t n64 = (s->n + QN_NB - 1) / QN_NB * QN_NB;
     s->newton_big = n64 > QN_TS; // 512-wide triangular blocks (inverses doubled up from the 64-wide ones)
     if (s->newton_big) n64 = (s->n + QN_TS - 1) / QN_TS * QN_TS;
     s->newton_n64 = n64;
     hipStream_t st = s->ctx->stream;
-    QNCHK(dev_alloc_zero(&s->newton_w, n64 * n64, st));
-    QNCHK(dev_alloc_zero(&s->newton_x, 2 * n64, st));
-    QNCHK(dev_alloc_zero(&s->newton_invl, n64 * QN_NB, st));
-    if (s->newton_big) { // inverse blocks of width 128, 256, 512, the transposed 512 ones, and the product scratch
-        QNCHK(dev_alloc_zero(&s->newton_inv2, n64 * (128 + 256 + 512 + 512 + 256), st));
+    auto group = [&]() -> int {
+        QNCHK(s->newton_w.alloc_zero(n64 * n64, st));
+        QNCHK(s->newton_x.alloc_zero(2 * n64, st));
+        QNCHK(s->newton_invl.alloc_zero(n64 * QN_NB, st));
+        // inverse blocks of width 128, 256, 512, the transposed 512 ones, and the product scratch
+        if (s->newton_big) QNCHK(s->newton_inv2.alloc_zero(n64 * (128 + 256 + 512 + 512 + 256), st));
+        QNCHK(s->newton_fail.alloc_zero(2, st));
+        QNCHK(s->newton_piv.alloc(n64));
+        QNCHK(s->newton_perm.alloc(n64));
+        return QN_OK;
+    };
+    const int status = group();
+    if (status != QN_OK) {
+        s->newton_w.reset(); s->newton_x.reset(); s->newton_invl.reset(); s->newton_inv2.reset();
+        s->newton_fail.reset(); s->newton_piv.reset(); s->newton_perm.reset();
     }
-    HIPCHK(hipMalloc((void**)&s->newton_fail, 2 * sizeof(int)));
-    HIPCHK(hipMemsetAsync(s->newton_fail, 0, 2 * sizeof(int), st));
-    HIPCHK(hipMalloc((void**)&s->newton_piv, n64 * sizeof(int)));
-    HIPCHK(hipMalloc((void**)&s->newton_perm, n64 * sizeof(int)));
+    s->V.nfail = s->newton_fail; // (set whenever the flag exists, null when it does not)
     s->newton_piv_host.resize(n64);
-    s->V.nfail = s->newton_fail;
-    return QN_OK;
+    return status;
 }
 
 static inline int rowdot_grid(int nrows) { return std::max(1, std::min(1024, nrows <= 4096 ? (nrows + 3) / 4 : (nrows + 15) / 16)); }
@@ -147,8 +153,8 @@ static int enqueue_newton_lu(qn_solver* s, const double* hsrc, size_t ld_src) {
     hipLaunchKernelGGL(newton_stage_kernel, dim3(2048), dim3(256), 0, st, W, ld, n, n64, hsrc, ld_src, 0); // both triangles
     uint64_t launches = 1;
     const size_t panel_doubles = (size_t)QN_NB * QN_LU_PT * QN_LU_RPT; // (two buffers: the look-ahead writes the next panel's while this one's is still read)
-    if (!s->newton_panel) HIPCHK(hipMalloc((void**)&s->newton_panel, 2 * panel_doubles * sizeof(double)));
-    if (!s->newton_sync) HIPCHK(hipMalloc((void**)&s->newton_sync, 128 * sizeof(int)));
+    QNCHK(s->newton_panel.ensure(2 * panel_doubles));
+    QNCHK(s->newton_sync.ensure(128));
     HIPCHK(hipMemsetAsync(s->newton_sync, 0, 128 * sizeof(int), st));
     // role A split over the workgroups of one XCD (qn_lu_split.hip.h): the parts' records, two panels' worth, all words the sentinel
     // (measured at n = 8192, ms per Newton iteration: every panel split 44.2 = no split 44.2 -- a split pivot step costs 2.6-3.2 us at any height, one
@@ -156,7 +162,7 @@ static int enqueue_newton_lu(qn_solver* s, const double* hsrc, size_t ld_src) {
     // 5184: 42.5.  The first ~16 panels gain nothing either way: there the previous panel's bulk update, not the chain, sets the period)
     const int lu_split_min = s->newton_lu_split_min; // panels of fewer rows: one workgroup (QN_OPT_LU_SPLIT_MIN_ROWS, default 4160)
     if (s->newton_lu_split > 1) {
-        if (!s->newton_rec) HIPCHK(hipMalloc((void**)&s->newton_rec, 2 * (size_t)QN_LUS_REC_WORDS * sizeof(unsigned long long)));
+        QNCHK(s->newton_rec.ensure(2 * (size_t)QN_LUS_REC_WORDS));
         HIPCHK(hipMemsetAsync(s->newton_rec, 0xff, 2 * (size_t)QN_LUS_REC_WORDS * sizeof(unsigned long long), st));
     }
     static const int lu_persist_on = getenv("QN_LU_PERSIST") ? atoi(getenv("QN_LU_PERSIST")) : 1;
@@ -382,7 +388,7 @@ static int newton_stage_hessian(qn_solver* s, const qn_oracle* o, qn_objective* 
     bool symmetric = true; // the Cholesky path reads the lower triangle only: it needs H == H' bit for bit
     if (obj) { hsrc = obj->Q; ld_src = (size_t)obj->T.n_pad; symmetric = obj->q_symmetric; }
     else {
-        if (!s->newton_hsrc) HIPCHK(hipMalloc((void**)&s->newton_hsrc, (size_t)n * n * sizeof(double)));
+        QNCHK(s->newton_hsrc.ensure((size_t)n * n));
         s->newton_hhost.resize((size_t)n * n * 2);
         HIPCHK(hipMemcpyAsync(s->hx, s->V.x, s->n * sizeof(double), hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));

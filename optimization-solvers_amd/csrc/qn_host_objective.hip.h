@@ -11,19 +11,19 @@ struct qn_objective {
     int kind = 0;
     size_t n = 0;
     QnTile T{};
-    double* Q = nullptr; // this rank's rows, [rpr][n_pad]
-    double* b = nullptr; // n_pad
+    DevBuf<double> Q; // this rank's rows, [rpr][n_pad]
+    DevBuf<double> b; // n_pad
     bool q_symmetric = true; // quadratic: Q == Q' bit for bit (checked at creation); the symmetric-storage evaluation needs it
     // scratch for qn_objective_eval
-    double *ex = nullptr, *eq = nullptr, *eg = nullptr, *ef = nullptr;
+    DevBuf<double> ex, eq, eg, ef;
     // log-sum-exp: A rows are in Q ([mrpr][n_pad]), c in b (m_pad)
     size_t m = 0;
     QnTile TA{}; // row partition of A (m rows)
     double mu = 0.0;
     int lse_rs = 1;
     int lse_two_pass = 0; // diagnostics (QN_LSE_TWO_PASS=1 in the environment at creation): the round-1 two-pass evaluation
-    double *lz = nullptr, *lw = nullptr, *lgpart = nullptr, *lgall = nullptr, *lscal = nullptr;
-    double *lwgms = nullptr, *lwgg = nullptr, *lms = nullptr; // one-pass evaluation: per-workgroup (m, S), G vectors; gathered per-rank (m, S)
+    DevBuf<double> lz, lw, lgpart, lgall, lscal;
+    DevBuf<double> lwgms, lwgg, lms; // one-pass evaluation: per-workgroup (m, S), G vectors; gathered per-rank (m, S)
     int lse_G = 0, lse_kch = 0;                                 // its grid and column chunks per thread (0: two-pass evaluation)
 };
 
@@ -37,8 +37,8 @@ static int objective_base(qn_context* ctx, size_t n, const double* b_host, qn_ob
     o->n = n;
     o->T = make_tile(n, ctx, 1);
     *out = o;
-    QNCHK(dev_alloc_zero(&o->Q, (size_t)o->T.rpr * o->T.n_pad, ctx->stream));
-    QNCHK(dev_alloc_zero(&o->b, o->T.n_pad, ctx->stream));
+    QNCHK(o->Q.alloc_zero((size_t)o->T.rpr * o->T.n_pad, ctx->stream));
+    QNCHK(o->b.alloc_zero(o->T.n_pad, ctx->stream));
     HIPCHK(hipMemcpyAsync(o->b, b_host, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return QN_OK;
@@ -67,13 +67,12 @@ extern "C" int qn_quadratic_create_synthetic(qn_context* ctx, size_t n, uint64_t
     if (!diag_host) return fail(QN_ERROR_INPUT_PARAMS, "diag is null");
     QNCHK(objective_base(ctx, n, b_host, out));
     qn_objective* o = *out;
-    double* diag = nullptr;
-    HIPCHK(hipMalloc((void**)&diag, n * sizeof(double)));
+    DevBuf<double> diag;
+    QNCHK(diag.alloc(n));
     HIPCHK(hipMemcpyAsync(diag, diag_host, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(synth_fill_kernel, dim3(2048), dim3(256), 0, ctx->stream, o->Q, o->T, seed, diag, 1.0 / (double)n);
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    HIPCHK(hipFree(diag));
     return QN_OK;
 }
 
@@ -89,8 +88,8 @@ extern "C" int qn_logsumexp_create(qn_context* ctx, size_t m, size_t n, const do
     o->TA = make_tile(m, ctx, 1); // rows of A are sharded
     const size_t np = o->T.n_pad, mp = o->TA.n_pad, mrpr = o->TA.rpr;
     hipStream_t st = ctx->stream;
-    QNCHK(dev_alloc_zero(&o->Q, mrpr * np, st));
-    QNCHK(dev_alloc_zero(&o->b, mp, st));
+    QNCHK(o->Q.alloc_zero(mrpr * np, st));
+    QNCHK(o->b.alloc_zero(mp, st));
     HIPCHK(hipMemcpyAsync(o->b, c_host, m * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCHK(hipStreamSynchronize(st)); // the zero-fill above must land before the (null-stream) 2-D upload below
     const size_t r0 = (size_t)o->TA.row_off;
@@ -99,20 +98,20 @@ extern "C" int qn_logsumexp_create(qn_context* ctx, size_t m, size_t n, const do
         HIPCHK(hipMemcpy2D(o->Q, np * sizeof(double), a_host + r0 * n, n * sizeof(double), n * sizeof(double), nr, hipMemcpyHostToDevice));
     }
     o->lse_rs = (int)std::max<size_t>(1, std::min<size_t>(64, mrpr / 64));
-    QNCHK(dev_alloc_zero(&o->lz, (size_t)ctx->world * 2 * mrpr, st));
-    QNCHK(dev_alloc_zero(&o->lw, mp, st));
-    QNCHK(dev_alloc_zero(&o->lgpart, (size_t)o->lse_rs * np, st));
-    QNCHK(dev_alloc_zero(&o->lgall, (size_t)ctx->world * np, st));
-    QNCHK(dev_alloc_zero(&o->lscal, 2, st));
+    QNCHK(o->lz.alloc_zero((size_t)ctx->world * 2 * mrpr, st));
+    QNCHK(o->lw.alloc_zero(mp, st));
+    QNCHK(o->lgpart.alloc_zero((size_t)o->lse_rs * np, st));
+    QNCHK(o->lgall.alloc_zero((size_t)ctx->world * np, st));
+    QNCHK(o->lscal.alloc_zero(2, st));
     o->lse_two_pass = getenv("QN_LSE_TWO_PASS") && atoi(getenv("QN_LSE_TWO_PASS")) != 0;
     if (np <= 16384 && np >= 2) { // the one-pass evaluation keeps a whole row per workgroup in registers
         int kch = 1;
         while ((size_t)kch * 1024 < np) kch *= 2;
         o->lse_kch = kch;
         o->lse_G = (int)std::max<size_t>(1, std::min<size_t>(256, (mrpr + 3) / 4));
-        QNCHK(dev_alloc_zero(&o->lwgms, 2 * (size_t)o->lse_G, st));
-        QNCHK(dev_alloc_zero(&o->lwgg, (size_t)o->lse_G * np, st));
-        QNCHK(dev_alloc_zero(&o->lms, 2 * (size_t)ctx->world, st));
+        QNCHK(o->lwgms.alloc_zero(2 * (size_t)o->lse_G, st));
+        QNCHK(o->lwgg.alloc_zero((size_t)o->lse_G * np, st));
+        QNCHK(o->lms.alloc_zero(2 * (size_t)ctx->world, st));
     }
     HIPCHK(hipStreamSynchronize(st));
     return QN_OK;
@@ -202,10 +201,6 @@ static int lse_enqueue_eval(qn_objective* o, const double* x_dev, double* f_dev,
 extern "C" void qn_objective_destroy(qn_objective* o) {
     if (!o) return;
     (void)hipSetDevice(o->ctx->device);
-    (void)hipFree(o->Q); (void)hipFree(o->b);
-    (void)hipFree(o->ex); (void)hipFree(o->eq); (void)hipFree(o->eg); (void)hipFree(o->ef);
-    (void)hipFree(o->lz); (void)hipFree(o->lw); (void)hipFree(o->lgpart); (void)hipFree(o->lgall); (void)hipFree(o->lscal);
-    (void)hipFree(o->lwgms); (void)hipFree(o->lwgg); (void)hipFree(o->lms);
     delete o;
 }
 
@@ -253,11 +248,9 @@ extern "C" int qn_objective_eval(qn_objective* o, const double* x_host, double* 
     HIPCHK(hipSetDevice(c->device));
     const size_t np = o->T.n_pad;
     if (o->kind == OBJ_LOGSUMEXP) {
-        if (!o->ex) {
-            QNCHK(dev_alloc_zero(&o->ex, 2 * np, c->stream));
-            QNCHK(dev_alloc_zero(&o->eg, np, c->stream));
-            QNCHK(dev_alloc_zero(&o->ef, 2, c->stream));
-        }
+        QNCHK(o->ex.ensure(2 * np, c->stream));
+        QNCHK(o->eg.ensure(np, c->stream));
+        QNCHK(o->ef.ensure(2, c->stream));
         HIPCHK(hipMemcpyAsync(o->ex, x_host, o->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
         QNCHK(lse_enqueue_eval(o, o->ex, o->ef, o->eg));
         HIPCHK(hipMemcpyAsync(f, o->ef, sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -266,12 +259,10 @@ extern "C" int qn_objective_eval(qn_objective* o, const double* x_host, double* 
         return QN_OK;
     }
     if (o->kind != OBJ_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
-    if (!o->ex) {
-        QNCHK(dev_alloc_zero(&o->ex, 2 * np, c->stream)); // x and xt
-        QNCHK(dev_alloc_zero(&o->eq, np, c->stream));
-        QNCHK(dev_alloc_zero(&o->eg, np, c->stream));
-        QNCHK(dev_alloc_zero(&o->ef, 2, c->stream));
-    }
+    QNCHK(o->ex.ensure(2 * np, c->stream)); // x and xt
+    QNCHK(o->eq.ensure(np, c->stream));
+    QNCHK(o->eg.ensure(np, c->stream));
+    QNCHK(o->ef.ensure(2, c->stream));
     HIPCHK(hipMemcpyAsync(o->ex, x_host, o->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     QnQuadArgs a{};
     a.Q = o->Q; a.T = o->T; a.x = o->ex; a.d = o->ex; a.xt = o->ex + np;

@@ -6,9 +6,7 @@
 
 static int r1_alloc(qn_solver* s) {
     const int nb = (s->T.n_pad + QN_R1_TB - 1) / QN_R1_TB;
-    if (s->r1_part && s->r1_nb == nb) return QN_OK;
-    if (s->r1_part) { HIPCHK(hipFree(s->r1_part)); s->r1_part = nullptr; }
-    QNCHK(dev_alloc_zero(&s->r1_part, (size_t)3 * nb * s->T.n_pad, s->ctx->stream)); // row partials [2][nb][n_pad], column partials [nb][n_pad]
+    QNCHK(s->r1_part.ensure((size_t)3 * nb * s->T.n_pad, s->ctx->stream)); // row partials [2][nb][n_pad], column partials [nb][n_pad]
     s->r1_nb = nb;
     return QN_OK;
 }

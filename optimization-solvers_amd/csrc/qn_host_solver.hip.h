@@ -15,24 +15,25 @@ struct qn_solver {
     double tol = 0.0;
     QnTile T{};
     int R = 4, U = 1, hcs = 1, qcs = 1; // row tile, chunks per trip (fused kernels), column splits
-    double* H = nullptr;
-    double* vec_block = nullptr; // one allocation holding all n_pad vectors
-    QnVecs V{};
-    double* f_dev = nullptr;
+    DevBuf<double> H;
+    DevBuf<double> vec_block; // one allocation holding all n_pad vectors
+    QnVecs V{}; // what the kernels see: plain pointers, views of the owners in this struct
+    DevBuf<double> hp, q, xtrace; DevBuf<QnTraceRec> trace; DevBuf<unsigned long long> dbg; // V.hp, V.q (solver_alloc_hp), V.xtrace, V.trace (qn_solver_set_trace), V.dbg (diagnostic builds)
+    DevBuf<double> f_dev;
     // Newton: Hessian work matrix (row-major, ld = nw), right-hand sides, staging for host Hessians, failure flag
-    double *newton_w = nullptr, *newton_x = nullptr, *newton_hsrc = nullptr, *newton_invl = nullptr, *newton_inv2 = nullptr;
+    DevBuf<double> newton_w, newton_x, newton_hsrc, newton_invl, newton_inv2;
     bool newton_big = false;
     // symmetric-storage fast path (qn_sym.hip.h): slot buffer, tile count per side, opt-out, "user installed a non-symmetric H"
-    double* sym_part = nullptr;
+    DevBuf<double> sym_part;
     int sym_nb = 0;
-    double* r1_part = nullptr; // QN_BROYDEN (qn_rank1.hip.h): the tiles' row and column partials, [3][r1_nb][n_pad]
+    DevBuf<double> r1_part; // QN_BROYDEN (qn_rank1.hip.h): the tiles' row and column partials, [3][r1_nb][n_pad]
     int r1_nb = 0;
     bool no_sym = false, h_nonsym = false;
     bool h_lower_stale = false; // a symmetric-storage run is (or was) updating the upper block triangle only
-    double *symsh_xg = nullptr, *symsh_gath = nullptr; // row-sharded symmetric storage: gathered partial sums [world][2][n_pad]; mirror staging
+    DevBuf<double> symsh_xg, symsh_gath; // row-sharded symmetric storage: gathered partial sums [world][2][n_pad]; mirror staging
     bool h_diag_stale = false;  // ... and (second-generation kernels) only the upper triangle of 16 x 16 sub-blocks inside the diagonal tiles
     // second-generation symmetric path (qn_sym2.hip.h): static work lists, per-workgroup scalars, double-buffered control block
-    int* s2_items = nullptr;
+    DevBuf<int> s2_items;
     int s2_G = 0, s2_nb = 0, s2_maxk = 0, s2_inorder = 0;
     int s2_sl_first = 0, s2_sl_per = 0, s2_sl_cfg = -1; // row slivers (QnS2Args.sl_first / sl_per); the switches the lists were built for
     bool no_sliver = false;    // diagnostics: sym2 without row slivers (round 2's work lists)
@@ -44,26 +45,26 @@ struct qn_solver {
     int touch_delay = getenv("QN_S2_TOUCH_DELAY") ? atoi(getenv("QN_S2_TOUCH_DELAY")) : 32; // ... units of 64 clocks the accept-reduce's touching workgroups sleep first
     int touchq_delay = getenv("QN_S2_TOUCHQ_DELAY") ? atoi(getenv("QN_S2_TOUCHQ_DELAY")) : 0; // ... and the update-reduce's
     bool tred = false;         // measurement: the update-reduce in the tail of the update-tile launch (s2_hpass_kernel<.., TRED>: bit-identical, slower)
-    int* s2_cnt = nullptr;     // tail reduce: arrival counters of the block-rows
+    DevBuf<int> s2_cnt;        // tail reduce: arrival counters of the block-rows
     int gen_slots_hint = 0;    // generic pipelined path: evaluation slots per period the last batch needed (0: none run yet)
-    double* s2_gws = nullptr;  // row-sharded log-sum-exp (qn_sym2g.hip.h): the ranks' weights and S of the last evaluation consumed
-    double* s2_wgV = nullptr;  // generic objectives: the second table of per-workgroup sums (QnS2Args.wgV)
+    DevBuf<double> s2_gws;     // row-sharded log-sum-exp (qn_sym2g.hip.h): the ranks' weights and S of the last evaluation consumed
+    DevBuf<double> s2_wgV;     // generic objectives: the second table of per-workgroup sums (QnS2Args.wgV)
     hipGraphExec_t s2_graph_exec = nullptr; // measurement (QN_S2_GRAPH): two periods of the pipelined pattern as one graph, and what it was captured for
     QnS2Args s2_graph_args{}; int s2_graph_slots = 0, s2_graph_bnd = 0; uint64_t s2_graph_len = 0, s2_graph_stat = 0;
     int last_ls_kind = -1; std::vector<double> last_ls_box; bool ls_box_changed = false; // the line search (kind, box) of the last qn_minimize call: see plan_run
     double mtb_cand_keep = INFINITY; // bounded second-generation runs: the step to the box of the direction a warm call continues with
     bool no_s2bnd = false;     // tests: bounded runs keep the generic path (QN_OPT_BOUNDED_SECOND_GENERATION 0)
     bool h_sliver_whole = false; // the diagonal tiles that sliver rows read are complete (both triangles): kept so by sliver-mode update passes
-    double* s2_evS = nullptr;   // row-sharded: [2][world][QN_S2SH_NEC][QN_S2_MAXG] the ranks' evaluation scalars, by launch parity (QnS2Args.evS)
-    int *s2_sl_off = nullptr, *s2_sl_idx = nullptr; // row-sharded: per block-row, the slots this rank's tiles write (QnS2Args.sl_off / sl_idx)
+    DevBuf<double> s2_evS;      // row-sharded: [2][world][QN_S2SH_NEC][QN_S2_MAXG] the ranks' evaluation scalars, by launch parity (QnS2Args.evS)
+    DevBuf<int> s2_sl_off, s2_sl_idx; // row-sharded: per block-row, the slots this rank's tiles write (QnS2Args.sl_off / sl_idx)
     int s2_sl_nb = 0;
     bool h_placed = false;      // H's placement has been measured (place_h)
-    int* symsh_tiles = nullptr; // row-sharded, first-generation kernels: this rank's tiles in launch order (QnSymShard.tiles)
+    DevBuf<int> symsh_tiles;    // row-sharded, first-generation kernels: this rank's tiles in launch order (QnSymShard.tiles)
     int s2_slots_hint = 0;      // row-sharded, pipelined: evaluation launches (each followed by a collective) enqueued per period
-    double* s2_partE = nullptr; // [nb][nb][128]: row / column slots of the last evaluation (QnS2Args.partE)
-    double* s2_wgS = nullptr; // [2][s2_trows][QN_S2_ROW]: the sums a servicing launch leaves for the next launch's prologue, by launch parity
+    DevBuf<double> s2_partE;    // [nb][nb][128]: row / column slots of the last evaluation (QnS2Args.partE)
+    DevBuf<double> s2_wgS; // [2][s2_trows][QN_S2_ROW]: the sums a servicing launch leaves for the next launch's prologue, by launch parity
     int s2_trows = 0;
-    QnCtl* s2_ctl = nullptr;
+    DevBuf<QnCtl> s2_ctl;
     bool no_sym2 = false; // diagnostics: the first-generation tile kernels (qn_sym.hip.h)
     bool fold = false; // sym2 with the accept-reduce folded into the update-tile launch (four launches per iteration instead of five).
                        // OFF by default -- measured, rocprofv3 averages, n = 4096, same box: the accept-reduce launch (6.7 us) goes, the
@@ -77,16 +78,16 @@ struct qn_solver {
     // nothing has touched the state since.  A serial, not the pointer: destroy A, create B of the same size and the allocator
     // hands the address back -- the run on B would have inherited f, g and the lazy direction of A.
     uint64_t warm_obj = 0;
-    int* newton_fail = nullptr; // [0]: the factorisation met a bad pivot, [1]: the staged Hessian is not symmetric bit for bit
-    int *newton_piv = nullptr, *newton_perm = nullptr; // LU fallback (qn_lu.hip.h): pivot rows, row permutation
-    double* newton_panel = nullptr; // ... and the column-major copy of the 64-column panel being factorised
+    DevBuf<int> newton_fail; // (V.nfail) [0]: the factorisation met a bad pivot, [1]: the staged Hessian is not symmetric bit for bit
+    DevBuf<int> newton_piv, newton_perm; // LU fallback (qn_lu.hip.h): pivot rows, row permutation
+    DevBuf<double> newton_panel; // ... and the column-major copy of the 64-column panel being factorised
     bool newton_lu_percol = false;  // diagnostics: the panel factorisation with two launches per column (rounds 1-2)
     std::vector<int> newton_piv_host;
     uint64_t newton_lu_runs = 0, newton_chol_runs = 0;
     int newton_lu_force_timeout = 0; // diagnostics (QN_OPT_LU_FORCE_WAIT_EXPIRY): the one-launch kernels' waits give up at once (exercises the fallback)
     int newton_lu_no_persist = 0; // diagnostics (QN_OPT_LU_ONE_LAUNCH_PANEL 0), or set after a bounded wait of the one-launch panel gave up: one launch per sub-panel
-    int* newton_sync = nullptr;   // the one-launch panel's counters (qn_lu.hip.h, lu_panel_persist_kernel)
-    unsigned long long* newton_rec = nullptr; // ... and, with role A split over workgroups, the parts' records (qn_lu_split.hip.h)
+    DevBuf<int> newton_sync;      // the one-launch panel's counters (qn_lu.hip.h, lu_panel_persist_kernel)
+    DevBuf<unsigned long long> newton_rec; // ... and, with role A split over workgroups, the parts' records (qn_lu_split.hip.h)
     bool no_projfold = getenv("QN_S2_PROJ_FOLD") && atoi(getenv("QN_S2_PROJ_FOLD")) == 0; // QN_OPT_BTB_PROJECT_IN_EVAL 0: BackTrackingB's projection as a launch per trial
     int newton_lu_split = getenv("QN_LU_SPLIT") ? atoi(getenv("QN_LU_SPLIT")) : 4; // parts of role A: 1 (one workgroup, rounds 4-5), 2 or 4 (QN_OPT_LU_SPLIT_ROLE_A)
     int newton_lu_split_min = getenv("QN_LU_SPLIT_MIN") ? atoi(getenv("QN_LU_SPLIT_MIN")) : 4160; // ... for panels of at least this many rows (QN_OPT_LU_SPLIT_MIN_ROWS)
@@ -96,24 +97,25 @@ struct qn_solver {
     int newton_force_lu = 0; // diagnostics (QN_OPT_NEWTON_PIVOTED_LU): skip the Cholesky attempt
     size_t newton_n64 = 0;
     std::vector<double> newton_hhost;
-    QnVecCtl *vctl = nullptr, *hvctl = nullptr; // QN_SPG / QN_PROJECTED_GRADIENT: device control block, pinned host copy (lambda, GLL history, memo)
-    double* vpart = nullptr;                    // ... and the per-workgroup partials of their vector kernels
+    DevBuf<QnVecCtl> vctl; PinnedBuf<QnVecCtl> hvctl; // QN_SPG / QN_PROJECTED_GRADIENT: device control block, pinned host copy (lambda, GLL history, memo)
+    DevBuf<double> vpart;                       // ... and the per-workgroup partials of their vector kernels
     // QN_PROJECTED_NEWTON / QN_SPECTRAL_PROJECTED_NEWTON: the factor in newton_w belongs to the device objective with this serial (0: to none);
     // QN_OPT_PNEWTON_REUSE_FACTOR; Cholesky factorisations enqueued by the last qn_minimize
     uint64_t pn_factor_serial = 0;
     int pn_reuse = 1;
     uint64_t pn_factorisations = 0;
-    double* bounds_block = nullptr; // lb, ub (solver), llb, lub (bounded line search): 4 n_pad vectors
+    DevBuf<double> bounds_block; // lb, ub (solver), llb, lub (bounded line search): 4 n_pad vectors
     int bounded = 0;
-    double* fused_block = nullptr; // X0[2], S0[2], G, GT, Y, UN, UP, VV (10 n_pad vectors)
-    double *fused_evp = nullptr, *fused_hpp = nullptr;
+    DevBuf<double> fused_block; // X0[2], S0[2], G, GT, Y, UN, UP, VV (10 n_pad vectors)
+    DevBuf<double> fused_evp, fused_hpp;
     int fused_nblk = 0;
-    QnCtl* ctl = nullptr;  // device
+    DevBuf<QnCtl> ctl;     // device
+    PinnedBuf<unsigned char> hctl_block; // pinned, device-mapped: [hctl | hrep | hrep_flag (64 bytes)]
     QnCtl* hctl = nullptr; // pinned host mirror
     QnCtl* hrep = nullptr; // pinned: the control block as the last launch of a sym2 batch left it (written by the device)
     unsigned long long* hrep_flag = nullptr;
     unsigned long long rep_seq = 0;
-    double *hx = nullptr, *hg = nullptr; // pinned staging for host oracles
+    PinnedBuf<double> hx, hg; // pinned staging for host oracles
     size_t trace_cap = 0;
     int trace_x = 0;
     int sync_mode = -1; // -1 auto
@@ -188,20 +190,15 @@ static void prof_collect(qn_solver* s) {
 static int solver_alloc_fused(qn_solver* s, bool sym) {
     const size_t np = s->T.n_pad;
     hipStream_t st = s->ctx->stream;
-    if (!s->fused_block) QNCHK(dev_alloc_zero(&s->fused_block, 10 * np, st));
+    QNCHK(s->fused_block.ensure(10 * np, st));
     const int nblk = sym ? (int)(np / QN_TB) : s->T.rpr / s->R; // partial-sum rows: 128-row blocks or R-row workgroups
-    if (sym && s->sym_nb != nblk) {
-        if (s->sym_part) { HIPCHK(hipFree(s->sym_part)); s->sym_part = nullptr; }
-        QNCHK(dev_alloc_zero(&s->sym_part, (size_t)nblk * nblk * 2 * QN_TB, st));
+    if (sym) {
+        QNCHK(s->sym_part.ensure((size_t)nblk * nblk * 2 * QN_TB, st));
         s->sym_nb = nblk;
     }
-    if (nblk != s->fused_nblk) {
-        if (s->fused_evp) { HIPCHK(hipFree(s->fused_evp)); s->fused_evp = nullptr; }
-        if (s->fused_hpp) { HIPCHK(hipFree(s->fused_hpp)); s->fused_hpp = nullptr; }
-        QNCHK(dev_alloc_zero(&s->fused_evp, (size_t)s->ctx->world * QN_NEVP * nblk, st));
-        QNCHK(dev_alloc_zero(&s->fused_hpp, (size_t)s->ctx->world * QN_NHPP * nblk, st));
-        s->fused_nblk = nblk;
-    }
+    QNCHK(s->fused_evp.ensure((size_t)s->ctx->world * QN_NEVP * nblk, st));
+    QNCHK(s->fused_hpp.ensure((size_t)s->ctx->world * QN_NHPP * nblk, st));
+    s->fused_nblk = nblk;
     double* p = s->fused_block;
     QnFused& F = s->V.F;
     F.X0 = p; F.S0 = p + 2 * np; F.G = p + 4 * np; F.GT = p + 5 * np; F.Y = p + 6 * np;
@@ -217,15 +214,13 @@ static int solver_alloc_fused(qn_solver* s, bool sym) {
 static int solver_alloc_symsh_lists(qn_solver* s) {
     const int nb = s->T.n_pad / QN_TB;
     if (s->s2_sl_off && s->s2_sl_nb == nb) return QN_OK;
-    (void)hipFree(s->s2_sl_off); (void)hipFree(s->s2_sl_idx); (void)hipFree(s->symsh_tiles);
-    s->s2_sl_off = nullptr; s->s2_sl_idx = nullptr; s->symsh_tiles = nullptr;
     const int nbl = s->T.rpr / QN_TB, ioff = s->ctx->rank * nbl;
     {
         std::vector<int> tiles;
         for (int il = 0; il < nbl; ++il)
             for (int k = 0, I = ioff + il; k < qn_symsh_cnt(I, nb); ++k) tiles.push_back((I << 16) | ((I + k) % nb));
         if (tiles.empty()) tiles.push_back(0);
-        HIPCHK(hipMalloc((void**)&s->symsh_tiles, tiles.size() * sizeof(int)));
+        QNCHK(s->symsh_tiles.alloc(tiles.size()));
         HIPCHK(hipMemcpy(s->symsh_tiles, tiles.data(), tiles.size() * sizeof(int), hipMemcpyHostToDevice));
     }
     std::vector<int> off(nb + 1, 0), idx;
@@ -238,8 +233,8 @@ static int solver_alloc_symsh_lists(qn_solver* s) {
         off[R + 1] = (int)idx.size();
     }
     if (idx.empty()) idx.push_back(0);
-    HIPCHK(hipMalloc((void**)&s->s2_sl_off, off.size() * sizeof(int)));
-    HIPCHK(hipMalloc((void**)&s->s2_sl_idx, idx.size() * sizeof(int)));
+    QNCHK(s->s2_sl_off.alloc(off.size()));
+    QNCHK(s->s2_sl_idx.alloc(idx.size()));
     HIPCHK(hipMemcpy(s->s2_sl_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(s->s2_sl_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
     s->s2_sl_nb = nb;
@@ -257,11 +252,9 @@ static int solver_alloc_sym2(qn_solver* s) {
     const bool sharded = world > 1;
     const int cfg = (s->fold ? 1 : 0) | (s->no_sliver ? 2 : 0) | (sharded ? 4 : 0);
     if (s->s2_nb != nb || s->s2_sl_cfg != cfg) {
-        (void)hipFree(s->s2_items); (void)hipFree(s->s2_wgS); (void)hipFree(s->s2_partE);
+        s->s2_items.reset(); s->s2_wgS.reset(); s->s2_partE.reset(); s->s2_evS.reset(); s->s2_cnt.reset();
+        s->s2_wgV.reset(); // (the generic objectives' second table: allocated by the runs that use it)
         if (s->s2_graph_exec) { (void)hipGraphExecDestroy(s->s2_graph_exec); s->s2_graph_exec = nullptr; } // (the pointer dangled -- a matching memcmp launched it again)
-    (void)hipFree(s->s2_evS); (void)hipFree(s->s2_cnt);
-        s->s2_items = nullptr; s->s2_wgS = nullptr; s->s2_partE = nullptr;
-        s->s2_evS = nullptr; s->s2_cnt = nullptr;
         s->s2_nb = 0;
         const int nbl = s->T.rpr / QN_TB, ioff = rank * nbl; // (sharded: this rank's block-rows)
         int nitems = nb * (nb + 1) / 2;
@@ -346,25 +339,18 @@ static int solver_alloc_sym2(qn_solver* s) {
         std::vector<int> items(maxk * (size_t)G, -1); // [k][g]: the workgroup's k-th item; -1 ends its list
         for (int g = 0; g < G; ++g)
             for (size_t k = 0; k < lists[g].size(); ++k) items[k * (size_t)G + g] = lists[g][k];
-        HIPCHK(hipMalloc((void**)&s->s2_items, items.size() * sizeof(int)));
+        QNCHK(s->s2_items.alloc(items.size()));
         HIPCHK(hipMemcpy(s->s2_items, items.data(), items.size() * sizeof(int), hipMemcpyHostToDevice));
         s->s2_maxk = (int)maxk;
         s->s2_inorder = inorder;
         s->s2_trows = std::max(QN_S2_MAXG, (nb + 63) / 64 * 64);
-        QNCHK(dev_alloc_zero(&s->s2_wgS, (size_t)2 * s->s2_trows * QN_S2_ROW, st));
-        (void)hipFree(s->s2_wgV); s->s2_wgV = nullptr; // (the generic objectives' second table: allocated by the runs that use it)
-        QNCHK(dev_alloc_zero(&s->s2_partE, (size_t)nb * nb * QN_TB, st));
-        if (sharded) {
-            QNCHK(dev_alloc_zero(&s->s2_evS, (size_t)2 * world * QN_S2SH_NEC * QN_S2_MAXG, st));
-        }
-
+        QNCHK(s->s2_wgS.alloc_zero((size_t)2 * s->s2_trows * QN_S2_ROW, st));
+        QNCHK(s->s2_partE.alloc_zero((size_t)nb * nb * QN_TB, st));
+        if (sharded) QNCHK(s->s2_evS.alloc_zero((size_t)2 * world * QN_S2SH_NEC * QN_S2_MAXG, st));
         s->s2_G = G;
         s->s2_nb = nb;
     }
-    if (!s->s2_ctl) {
-        HIPCHK(hipMalloc((void**)&s->s2_ctl, 2 * sizeof(QnCtl)));
-        HIPCHK(hipMemsetAsync(s->s2_ctl, 0, 2 * sizeof(QnCtl), st));
-    }
+    QNCHK(s->s2_ctl.ensure(2, st));
     return QN_OK;
 }
 
@@ -377,10 +363,10 @@ static int r1_flush(qn_solver* s); // QN_BROYDEN: qn_host_rank1.hip.h
 static int r1_secant_update(qn_solver* s, const double* s_host, const double* y_host, double ys);
 
 static int solver_alloc_hp(qn_solver* s) {
-    if (s->V.hp) { HIPCHK(hipFree(s->V.hp)); s->V.hp = nullptr; }
-    if (s->V.q) { HIPCHK(hipFree(s->V.q)); s->V.q = nullptr; }
-    QNCHK(dev_alloc_zero(&s->V.hp, (size_t)s->ctx->world * s->hcs * 2 * s->T.rpr, s->ctx->stream));
-    QNCHK(dev_alloc_zero(&s->V.q, (size_t)s->ctx->world * s->qcs * s->T.rpr, s->ctx->stream));
+    s->V.hp = s->V.q = nullptr; s->hp.reset(); s->q.reset();
+    QNCHK(s->hp.alloc_zero((size_t)s->ctx->world * s->hcs * 2 * s->T.rpr, s->ctx->stream));
+    QNCHK(s->q.alloc_zero((size_t)s->ctx->world * s->qcs * s->T.rpr, s->ctx->stream));
+    s->V.hp = s->hp; s->V.q = s->q;
     s->V.hcs = s->hcs;
     s->V.qcs = s->qcs;
     return QN_OK;
@@ -405,29 +391,28 @@ extern "C" int qn_solver_create(qn_context* ctx, int method, double tol, const d
     const size_t np = s->T.n_pad;
     hipStream_t st = ctx->stream;
     if (method == QN_BFGS || method == QN_DFP || method == QN_SR1 || method == QN_BROYDEN) {
-        QNCHK(dev_alloc_zero(&s->H, (size_t)s->T.rpr * np, st));
+        QNCHK(s->H.alloc_zero((size_t)s->T.rpr * np, st));
         hipLaunchKernelGGL(identity_fill_kernel, dim3(2048), dim3(256), 0, st, s->H, s->T); // bfgs.rs:27-39: H = I
         HIPCHK(hipGetLastError());
     }
-    QNCHK(dev_alloc_zero(&s->vec_block, 9 * np, st));
+    QNCHK(s->vec_block.alloc_zero(9 * np, st));
     double* p = s->vec_block;
     s->V.x = p; s->V.g = p + np; s->V.d = p + 2 * np; s->V.xt = p + 3 * np; s->V.gt = p + 4 * np;
     s->V.s = p + 5 * np; s->V.y = p + 6 * np; s->V.sp = p + 7 * np; s->V.up = p + 8 * np;
     s->V.n = (int)n; s->V.n_pad = (int)np; s->V.rpr = s->T.rpr; s->V.world = ctx->world;
     s->V.H = s->H;
     QNCHK(solver_alloc_hp(s));
-    QNCHK(dev_alloc_zero(&s->f_dev, 2, st));
+    QNCHK(s->f_dev.alloc_zero(2, st));
     s->V.f_dev = s->f_dev;
-    HIPCHK(hipMalloc((void**)&s->ctl, sizeof(QnCtl)));
-    HIPCHK(hipMemsetAsync(s->ctl, 0, sizeof(QnCtl), st));
+    QNCHK(s->ctl.alloc_zero(1, st));
     // (mapped + coherent, explicitly: s2_ctl_upload_kernel reads the mirror from the device, call after call -- with a non-coherent
     // mapping the second call could be served a stale line from L2)
-    HIPCHK(hipHostMalloc((void**)&s->hctl, 2 * sizeof(QnCtl) + 64, hipHostMallocMapped | hipHostMallocCoherent));
-    memset(s->hctl, 0, 2 * sizeof(QnCtl) + 64);
+    QNCHK(s->hctl_block.alloc_zero(2 * sizeof(QnCtl) + 64, hipHostMallocMapped | hipHostMallocCoherent));
+    s->hctl = reinterpret_cast<QnCtl*>(s->hctl_block.get());
     s->hrep = s->hctl + 1;                                                    // what a batch's last launch reports (QnS2Args.rep)
     s->hrep_flag = reinterpret_cast<unsigned long long*>(s->hctl + 2);        // ... and the sequence number it stores behind it
-    HIPCHK(hipHostMalloc((void**)&s->hx, n * sizeof(double), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void**)&s->hg, (n + 1) * sizeof(double), hipHostMallocDefault));
+    QNCHK(s->hx.alloc(n));
+    QNCHK(s->hg.alloc(n + 1));
     HIPCHK(hipMemcpyAsync(s->V.x, x0_host, n * sizeof(double), hipMemcpyHostToDevice, st));
     if (vec_method(method)) QNCHK(vec_state_alloc(s)); // O(n): no H, no n x n scratch
     HIPCHK(hipStreamSynchronize(st));
@@ -441,29 +426,20 @@ extern "C" void qn_solver_destroy(qn_solver* s) {
     for (auto& e : s->events) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto& e : s->event_pool) (void)hipEventDestroy(e);
     if (s->s2_graph_exec) (void)hipGraphExecDestroy(s->s2_graph_exec);
-    (void)hipFree(s->H); (void)hipFree(s->vec_block); (void)hipFree(s->V.hp); (void)hipFree(s->V.q);
-    (void)hipFree(s->newton_w); (void)hipFree(s->newton_x); (void)hipFree(s->newton_invl); (void)hipFree(s->newton_inv2); (void)hipFree(s->sym_part); (void)hipFree(s->r1_part); (void)hipFree(s->symsh_xg); (void)hipFree(s->symsh_gath); (void)hipFree(s->newton_hsrc); (void)hipFree(s->newton_fail); (void)hipFree(s->newton_piv); (void)hipFree(s->newton_perm); (void)hipFree(s->newton_panel); (void)hipFree(s->newton_sync); (void)hipFree(s->newton_rec);
-    (void)hipFree(s->bounds_block);
-    (void)hipFree(s->vctl); (void)hipFree(s->vpart); (void)hipHostFree(s->hvctl);
-    (void)hipFree(s->fused_block); (void)hipFree(s->fused_evp); (void)hipFree(s->fused_hpp);
-    (void)hipFree(s->s2_items); (void)hipFree(s->s2_wgS); (void)hipFree(s->s2_partE); (void)hipFree(s->s2_ctl);
-    (void)hipFree(s->s2_evS); (void)hipFree(s->s2_cnt); (void)hipFree(s->s2_gws); (void)hipFree(s->s2_wgV); (void)hipFree(s->s2_sl_off); (void)hipFree(s->s2_sl_idx); (void)hipFree(s->symsh_tiles);
-    (void)hipFree(s->f_dev); (void)hipFree(s->ctl); (void)hipFree(s->V.trace); (void)hipFree(s->V.xtrace);
-    (void)hipHostFree(s->hctl); (void)hipHostFree(s->hx); (void)hipHostFree(s->hg);
     delete s;
 }
 
 extern "C" int qn_solver_set_trace(qn_solver* s, size_t cap, int with_x) {
     HIPCHK(hipSetDevice(s->ctx->device));
-    if (s->V.trace) { HIPCHK(hipFree(s->V.trace)); s->V.trace = nullptr; }
-    if (s->V.xtrace) { HIPCHK(hipFree(s->V.xtrace)); s->V.xtrace = nullptr; }
+    s->V.trace = nullptr; s->V.xtrace = nullptr; s->trace.reset(); s->xtrace.reset();
     s->trace_cap = cap;
     s->trace_x = with_x && cap;
     if (cap) {
-        HIPCHK(hipMalloc((void**)&s->V.trace, cap * sizeof(QnTraceRec)));
-        HIPCHK(hipMemset(s->V.trace, 0, cap * sizeof(QnTraceRec)));
-        if (with_x) QNCHK(dev_alloc_zero(&s->V.xtrace, cap * s->n, s->ctx->stream));
+        QNCHK(s->trace.alloc(cap));
+        HIPCHK(hipMemset(s->trace, 0, cap * sizeof(QnTraceRec)));
+        if (with_x) QNCHK(s->xtrace.alloc_zero(cap * s->n, s->ctx->stream));
     }
+    s->V.trace = s->trace; s->V.xtrace = s->xtrace;
     return QN_OK;
 }
 
@@ -480,9 +456,10 @@ extern "C" int qn_solver_get_trace(qn_solver* s, qn_trace_rec* out_host, size_t 
 #if defined(QN_CTL_STAMPS) || defined(QN_S2_STAMPS)
 extern "C" int qn_debug_stamps(qn_solver* s, unsigned long long* out, size_t count) { // diagnostic build only
     HIPCHK(hipSetDevice(s->ctx->device));
-    if (!s->V.dbg) {
-        HIPCHK(hipMalloc((void**)&s->V.dbg, (1 << 20) * 8));
-        HIPCHK(hipMemset(s->V.dbg, 0, (1 << 20) * 8));
+    if (!s->dbg) {
+        QNCHK(s->dbg.alloc(1 << 20));
+        HIPCHK(hipMemset(s->dbg, 0, (1 << 20) * 8));
+        s->V.dbg = s->dbg;
         return QN_OK;
     }
     HIPCHK(hipStreamSynchronize(s->ctx->stream));
@@ -603,7 +580,7 @@ static int peek_ctl(qn_solver* s) { // device -> host mirror
 static int bounds_alloc(qn_solver* s) {
     if (s->bounds_block) return QN_OK;
     const size_t np = s->T.n_pad;
-    HIPCHK(hipMalloc((void**)&s->bounds_block, 4 * np * sizeof(double)));
+    QNCHK(s->bounds_block.alloc(4 * np));
     std::vector<double> init(4 * np);
     for (size_t i = 0; i < np; ++i) { init[i] = -INFINITY; init[np + i] = INFINITY; init[2 * np + i] = -INFINITY; init[3 * np + i] = INFINITY; }
     HIPCHK(hipMemcpy(s->bounds_block, init.data(), init.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -746,7 +723,7 @@ static int ensure_full_h(qn_solver* s) {
     if (c->world > 1) { // row-sharded: the stale half of a block-row is maintained by other ranks (circulant windows, qn_sym.hip.h)
         const size_t np = (size_t)s->T.n_pad, blk = (size_t)QN_TB * np;
         const QnSymShard sh = sym_shard(s);
-        if (!s->symsh_gath) HIPCHK(hipMalloc((void**)&s->symsh_gath, (size_t)c->world * blk * sizeof(double)));
+        QNCHK(s->symsh_gath.ensure((size_t)c->world * blk));
         if (s->h_diag_stale) // (second-generation tiles: inside the local diagonal tiles only the upper 16 x 16 sub-blocks are current)
             hipLaunchKernelGGL(s2sh_diag_mirror_kernel, dim3(QN_TB / 32, QN_TB / 32, sh.nbl), dim3(256), 0, c->stream, s->H, s->T.n_pad, sh.ioff);
         for (int il = 0; il < sh.nbl; ++il) {
@@ -793,8 +770,8 @@ extern "C" int qn_solver_get_inv_hessian(qn_solver* s, double* out, int all_rank
     const size_t n = s->n, np = s->T.n_pad, rpr = s->T.rpr;
     const size_t chunk = 16;
     std::vector<double> rows(chunk * np * (all_ranks ? c->world : 1));
-    double* tmp = nullptr;
-    if (all_ranks && c->world > 1) HIPCHK(hipMalloc((void**)&tmp, (size_t)c->world * chunk * np * sizeof(double)));
+    DevBuf<double> tmp;
+    if (all_ranks && c->world > 1) QNCHK(tmp.alloc((size_t)c->world * chunk * np));
     for (size_t r0 = 0; r0 < rpr; r0 += chunk) {
         if (all_ranks && c->world > 1) {
             HIPCHK(hipMemcpyAsync(tmp + (size_t)c->rank * chunk * np, s->H + r0 * np, chunk * np * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
@@ -819,7 +796,6 @@ extern "C" int qn_solver_get_inv_hessian(qn_solver* s, double* out, int all_rank
             }
         }
     }
-    if (tmp) HIPCHK(hipFree(tmp));
     return QN_OK;
 }
 
@@ -838,19 +814,13 @@ extern "C" int qn_solver_compute_direction(qn_solver* s, const double* g_host, d
     HIPCHK(hipSetDevice(c->device));
     QNCHK(flush_pending(s)); // the lazy update of the last iteration, and whole rows of H
     const size_t np = s->T.n_pad, rpr = s->T.rpr;
-    double* buf = nullptr; // [g (np) | H g (np)]
-    HIPCHK(hipMalloc((void**)&buf, 2 * np * sizeof(double)));
-    HIPCHK(hipMemsetAsync(buf, 0, 2 * np * sizeof(double), c->stream));
+    DevBuf<double> buf; // [g (np) | H g (np)]
+    QNCHK(buf.alloc_zero(2 * np, c->stream));
     HIPCHK(hipMemcpyAsync(buf, g_host, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    int st = qn_gemv(c, s->H, np, rpr, n, buf, buf + np + (size_t)s->T.row_off);
-    if (st == QN_OK) st = exchange(c, buf + np, rpr);
-    if (st == QN_OK) {
-        hipError_t e = hipMemcpyAsync(d_host, buf + np, n * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) st = fail(QN_ABNORMAL_TERMINATION, hipGetErrorString(e));
-    }
-    (void)hipFree(buf);
-    if (st != QN_OK) return st;
+    QNCHK(qn_gemv(c, s->H, np, rpr, n, buf, buf + np + (size_t)s->T.row_off));
+    QNCHK(exchange(c, buf + np, rpr));
+    HIPCHK(hipMemcpyAsync(d_host, buf + np, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     if (s->bounded) { // BFGSB / DFPB / SR1B: P(x - H g) - x with the solver's box (bfgs_b.rs:66-77), not -H g
         std::vector<double> x(n), lb(n), ub(n);
         QNCHK(qn_solver_get_x(s, x.data()));
@@ -889,31 +859,23 @@ extern "C" int qn_solver_secant_update(qn_solver* s, const double* s_host, const
     QNCHK(poke_ctl(s));
     if (h->s_norm < s->tol || h->y_norm < s->tol) return QN_OK;
     if (s->method == QN_BROYDEN) return r1_secant_update(s, s_host, y_host, ys); // H += ((s - H y) s') H / s.y: one pass for u and w = H' s, one to apply
-    double* buf = nullptr; // [s | y | u = H y], n_pad each
-    HIPCHK(hipMalloc((void**)&buf, 3 * np * sizeof(double)));
+    DevBuf<double> buf; // [s | y | u = H y], n_pad each
+    QNCHK(buf.alloc_zero(3 * np, c->stream));
     std::vector<double> u(n);
-    int st = QN_OK;
-    auto hip_ok = [&](hipError_t e) { if (e != hipSuccess && st == QN_OK) st = fail(QN_ABNORMAL_TERMINATION, hipGetErrorString(e)); return e == hipSuccess; };
-    hip_ok(hipMemsetAsync(buf, 0, 3 * np * sizeof(double), c->stream));
-    hip_ok(hipMemcpyAsync(buf, s_host, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    hip_ok(hipMemcpyAsync(buf + np, y_host, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (st == QN_OK) st = qn_gemv(c, s->H, np, rpr, n, buf + np, buf + 2 * np + (size_t)s->T.row_off);
-    if (st == QN_OK) st = exchange(c, buf + 2 * np, rpr);
-    if (st == QN_OK) {
-        hip_ok(hipMemcpyAsync(u.data(), buf + 2 * np, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-        hip_ok(hipStreamSynchronize(c->stream));
-    }
-    if (st == QN_OK) {
-        double yu = 0.0;
-        for (size_t i = 0; i < n; ++i) yu += y_host[i] * u[i];
-        double c_ss, c_su, c_uu;
-        if (s->method == QN_BFGS) { const double rho = 1.0 / ys; c_su = -rho; c_ss = rho * rho * yu + rho; c_uu = 0.0; }
-        else { c_ss = 1.0 / ys; c_su = 0.0; c_uu = -1.0 / yu; }
-        st = qn_rank2_update(c, s->H, np, (size_t)s->T.row_off, rpr, n, buf, buf + 2 * np, c_ss, c_su, c_uu);
-        if (st == QN_OK) hip_ok(hipStreamSynchronize(c->stream));
-    }
-    (void)hipFree(buf);
-    return st;
+    HIPCHK(hipMemcpyAsync(buf, s_host, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(buf + np, y_host, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    QNCHK(qn_gemv(c, s->H, np, rpr, n, buf + np, buf + 2 * np + (size_t)s->T.row_off));
+    QNCHK(exchange(c, buf + 2 * np, rpr));
+    HIPCHK(hipMemcpyAsync(u.data(), buf + 2 * np, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    double yu = 0.0;
+    for (size_t i = 0; i < n; ++i) yu += y_host[i] * u[i];
+    double c_ss, c_su, c_uu;
+    if (s->method == QN_BFGS) { const double rho = 1.0 / ys; c_su = -rho; c_ss = rho * rho * yu + rho; c_uu = 0.0; }
+    else { c_ss = 1.0 / ys; c_su = 0.0; c_uu = -1.0 / yu; }
+    QNCHK(qn_rank2_update(c, s->H, np, (size_t)s->T.row_off, rpr, n, buf, buf + 2 * np, c_ss, c_su, c_uu));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return QN_OK;
 }
 
 extern "C" int qn_solver_set_inv_hessian(qn_solver* s, const double* h) {

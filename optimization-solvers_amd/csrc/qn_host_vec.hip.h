@@ -27,12 +27,10 @@ static int vec_grid(size_t np) { // a function of n alone: four 16-byte accesses
 static int vec_state_alloc(qn_solver* s) {
     if (s->vctl) return QN_OK;
     hipStream_t st = s->ctx->stream;
-    HIPCHK(hipMalloc((void**)&s->vctl, sizeof(QnVecCtl)));
-    HIPCHK(hipMemsetAsync(s->vctl, 0, sizeof(QnVecCtl), st));
-    HIPCHK(hipHostMalloc((void**)&s->hvctl, sizeof(QnVecCtl), hipHostMallocDefault));
-    memset(s->hvctl, 0, sizeof(QnVecCtl));
+    QNCHK(s->vctl.alloc_zero(1, st));
+    QNCHK(s->hvctl.alloc_zero(1));
     s->hvctl->lambda_min = 1e-3; s->hvctl->lambda_max = 1e3; // spg.rs:36-37
-    QNCHK(dev_alloc_zero(&s->vpart, (size_t)QN_VEC_NPART * QN_VEC_MAXG, st));
+    QNCHK(s->vpart.alloc_zero((size_t)QN_VEC_NPART * QN_VEC_MAXG, st));
     QNCHK(bounds_alloc(s)); // the box is (-inf, +inf) until qn_solver_set_bounds
     return QN_OK;
 }

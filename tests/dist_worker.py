@@ -1,5 +1,6 @@
 """Worker for the world_size-2 tests; launched by test_dist_gloo.py / test_gpu_sharded.py through
 `python -m torch.distributed.run --nproc-per-node 2 --master-addr 127.0.0.1 ... tests/dist_worker.py MODE OUT`."""
+import gc
 import json
 import os
 import sys
@@ -9,6 +10,15 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def _live_allocations(qn):
+    import ctypes as C
+    fn = qn._abi.lib().qn_debug_live_allocations
+    fn.restype, fn.argtypes = C.c_int, [C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    count, nbytes = C.c_size_t(), C.c_size_t()
+    assert fn(C.byref(count), C.byref(nbytes)) == 0
+    return count.value, nbytes.value
 
 
 def main():
@@ -145,6 +155,8 @@ def main():
         # partial n-vectors are all-gathered (host-staged here) and summed in rank order.  Against the single-rank run of the same
         # problem: same line-search cases and evaluation counts, iterates to the parity tolerance; between ranks: the same bits.
         result["cases"] = []
+        gc.collect()
+        live_before = _live_allocations(qn)  # what the library's buffer owners hold (tests/test_gpu_ownership.py): read again once all is closed
         for n in ([1024, 2048, 2040] if world == 2 else [128 * 3 * world]):  # nb = 8, 16 (even), 16 with 8 padding rows; world 3: nb = 9 (odd)
             iters = 12
             diag = P.synth_diag(n)
@@ -410,6 +422,12 @@ def main():
             case["rows_pipelined_path"] = [outs[0][1], outs[1][1]]
             ctx.set_host_exchange_async(False)
             result["cases"].append(case)
+        # every solver, objective and context of this mode closed (solvers first): the row-sharded buffers, the exchange's pinned staging
+        # and everything else the runs above allocated are released
+        dist.barrier()
+        qn.solver._close_all()
+        gc.collect()
+        result["live_allocations"] = [list(live_before), list(_live_allocations(qn))]
     gathered = [None] * world
     dist.all_gather_object(gathered, result)
     if rank == 0:

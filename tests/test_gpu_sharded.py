@@ -38,6 +38,8 @@ def _check_sharded_symmetric(res, nproc):
     on the one GPU against the single-rank run -- same line-search decisions, iterates to the parity tolerance, identical bits
     on every rank, half the matrix bytes per pass, and the getters / the row kernels see a whole matrix again afterwards."""
     assert len(res) == nproc
+    for r in res:  # nothing is left behind: the owners' count and bytes are back where they were once every handle is closed
+        assert r["live_allocations"][0] == r["live_allocations"][1], (r["rank"], r["live_allocations"])
     for r in res:
         for case in r["cases"]:
             n = case["n"]
