@@ -102,10 +102,15 @@ void* qn_context_stream(qn_context* ctx); /* hipStream_t */
  * Line searches.  Plain structs by value, as the reference's are plain data.
  *   QN_LS_MORETHUENTE : MoreThuente        (morethuente.rs:6-62, compute_step_len :165-297)
  *   QN_LS_BACKTRACKING: BackTracking       (backtracking.rs:3-58)
+ *   QN_LS_NO_SEARCH   : NoSearch           (nosearch.rs:3-15): compute_step_len returns 1.0 and makes no oracle call -- how the reference writes a pure
+ *                       Newton step.  Built for the four solvers whose update hook is the trait's default x += t d: QN_GRADIENT_DESCENT, QN_NEWTON,
+ *                       QN_COORDINATE_DESCENT, QN_PNORM_DESCENT (and qn_compute_step_len).  NOT BUILT for the quasi-Newton methods, QN_BROYDEN and the
+ *                       first-order / projected-Newton family: qn_minimize returns QN_ERROR_INPUT_PARAMS there.
  * ------------------------------------------------------------------------------------------- */
 enum { QN_LS_MORETHUENTE = 0, QN_LS_BACKTRACKING = 1,
        QN_LS_MORETHUENTE_B = 2 /* MoreThuenteB, morethuente_b.rs */, QN_LS_BACKTRACKING_B = 3 /* BackTrackingB, backtracking_b.rs */,
-       QN_LS_GLL_QUADRATIC = 4 /* GLLQuadratic, gll_quadratic.rs: the non-monotone search of Grippo, Lampariello, Lucidi; QN_SPG / QN_PROJECTED_GRADIENT only */ };
+       QN_LS_GLL_QUADRATIC = 4 /* GLLQuadratic, gll_quadratic.rs: the non-monotone search of Grippo, Lampariello, Lucidi; QN_SPG / QN_PROJECTED_GRADIENT only */,
+       QN_LS_NO_SEARCH = 5 /* NoSearch, nosearch.rs: constant step 1.0 */ };
 typedef struct {
     int32_t kind;
     int32_t _pad;
@@ -133,6 +138,7 @@ void qn_morethuente_b_new(qn_linesearch* ls);                          /* MoreTh
 void qn_backtracking_b_new(qn_linesearch* ls, double c1, double beta, const double* lower_bound_host, const double* upper_bound_host); /* backtracking_b.rs:10-23 */
 void qn_linesearch_with_lower_bound(qn_linesearch* ls, const double* lower_bound_host); /* morethuente_b.rs:32-35 */
 void qn_linesearch_with_upper_bound(qn_linesearch* ls, const double* upper_bound_host); /* morethuente_b.rs:36-39 */
+void qn_nosearch_new(qn_linesearch* ls);                               /* NoSearch, nosearch.rs:3 */
 void qn_gll_quadratic_new(qn_linesearch* ls, double c1, size_t m);                      /* GLLQuadratic::new, gll_quadratic.rs:13-23: sigma1 = 0.1, sigma2 = 0.9 */
 void qn_gll_quadratic_with_sigmas(qn_linesearch* ls, double sigma1, double sigma2);     /* :24-28 */
 
@@ -217,7 +223,20 @@ enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton
         * equation does not hold.  Line searches: every one but QN_LS_GLL_QUADRATIC.  Every oracle kind; one rank (a row-sharded context:
         * QN_ERROR_INPUT_PARAMS); synchronous requests; the full row-major H streamed once per iteration by csrc/qn_rank1.hip.h (QN_PATH_RANK1).
         * qn_solver_set_inv_hessian accepts any matrix. */
-       QN_BROYDEN = 9 /* Broyden, quasi_newton/broyden.rs */ };
+       QN_BROYDEN = 9 /* Broyden, quasi_newton/broyden.rs */,
+       /* The two remaining members of the steepest-descent family.  Both run beside QN_GRADIENT_DESCENT on the control-step machine: the default hook
+        * x += t d, has_converged = ||g||_inf < grad_tol with the NaN-ignoring max, no s_norm / y_norm, no evaluation at the accepted point; every line
+        * search QN_GRADIENT_DESCENT takes, and QN_LS_NO_SEARCH; every oracle kind; memoize 0 / 1; callbacks, trace, warm restarts.  One rank (a
+        * row-sharded context: QN_ERROR_INPUT_PARAMS); synchronous requests.
+        * QN_COORDINATE_DESCENT (coordinate_descent.rs:30-44, AS WRITTEN): p = the FIRST index of the largest |g_i| (strict >, a NaN never wins; no
+        * positive magnitude at all: p = 0) and d = -max_value.signum() e_p.  max_value is a MAGNITUDE, so its signum is +1.0: d = -e_p WHATEVER THE SIGN
+        * OF g_p.  On a coordinate with a negative gradient that is an ascent direction, and BackTracking returns beta^max_iter_line_search.  Reference
+        * behaviour, reproduced.  On the device: a two-stage (magnitude, index) reduction (cd_argmax_kernel, then the control kernel).
+        * QN_PNORM_DESCENT (pnorm_descent.rs:35): d = (-inverse_p) * g with the caller's dense matrix (qn_solver_set_inverse_p; qn_minimize without
+        * one: QN_ERROR_INPUT_PARAMS).  ONE read-only stream of the matrix per iteration -- 8 n^2 bytes, csrc/qn_pnorm.hip.h (QN_PATH_PNORM) -- whose launch
+        * also leaves g.d and ||g||_inf; n <= 5: the reference's literal column sweep.  h_passes / h_bytes of qn_stats count those streams. */
+       QN_COORDINATE_DESCENT = 10 /* CoordinateDescent, steepest_descent/coordinate_descent.rs */,
+       QN_PNORM_DESCENT = 11 /* PnormDescent, steepest_descent/pnorm_descent.rs */ };
 typedef struct qn_solver qn_solver;
 
 /* BFGS::new(tol, x0) / DFP::new / GradientDescent::new(grad_tol, x0): H = I (no identity copy is kept) */
@@ -238,6 +257,11 @@ int qn_solver_spg_lambda(qn_solver* s, double* out, int* is_some);
  * (The count comes back through a size_t*, like every other count in this header, and not through a uint64_t*: the ABI check that compares this
  * header with the Python and Rust mirrors knows the pointer types the header already used.  Both are 64 bits wide on every platform ROCm runs on.) */
 int qn_solver_newton_factorisations(qn_solver* s, size_t* out);
+/* QN_PNORM_DESCENT: inverse_p of PnormDescent::new(grad_tol, x0, inverse_p) (pnorm_descent.rs:20-27) and its getter; column-major n x n, like DMatrix
+ * and like qn_solver_set_inv_hessian.  ANY matrix is accepted: the reference tests neither symmetry nor definiteness.  It is a constructor argument,
+ * not state: qn_solver_reset keeps it.  Other methods: QN_ERROR_INPUT_PARAMS. */
+int qn_solver_set_inverse_p(qn_solver* s, const double* p_colmajor_host);
+int qn_solver_get_inverse_p(qn_solver* s, double* out_colmajor_host);
 /* back to the state right after BFGS::new(tol, x0): x = x0, H = I, k = 0, s_norm = y_norm = None */
 int qn_solver_reset(qn_solver* s, const double* x0_host);
 
@@ -340,6 +364,7 @@ typedef struct {
 #define QN_PATH_VECTOR 64u     /* the first-order family's device-wide vector kernels (csrc/qn_vec.hip.h): QN_SPG, QN_PROJECTED_GRADIENT */
 #define QN_PATH_PNEWTON 128u   /* ... with the direction from a Cholesky solve: QN_PROJECTED_NEWTON, QN_SPECTRAL_PROJECTED_NEWTON (set beside QN_PATH_VECTOR) */
 #define QN_PATH_RANK1 256u     /* QN_BROYDEN's H passes: the square-tile kernel of csrc/qn_rank1.hip.h (non-symmetric rank-1 update, row AND column sums in one stream of H) */
+#define QN_PATH_PNORM 512u     /* QN_PNORM_DESCENT's directions: pnorm_dir_kernel of csrc/qn_pnorm.hip.h (one read-only stream of inverse_p, with g.d and ||g||_inf in the same launch) */
 int qn_solver_get_stats(qn_solver* s, qn_stats* out);
 /* profiling != 0: bracket every launch with HIP events on the solver's stream (slower; for roofline reports) */
 int qn_solver_set_profiling(qn_solver* s, int on);
@@ -375,7 +400,9 @@ typedef enum {
     QN_OPT_EVAL_ZIGZAG = 20,               /* [1] the mover + multiplier kernel streams its two tiles in the other order in launches of odd parity: an evaluation launch right behind another one starts with the tile the XCD's L2 still holds (csrc/qn_sym2r.hip.h, ZIG-ZAG); 0: the same order in every launch -- the same bits */
     QN_OPT_TOUCH_H_ROWS = 21,              /* [8] n = 4096: the accept-reduce launch carries workgroups that only load the first `value` rows (of a wave's 16; 0, 4, 6, 8, 10, 12 or 16) of the tile the update-tile launch's workgroup of the same index streams first -- into the L2 of the XCD both run on (csrc/qn_sym2.hip.h, TOUCH WORKGROUPS); a NUMBER; loads only -- the same bits */
     QN_OPT_TOUCH_Q_ROWS = 22,              /* [6] ... and the update-reduce launch for the evaluation launch behind it (rows of Q's tiles) */
-    QN_OPT_PNEWTON_REUSE_FACTOR = 23       /* [1] ProjectedNewton / SpectralProjectedNewton on a device quadratic: the Hessian's Cholesky factor is kept between iterations (the matrix does not change); 0: factorise in every iteration -- the same bits */
+    QN_OPT_PNEWTON_REUSE_FACTOR = 23,      /* [1] ProjectedNewton / SpectralProjectedNewton on a device quadratic: the Hessian's Cholesky factor is kept between iterations (the matrix does not change); 0: factorise in every iteration -- the same bits */
+    QN_OPT_PNORM_NONTEMPORAL = 24,         /* [-1] PnormDescent: inverse_p through non-temporal loads; 1 / 0 force it on / off, -1 (a NUMBER): by size -- on once the matrix is past the Infinity Cache's reach (~230 MB, n ~ 5400) -- the same bits */
+    QN_OPT_PNORM_ROWS_PER_WAVE = 25        /* [0] ... rows a wave of its direction kernel holds in flight: 2 or 4 (a NUMBER); 0: by size (2 up to n = 8192) -- the same bits */
 } qn_option;
 int qn_solver_set_option(qn_solver* s, int option, int value);
 

@@ -141,6 +141,14 @@ class BackTracking {
 };
 
 // gll_quadratic.rs: the non-monotone search for SpectralProjectedGradient / ProjectedGradientDescent (the history lives in the solver)
+// line_search/nosearch.rs: compute_step_len returns 1.0 and never calls the oracle; pairs with GradientDescent, Newton, CoordinateDescent, PnormDescent
+class NoSearch {
+    qn_linesearch s_;
+  public:
+    NoSearch() { qn_nosearch_new(&s_); }
+    qn_linesearch& ffi() { return s_; }
+};
+
 class GLLQuadratic {
     qn_linesearch s_;
   public:
@@ -215,7 +223,7 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
     bool gradient_next_iterate_too_close() const { int v; check(qn_solver_gradient_next_iterate_too_close(h_, &v)); return v != 0; } // bfgs.rs:21-26
     DVector approx_inv_hessian() const { DVector m(n_ * n_); check(qn_solver_get_inv_hessian(h_, m.data(), 1)); return m; }          // column-major, like DMatrix
     bool has_converged(const FuncEvalMultivariate& eval) const { // bfgs.rs:64-76 / gradient_descent.rs:46-53
-        if (METHOD == QN_GRADIENT_DESCENT) {
+        if (METHOD == QN_GRADIENT_DESCENT || METHOD == QN_COORDINATE_DESCENT || METHOD == QN_PNORM_DESCENT) { // (pnorm_descent.rs:52-59, coordinate_descent.rs:61-68)
             Floating acc = -INFINITY;
             for (Floating v : eval.g()) acc = std::fmax(std::fabs(v), acc);
             return acc < tol();
@@ -276,6 +284,21 @@ using BFGS = LineSearchSolver<QN_BFGS>;                       // quasi_newton/bf
 using DFP = LineSearchSolver<QN_DFP>;                         // quasi_newton/dfp.rs
 using GradientDescent = LineSearchSolver<QN_GRADIENT_DESCENT>; // steepest_descent/gradient_descent.rs
 using Broyden = LineSearchSolver<QN_BROYDEN>;                 // quasi_newton/broyden.rs
+
+using CoordinateDescent = LineSearchSolver<QN_COORDINATE_DESCENT>; // steepest_descent/coordinate_descent.rs: d = -e_p, p the first index of the largest |g_i|
+
+// steepest_descent/pnorm_descent.rs: new(grad_tol, x0, inverse_p) with inverse_p column-major n x n (DMatrix); d = (-inverse_p) * g
+class PnormDescent : public LineSearchSolver<QN_PNORM_DESCENT> {
+  public:
+    PnormDescent(Floating grad_tol, const DVector& x0, const DVector& inverse_p_colmajor, Context& ctx = Context::default_context())
+        : LineSearchSolver<QN_PNORM_DESCENT>(grad_tol, x0, ctx) {
+        if (inverse_p_colmajor.size() != x0.size() * x0.size()) throw SolverError(QN_ERROR_INPUT_PARAMS);
+        check(qn_solver_set_inverse_p(this->handle(), inverse_p_colmajor.data()));
+    }
+    static PnormDescent new_(Floating grad_tol, const DVector& x0, const DVector& inverse_p_colmajor) { return PnormDescent(grad_tol, x0, inverse_p_colmajor); }
+    Floating grad_tol() const { return this->tol(); }
+    DVector inverse_p() const { const size_t n = this->x().size(); DVector m(n * n); check(qn_solver_get_inverse_p(this->handle(), m.data())); return m; }
+};
 
 // quasi_newton/broyden_b.rs: new(tol, x0, lower_bound, upper_bound); x0 is projected (:51), d = P(x - H g) - x (:73-77); everything else is Broyden's
 class BroydenB : public LineSearchSolver<QN_BROYDEN> {

@@ -8,9 +8,11 @@ LIB_PATH = os.environ.get("QN_HIP_LIB") or os.path.join(_HERE, "lib", "libqn_hip
 
 OK, MAX_ITER_REACHED, OUT_OF_DOMAIN, ERROR_INPUT_PARAMS, ABNORMAL_TERMINATION = range(5)
 LS_MORETHUENTE, LS_BACKTRACKING, LS_MORETHUENTE_B, LS_BACKTRACKING_B, LS_GLL_QUADRATIC = 0, 1, 2, 3, 4
+LS_NO_SEARCH = 5  # line_search/nosearch.rs
 ORACLE_HOST, ORACLE_DEVICE_FN, ORACLE_OBJECTIVE = 0, 1, 2
 BFGS, DFP, GRADIENT_DESCENT, NEWTON, SR1, SPG, PROJECTED_GRADIENT, PROJECTED_NEWTON, SPECTRAL_PROJECTED_NEWTON = 0, 1, 2, 3, 4, 5, 6, 7, 8
 BROYDEN = 9  # quasi_newton/broyden.rs (BroydenB once bounds are set)
+COORDINATE_DESCENT, PNORM_DESCENT = 10, 11  # steepest_descent/coordinate_descent.rs, pnorm_descent.rs
 UNIQUE_ID_BYTES = 128
 
 dp = C.POINTER(C.c_double)
@@ -60,6 +62,7 @@ class Stats(C.Structure):
 
 PATH_FUSED, PATH_SYM, PATH_SYM_GENERIC, PATH_PIPELINED, PATH_SYM2, PATH_TILES1, PATH_VECTOR, PATH_PNEWTON = 1, 2, 4, 8, 16, 32, 64, 128
 PATH_RANK1 = 256
+PATH_PNORM = 512
 
 
 # every symbol include/qn_hip.h declares: (name, restype, argtypes)
@@ -96,6 +99,7 @@ SYMBOLS = [
     ("qn_backtracking_b_new", None, [C.POINTER(LineSearchStruct), C.c_double, C.c_double, C.c_void_p, C.c_void_p]),
     ("qn_linesearch_with_lower_bound", None, [C.POINTER(LineSearchStruct), C.c_void_p]),
     ("qn_linesearch_with_upper_bound", None, [C.POINTER(LineSearchStruct), C.c_void_p]),
+    ("qn_nosearch_new", None, [C.POINTER(LineSearchStruct)]),
     ("qn_gll_quadratic_new", None, [C.POINTER(LineSearchStruct), C.c_double, C.c_size_t]),
     ("qn_gll_quadratic_with_sigmas", None, [C.POINTER(LineSearchStruct), C.c_double, C.c_double]),
     ("qn_quadratic_create", C.c_int, [C.c_void_p, C.c_size_t, dp, dp, C.POINTER(C.c_void_p)]),
@@ -108,6 +112,8 @@ SYMBOLS = [
     ("qn_solver_destroy", None, [C.c_void_p]),
     ("qn_solver_reset", C.c_int, [C.c_void_p, dp]),
     ("qn_solver_set_bounds", C.c_int, [C.c_void_p, dp, dp]),
+    ("qn_solver_set_inverse_p", C.c_int, [C.c_void_p, dp]),
+    ("qn_solver_get_inverse_p", C.c_int, [C.c_void_p, dp]),
     ("qn_solver_set_spg_lambdas", C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     ("qn_solver_spg_lambda", C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int)]),
     ("qn_solver_newton_factorisations", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),

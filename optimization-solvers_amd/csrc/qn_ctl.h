@@ -19,8 +19,10 @@ enum QnPhase : int32_t {
                               // coefficients of the update this pass completes (derived from the pass's partial sums)
     QN_PH_REQ_VEC = 8,   // sym2: turn the slots of the last evaluation into vectors (g+, y, x+, s) and their sums
     QN_PH_REQ_NEWTON = 6, // Newton: factorise the Hessian at x_k and solve for d and H^-1 d (5 is the in-kernel RUNNING marker)
-    QN_PH_REQ_DIR = 9    // sym2, bounded variants: turn the lazy direction into a stored one -- projected onto the solver's box (bfgs_b.rs:72-75)
+    QN_PH_REQ_DIR = 9,   // sym2, bounded variants: turn the lazy direction into a stored one -- projected onto the solver's box (bfgs_b.rs:72-75)
                          // -- and find the step at which it leaves the line search's box (morethuente_b.rs:185-198): s2_dir_kernel
+    QN_PH_REQ_STEEP = 10 // PnormDescent / CoordinateDescent: run the direction kernel of qn_pnorm.hip.h on g (pnorm_dir_kernel: d and the shares of
+                         // g.d, ||g||_inf; cd_argmax_kernel: the (magnitude, index) shares) -- like Newton's, a direction that arrives from outside
 };
 
 enum QnReqKind : int32_t { QN_REQ_X = 0 /* at x_k itself */, QN_REQ_T = 1 /* at x_k + t d_k */ };
@@ -44,10 +46,14 @@ enum QnState : int32_t {
     QN_ST_AFTER_U,
     QN_ST_ITER_END,
     QN_ST_AFTER_NEWTON,
-    QN_ST_LS_ONLY // qn_compute_step_len: g.d for the caller's direction, then the line search alone
+    QN_ST_LS_ONLY, // qn_compute_step_len: g.d for the caller's direction, then the line search alone
+    QN_ST_AFTER_STEEP // PnormDescent / CoordinateDescent: fold the direction kernel's shares (and write CoordinateDescent's one-hot d), convergence test
 };
 
 #define QN_METHOD_BROYDEN 9 // == QN_BROYDEN (include/qn_hip.h): the one method whose pending update is rank-1 and not symmetric (qn_rank1.hip.h)
+#define QN_METHOD_CD 10     // == QN_COORDINATE_DESCENT
+#define QN_METHOD_PNORM 11  // == QN_PNORM_DESCENT
+#define QN_LS_KIND_NOSEARCH 5 // == QN_LS_NO_SEARCH: compute_step_len returns 1.0 and calls nothing (line_search/nosearch.rs)
 #define QN_LS_MODIFIED_BIT (1 << 30) // trace: ls_cases bit 30 = the modified-updating switch of morethuente.rs:212-215 was thrown
 
 struct QnTraceRec { // == qn_trace_rec (include/qn_hip.h)

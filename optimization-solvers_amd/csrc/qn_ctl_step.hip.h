@@ -43,7 +43,7 @@ __device__ __forceinline__ void qn_keepalive(double v) { asm volatile("" ::"v"(v
 // scalar states (thread 0 only).  Runs until the machine yields or reaches a state that needs all threads.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool qn_check_is_scalar(const QnCtl& c) {
-    return c.method != 2 && (c.small_n || c.gg_valid || c.method == 3);
+    return c.method != 2 && c.method != QN_METHOD_CD && c.method != QN_METHOD_PNORM && (c.small_n || c.gg_valid || c.method == 3);
 }
 
 // Every scalar state is a function of its own; ctl_scalar_run dispatches on the state and then runs the successions that are
@@ -234,6 +234,7 @@ __device__ __forceinline__ bool qn_st_check(QnCtl& c, const QnVecs& V, double* s
 template <int LEAN>
 __device__ __forceinline__ void qn_st_ls_begin(QnCtl& c) {
     c.ls_i = 0;
+    if (!LEAN && c.ls_kind == QN_LS_KIND_NOSEARCH) { c.ls_result = 1.0; c.state = QN_ST_AFTER_LS; return; } // nosearch.rs:13: the step is 1.0, no oracle call
     if (!LEAN && c.ls_kind == 2) c.mt_tmax = fmin(c.mt_tmax, c.mtb_cand); // morethuente_b.rs:201: self.t_max = self.t_max.min(candidate) -- persists
     if (c.ls_kind == 0 || (!LEAN && c.ls_kind == 2)) { // morethuente.rs:173-178
         c.use_mod = 0; c.conv = 0;
@@ -343,7 +344,7 @@ __device__ __forceinline__ void qn_st_bt_after(QnCtl& c) { // backtracking.rs:37
 template <int LEAN>
 __device__ __forceinline__ bool qn_st_after_ls(QnCtl& c) {
     if (!LEAN && c.ls_only) { c.status = 0; c.phase = QN_PH_DONE; return true; } // compute_step_len returns the step, nothing else
-    if (!LEAN && (c.method == 2 || c.method == 3)) return false; // gradient descent / Newton: the default hook x += step*d needs all threads
+    if (!LEAN && (c.method == 2 || c.method == 3 || c.method == QN_METHOD_CD || c.method == QN_METHOD_PNORM)) return false; // gradient descent / Newton / coordinate / p-norm descent: the default hook x += step*d needs all threads
     req_eval_t<LEAN>(c, c.ls_result, QN_ST_AFTER_NEXT, 1); // bfgs.rs:94,98: oracle(x + step*d)
     return true;
 }
@@ -609,7 +610,7 @@ __global__ __launch_bounds__(QN_CTL_TPB) void ctl_step_kernel(QnCtl* __restrict_
             else c.last_valid = 0;
         }
         if (expect_phase == QN_PH_IDLE) c.state = c.ls_only ? QN_ST_LS_ONLY : QN_ST_BEGIN;
-        else if (expect_phase == QN_PH_REQ_EVAL || expect_phase == QN_PH_REQ_HPASS || expect_phase == QN_PH_REQ_NEWTON) c.state = c.after_state;
+        else if (expect_phase == QN_PH_REQ_EVAL || expect_phase == QN_PH_REQ_HPASS || expect_phase == QN_PH_REQ_NEWTON || expect_phase == QN_PH_REQ_STEEP) c.state = c.after_state;
         // (QN_PH_REQ_HPASS_EVAL was turned into QN_PH_REQ_EVAL by the commit above)
         c.phase = QN_PH_RUNNING;
         ctl_scalar_run(c, V, small_scratch);
@@ -644,13 +645,26 @@ __global__ __launch_bounds__(QN_CTL_TPB) void ctl_step_kernel(QnCtl* __restrict_
         } break;
 
         case QN_ST_CHECK: { // vector variant: gradient descent (inf-norm, d = -g), or ||g|| not known yet
-            const bool gd_method = c.method == 2;
+            // CoordinateDescent, and PnormDescent beyond n = 5: the direction, ||g||_inf and g.d come from the direction kernel (qn_pnorm.hip.h).
+            // ls_solver.rs:37-40 tests f first; the convergence test waits for the kernel's ||g||_inf (QN_ST_AFTER_STEEP) -- the same decisions.
+            if (c.method == QN_METHOD_CD || (c.method == QN_METHOD_PNORM && !c.small_n)) {
+                if (tid == 0) {
+                    const double f = c.f_k;
+                    c.tr_f = f;
+                    if (isnan(f) || isinf(f)) { c.gnorm = NAN; c.tr_gnorm = NAN; c.status = 2; c.phase = QN_PH_DONE; }
+                    else { c.after_state = QN_ST_AFTER_STEEP; c.phase = QN_PH_REQ_STEEP; }
+                }
+                break;
+            }
+            const bool pn_small = c.method == QN_METHOD_PNORM; // n <= 5: the reference's literal column sweep, thread 0
+            const bool gd_method = c.method == 2 || pn_small;
             double gnorm, p[2] = {0.0, 0.0};
             if (gd_method) {
                 double m = -INFINITY; // fold(NEG_INFINITY, |acc, x| x.abs().max(acc)): NaN entries are ignored
                 for (int i = tid; i < n; i += tpb) {
                     const double gi = vg[i];
                     m = fmax(fabs(gi), m);
+                    if (pn_small) continue;
                     const double di = -gi; // gradient_descent.rs:29
                     vd[i] = di;
                     p[0] = __builtin_fma(gi, di, p[0]);
@@ -660,7 +674,14 @@ __global__ __launch_bounds__(QN_CTL_TPB) void ctl_step_kernel(QnCtl* __restrict_
                 ctl_block_sum<2, true>(p, lds);
                 if (c.small_n) {
                     __syncthreads();
-                    if (tid == 0) p[0] = ref_dot(V.g, V.d, n);
+                    if (tid == 0) {
+                        if (pn_small) { // pnorm_descent.rs:35: y = P[:,0] g_0; y += P[:,j] g_j (two roundings per term); d = -y
+                            small_direction(V.H, n_pad, n, V.g, V.d, small_scratch);
+                            for (int i = 0; i < n; ++i) p[1] += isfinite(V.d[i]) ? 0.0 : 1.0;
+                            c.n_hpasses++;
+                        }
+                        p[0] = ref_dot(V.g, V.d, n);
+                    }
                 }
             } else {
                 for (int i = tid; i < n_pad; i += tpb) { const double gi = vg[i]; p[0] = __builtin_fma(gi, gi, p[0]); }
@@ -677,6 +698,55 @@ __global__ __launch_bounds__(QN_CTL_TPB) void ctl_step_kernel(QnCtl* __restrict_
                     else if (gnorm < c.tol) { c.status = 0; c.phase = QN_PH_DONE; } // gradient_descent.rs:46-53
                     else { c.gd0 = p[0]; c.d_finite = p[1] == 0.0; c.last_valid = 0; c.state = QN_ST_LS_BEGIN; }
                 }
+            }
+        } break;
+
+        case QN_ST_AFTER_STEEP: { // the direction kernel has run on g (qn_pnorm.hip.h): stage two of its reductions, then has_converged and g.d
+            const int ns = V.steep_nshare;
+            const double* __restrict__ const part = V.steep_part;
+            double gnorm, p[2] = {0.0, 0.0};
+            if (c.method == QN_METHOD_CD) {
+                // coordinate_descent.rs:31-41: the shares cover ascending runs of indices; thread t folds shares t, t + tpb, ... in ascending order
+                // with the strict >, the workgroup's pairs meet under the same rule: the FIRST index of the largest magnitude, whatever the tree
+                double m = 0.0, gm = -INFINITY;
+                int ix = QN_CD_NOIDX;
+                for (int b = tid; b < ns; b += tpb) {
+                    qn_argmax_take(m, ix, part[b], (int)part[(size_t)ns + b]);
+                    gm = fmax(part[2 * (size_t)ns + b], gm);
+                }
+                ctl_block_argmax(m, ix, lds);
+                gnorm = ctl_block_fmax<false>(gm, lds);
+                const int pos = ix == QN_CD_NOIDX ? 0 : ix; // nothing above 0 (all zeros, all NaN): the fold's start, position 0
+                // direction_k[position] = -max_value.signum(), :42-43: max_value is a MAGNITUDE, its signum is +1.0 (0.0f64.signum() too), so d = -e_p
+                // whatever the sign of g_p -- the reference's behaviour, reproduced.  g.d is the full dot product: a non-finite g_i poisons it there too.
+                for (int i = tid; i < n_pad; i += tpb) {
+                    const double di = (i == pos) ? -1.0 : 0.0;
+                    vd[i] = di;
+                    if (i < n) p[0] = __builtin_fma(vg[i], di, p[0]);
+                }
+                ctl_block_sum<2, false>(p, lds);
+            } else {
+                // thread t adds its contiguous run of shares in index order, the block sum adds the threads' totals: an order fixed by n alone
+                const int per = (ns + tpb - 1) / tpb;
+                double gm = -INFINITY;
+                for (int b = tid * per; b < min(ns, (tid + 1) * per); ++b) {
+                    p[0] = p[0] + part[b];
+                    gm = fmax(part[(size_t)ns + b], gm);
+                    p[1] += part[2 * (size_t)ns + b];
+                }
+                gnorm = ctl_block_fmax<false>(gm, lds);
+                ctl_block_sum<2, false>(p, lds);
+            }
+            if (c.small_n) {
+                __threadfence_block();
+                __syncthreads();
+                if (tid == 0) p[0] = ref_dot(V.g, V.d, n);
+            }
+            if (tid == 0) {
+                if (c.method == QN_METHOD_PNORM) c.n_hpasses++; // one read-only stream of inverse_p
+                c.gnorm = gnorm; c.tr_gnorm = gnorm;
+                if (gnorm < c.tol) { c.status = 0; c.phase = QN_PH_DONE; } // pnorm_descent.rs:52-59, coordinate_descent.rs:61-68
+                else { c.gd0 = p[0]; c.d_finite = p[1] == 0.0; c.last_valid = 0; c.state = QN_ST_LS_BEGIN; }
             }
         } break;
 

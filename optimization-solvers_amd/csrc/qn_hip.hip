@@ -57,6 +57,7 @@ extern "C" const char* qn_status_string(int status) {
 #include "qn_host_solver.hip.h"
 #include "qn_host_launch.hip.h"
 #include "qn_host_rank1.hip.h"
+#include "qn_host_pnorm.hip.h"
 #include "qn_host_newton.hip.h"
 #include "qn_host_minimize.hip.h"
 #include "qn_host_blas.hip.h"

@@ -4,6 +4,7 @@
 #pragma once
 struct Run;
 static int r1_enqueue_req(qn_solver* s); // QN_BROYDEN: qn_host_rank1.hip.h
+static int steep_enqueue_req(qn_solver* s); // QN_COORDINATE_DESCENT / QN_PNORM_DESCENT: qn_host_pnorm.hip.h
 static int enqueue_newton(qn_solver* s, const qn_oracle* o, qn_objective* obj);
 
 // the oracle of a minimize call, validated; *obj: its device objective, if it is one (whether the solver family runs that objective is the caller's test)
@@ -41,6 +42,7 @@ struct Run {
     bool proj = false;        // ... whose line search is BackTrackingB: every evaluation slot has s2_proj_kernel in front of it (projected trial points)
     bool btb = false;         // ... BackTrackingB on this path at all (proj: with the projection as a launch of its own; QnS2Args.projfold: inside the evaluation kernel)
     bool bnd = false;         // ... a bounded run on it (BFGSB / DFPB, MoreThuenteB): one more launch per iteration, s2_dir_kernel (qn_sym2.hip.h)
+    bool pnorm = false;       // PnormDescent beyond n = 5: its directions by pnorm_dir_kernel (qn_pnorm.hip.h)
     bool rank1 = false;       // Broyden: the generic machine, its H passes by the rank-1 tile kernel (qn_rank1.hip.h)
     bool tiles1 = false;      // the update pass's tiles through the first-generation tile kernel (one workgroup per tile, two per CU) behind a
                               // one-workgroup launch that runs the machine: H's share past the Infinity Cache (see plan_run)

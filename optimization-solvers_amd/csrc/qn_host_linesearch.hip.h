@@ -37,6 +37,10 @@ extern "C" void qn_backtracking_b_new(qn_linesearch* ls, double c1, double beta,
 }
 extern "C" void qn_linesearch_with_lower_bound(qn_linesearch* ls, const double* lb) { ls->lower_bound_host = lb; }
 extern "C" void qn_linesearch_with_upper_bound(qn_linesearch* ls, const double* ub) { ls->upper_bound_host = ub; }
+extern "C" void qn_nosearch_new(qn_linesearch* ls) { // NoSearch, nosearch.rs:3
+    memset(ls, 0, sizeof(*ls));
+    ls->kind = QN_LS_NO_SEARCH;
+}
 extern "C" void qn_backtracking_new(qn_linesearch* ls, double c1, double beta) { // backtracking.rs:8-10
     memset(ls, 0, sizeof(*ls));
     ls->kind = QN_LS_BACKTRACKING;

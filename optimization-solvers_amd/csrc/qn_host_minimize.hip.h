@@ -15,7 +15,12 @@ static int plan_run(Run& r, qn_solver* s, qn_linesearch* ls, const qn_oracle* o,
     qn_context* c = s->ctx;
     const qn_callback_fn callback = r.callback;
     const int ls_only = r.ls_only;
-    if (ls->kind < QN_LS_MORETHUENTE || ls->kind > QN_LS_BACKTRACKING_B) return fail(QN_ERROR_INPUT_PARAMS, "unknown line search");
+    if (ls->kind < QN_LS_MORETHUENTE || (ls->kind > QN_LS_BACKTRACKING_B && ls->kind != QN_LS_NO_SEARCH)) return fail(QN_ERROR_INPUT_PARAMS, "unknown line search");
+    // NoSearch (nosearch.rs): built for the four solvers whose update hook is the trait's default x += t d
+    if (ls->kind == QN_LS_NO_SEARCH && s->method != QN_GRADIENT_DESCENT && s->method != QN_NEWTON && !steep_method(s->method))
+        return fail(QN_ERROR_INPUT_PARAMS, "NoSearch pairs with GradientDescent, Newton, CoordinateDescent and PnormDescent only");
+    if (s->method == QN_PNORM_DESCENT && !s->pnorm_set) return fail(QN_ERROR_INPUT_PARAMS, "PnormDescent: inverse_p has not been set (qn_solver_set_inverse_p)");
+    if (steep_method(s->method)) QNCHK(steep_alloc(s));
     const bool ls_bounded = r.ls_bounded = ls->kind == QN_LS_MORETHUENTE_B || ls->kind == QN_LS_BACKTRACKING_B;
     if (ls_bounded || s->bounded) {
         QNCHK(bounds_alloc(s));
@@ -101,6 +106,7 @@ static int plan_run(Run& r, qn_solver* s, qn_linesearch* ls, const qn_oracle* o,
     // below all start from BFGS / DFP / SR1).  It runs the generic machine with synchronous requests, its H passes by qn_rank1.hip.h; n <= 5: the
     // control kernel alone.
     r.rank1 = s->method == QN_BROYDEN && !h->small_n;
+    r.pnorm = s->method == QN_PNORM_DESCENT && !h->small_n; // (CoordinateDescent and PnormDescent: no H, so none of the predicates above admits them either)
     if (s->method == QN_BROYDEN && (r.fused || r.sym || r.sym_generic)) return fail(QN_ABNORMAL_TERMINATION, "Broyden on a symmetric-storage path");
     if ((r.sym || r.sym_generic) && c->world > 1) QNCHK(solver_alloc_symsh_lists(s));
     if (r.sym_generic) {
@@ -167,7 +173,7 @@ static int plan_run(Run& r, qn_solver* s, qn_linesearch* ls, const qn_oracle* o,
     h->status = -1;
     // only the quadratic objective's kernels are predicated on the control block; everything else is serviced synchronously
     const bool can_pipeline = (r.oracle_tpl == QN_ORACLE_QUAD || r.gobj) && !callback && !(c->world > 1 && !c->comm && !c->host_async);
-    r.sync = s->method == QN_NEWTON || s->method == QN_BROYDEN || s->sync_mode == 1 || (s->sync_mode == -1 && !(can_pipeline && o->memoize)) || !can_pipeline;
+    r.sync = s->method == QN_NEWTON || s->method == QN_BROYDEN || steep_method(s->method) || s->sync_mode == 1 || (s->sync_mode == -1 && !(can_pipeline && o->memoize)) || !can_pipeline;
     return QN_OK;
 }
 
@@ -395,6 +401,7 @@ static int pump_ctl_sync(Run& r) {
             QNCHK(enqueue_hpass_req(r)); QNCHK(enqueue_eval(r, 1)); QNCHK(launch_ctl(r, QN_PH_REQ_HPASS_EVAL));
         }
         else if (ph == QN_PH_REQ_NEWTON) { { ProfScope ps(s, KC_NEWTON); QNCHK(enqueue_newton(s, r.o, r.obj)); } QNCHK(launch_ctl(r, QN_PH_REQ_NEWTON)); }
+        else if (ph == QN_PH_REQ_STEEP) { QNCHK(steep_enqueue_req(s)); QNCHK(launch_ctl(r, QN_PH_REQ_STEEP)); }
         else if (ph == QN_PH_ITER_DONE) { r.callback(r.callback_user, s); QNCHK(launch_ctl(r, QN_PH_ITER_DONE)); }
         else return fail(QN_ABNORMAL_TERMINATION, "control block in an unexpected phase");
     }
@@ -485,7 +492,7 @@ static void finish_stats(Run& r) {
     s->stats.total_xchg_scalar += c->n_xchg_scalar - r.xs0;
     s->stats.path = (r.fused ? QN_PATH_FUSED : 0u) | (r.sym ? QN_PATH_SYM : 0u) | (r.sym_generic ? QN_PATH_SYM_GENERIC : 0u) |
                     (r.sync ? 0u : QN_PATH_PIPELINED) | (r.sym2 ? QN_PATH_SYM2 : 0u) | ((r.tiles1 || (r.gobj && c->world == 1)) ? QN_PATH_TILES1 : 0u) |
-                    (r.rank1 ? QN_PATH_RANK1 : 0u);
+                    (r.rank1 ? QN_PATH_RANK1 : 0u) | (r.pnorm ? QN_PATH_PNORM : 0u);
 }
 
 static int minimize_impl(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, size_t max_iter_solver, size_t max_iter_line_search,

@@ -26,6 +26,11 @@ struct qn_solver {
     // symmetric-storage fast path (qn_sym.hip.h): slot buffer, tile count per side, opt-out, "user installed a non-symmetric H"
     DevBuf<double> sym_part;
     int sym_nb = 0;
+    DevBuf<double> pnorm_P; // QN_PNORM_DESCENT: inverse_p, row-major n_pad x n_pad, padding zero (qn_solver_set_inverse_p; kept by qn_solver_reset)
+    bool pnorm_set = false;
+    int pnorm_nt = -1, pnorm_rw = 0; // QN_OPT_PNORM_NONTEMPORAL (-1: by size), QN_OPT_PNORM_ROWS_PER_WAVE (0: by size)
+    DevBuf<double> steep_part; // QN_PNORM_DESCENT / QN_COORDINATE_DESCENT (qn_pnorm.hip.h): the direction kernel's shares, [3][steep_nshare]
+    int steep_nshare = 0;
     DevBuf<double> r1_part; // QN_BROYDEN (qn_rank1.hip.h): the tiles' row and column partials, [3][r1_nb][n_pad]
     int r1_nb = 0;
     bool no_sym = false, h_nonsym = false;
@@ -359,6 +364,9 @@ static int vec_state_alloc(qn_solver* s);
 static void vec_state_reset(qn_solver* s);
 static int vec_compute_direction(qn_solver* s, const double* g_host, double* d_host);
 static int bounds_alloc(qn_solver* s);
+static bool steep_method(int method); // QN_COORDINATE_DESCENT / QN_PNORM_DESCENT: qn_host_pnorm.hip.h
+static int steep_alloc(qn_solver* s);
+static int steep_compute_direction(qn_solver* s, const double* g_host, double* d_host);
 static int r1_flush(qn_solver* s); // QN_BROYDEN: qn_host_rank1.hip.h
 static int r1_secant_update(qn_solver* s, const double* s_host, const double* y_host, double ys);
 
@@ -374,8 +382,9 @@ static int solver_alloc_hp(qn_solver* s) {
 
 extern "C" int qn_solver_create(qn_context* ctx, int method, double tol, const double* x0_host, size_t n, qn_solver** out) {
     if (!ctx || !x0_host || !out || n == 0) return fail(QN_ERROR_INPUT_PARAMS, "null argument or n == 0");
-    if (method != QN_BFGS && method != QN_DFP && method != QN_GRADIENT_DESCENT && method != QN_NEWTON && method != QN_SR1 && method != QN_BROYDEN && !vec_method(method))
+    if (method != QN_BFGS && method != QN_DFP && method != QN_GRADIENT_DESCENT && method != QN_NEWTON && method != QN_SR1 && method != QN_BROYDEN && !steep_method(method) && !vec_method(method))
         return fail(QN_ERROR_INPUT_PARAMS, "unknown method");
+    if (steep_method(method) && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "CoordinateDescent / PnormDescent run on one rank");
     if (method == QN_BROYDEN && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "Broyden runs on one rank: its non-symmetric H needs column sums, which a row-sharded context (world > 1) does not have");
     if (vec_method(method) && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient / projected Newton run on one rank");
     if (n > (size_t)1 << 30) return fail(QN_ERROR_INPUT_PARAMS, "n too large");
@@ -415,6 +424,7 @@ extern "C" int qn_solver_create(qn_context* ctx, int method, double tol, const d
     QNCHK(s->hg.alloc(n + 1));
     HIPCHK(hipMemcpyAsync(s->V.x, x0_host, n * sizeof(double), hipMemcpyHostToDevice, st));
     if (vec_method(method)) QNCHK(vec_state_alloc(s)); // O(n): no H, no n x n scratch
+    if (steep_method(method)) QNCHK(steep_alloc(s));
     HIPCHK(hipStreamSynchronize(st));
     return QN_OK;
 }
@@ -501,6 +511,14 @@ extern "C" int qn_solver_set_option(qn_solver* s, int option, int value) {
     case QN_OPT_BTB_PROJECT_IN_EVAL: s->no_projfold = !on; return QN_OK;
     case QN_OPT_EVAL_ZIGZAG: s->zig = on ? 1 : 0; return QN_OK;
     case QN_OPT_PNEWTON_REUSE_FACTOR: s->pn_reuse = on ? 1 : 0; s->pn_factor_serial = 0; return QN_OK;
+    case QN_OPT_PNORM_NONTEMPORAL:
+        if (value < -1 || value > 1) return fail(QN_ERROR_INPUT_PARAMS, "non-temporal loads of inverse_p: 0 (plain), 1 (non-temporal) or -1 (by size)");
+        s->pnorm_nt = value;
+        return QN_OK;
+    case QN_OPT_PNORM_ROWS_PER_WAVE:
+        if (value != 0 && value != 2 && value != 4) return fail(QN_ERROR_INPUT_PARAMS, "rows per wave of the p-norm direction kernel: 2, 4 or 0 (by size)");
+        s->pnorm_rw = value;
+        return QN_OK;
     case QN_OPT_TOUCH_H_ROWS:
     case QN_OPT_TOUCH_Q_ROWS:
         if (value != 0 && value != 4 && value != 6 && value != 8 && value != 10 && value != 12 && value != 16) return fail(QN_ERROR_INPUT_PARAMS, "rows per wave to touch: 0, 4, 6, 8, 10, 12 or 16");
@@ -806,6 +824,7 @@ extern "C" int qn_solver_compute_direction(qn_solver* s, const double* g_host, d
     if (s->method == QN_NEWTON) return fail(QN_ERROR_INPUT_PARAMS, "the Newton direction needs the oracle's Hessian: use qn_minimize");
     const size_t n = s->n;
     if (vec_method(s->method)) return vec_compute_direction(s, g_host, d_host);
+    if (steep_method(s->method)) return steep_compute_direction(s, g_host, d_host);
     if (!s->H) { // gradient descent
         for (size_t i = 0; i < n; ++i) d_host[i] = -g_host[i];
         return QN_OK;

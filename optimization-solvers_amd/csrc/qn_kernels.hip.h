@@ -94,6 +94,8 @@ struct QnVecs {
     const double *lb, *ub;   // solver bounds (BFGSB / DFPB / SR1B), n_pad entries, padding -inf / +inf
     const double *llb, *lub; // the bounded line search's own box
     const int* nfail; // Newton: set by the factorisation when the Hessian is not positive definite
+    const double* steep_part; // PnormDescent / CoordinateDescent: the direction kernel's shares, [3][steep_nshare] (qn_pnorm.hip.h)
+    int steep_nshare;
     int n, n_pad, rpr, world, hcs, qcs;
 };
 
@@ -519,6 +521,23 @@ __device__ __forceinline__ double ctl_block_fmax(double v, double* lds) {
     double t = -INFINITY;
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t = fmax(t, lds[w]);
     return t;
+}
+
+// (magnitude, index) over the workgroup with qn_argmax_take's rule (qn_pnorm.hip.h): every thread returns the winner
+__device__ __forceinline__ void qn_argmax_take(double& m, int& ix, const double m2, const int i2);
+__device__ __forceinline__ void ctl_block_argmax(double& m, int& ix, double* lds /* 32 */) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        const double m2 = __shfl_xor(m, off, 64);
+        const int i2 = __shfl_xor(ix, off, 64);
+        qn_argmax_take(m, ix, m2, i2);
+    }
+    __syncthreads();
+    if (lane == 0) { lds[2 * wave] = m; lds[2 * wave + 1] = (double)ix; }
+    __syncthreads();
+    m = lds[0]; ix = (int)lds[1];
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) qn_argmax_take(m, ix, lds[2 * w], (int)lds[2 * w + 1]);
 }
 
 __device__ __forceinline__ double hp_val(const QnVecs& V, int nrhs, int rhs, int i) {
@@ -948,6 +967,7 @@ __global__ __launch_bounds__(256) void lse_finish1_kernel(const QnLseArgs a, con
 }
 
 #include "qn_rank1.hip.h"
+#include "qn_pnorm.hip.h"
 #include "qn_fused.hip.h"
 #include "qn_sym.hip.h"
 #include "qn_newton.hip.h"

@@ -61,6 +61,8 @@ OPTIONS = {
     "touch_h_rows": 21,
     "touch_q_rows": 22,
     "pnewton_reuse_factor": 23,
+    "pnorm_nontemporal": 24,
+    "pnorm_rows_per_wave": 25,
 }
 OPT_GENERIC_KERNELS = 1
 OPT_DEFERRED_UPDATE_STEP = 2
@@ -85,6 +87,8 @@ OPT_EVAL_ZIGZAG = 20
 OPT_TOUCH_H_ROWS = 21
 OPT_TOUCH_Q_ROWS = 22
 OPT_PNEWTON_REUSE_FACTOR = 23
+OPT_PNORM_NONTEMPORAL = 24
+OPT_PNORM_ROWS_PER_WAVE = 25
 
 
 class SolverError(Exception):
@@ -384,6 +388,19 @@ class BackTracking(_LineSearch, _WolfeConditions):
     @classmethod
     def new(cls, c1, beta):
         return cls(c1, beta)
+
+
+class NoSearch(_LineSearch):
+    """nosearch.rs: `compute_step_len` returns 1.0 and never calls the oracle -- how the reference writes a pure Newton step.  Pairs with
+    GradientDescent, Newton, CoordinateDescent and PnormDescent (the solvers on the trait's default update hook)."""
+
+    def __init__(self):
+        self.s = A.LineSearchStruct()
+        A.lib().qn_nosearch_new(C.byref(self.s))
+
+    @classmethod
+    def new(cls):
+        return cls()
 
 
 class MoreThuenteB(MoreThuente):
@@ -771,6 +788,44 @@ class GradientDescent(_SolverBase):
     def has_converged(self, eval_x_k):
         g = eval_x_k.g() if isinstance(eval_x_k, FuncEvalMultivariate) else eval_x_k[1]
         return float(np.max(np.abs(g))) < self.tol()
+
+
+class CoordinateDescent(GradientDescent):
+    """steepest_descent/coordinate_descent.rs, as written: d = -e_p with p the first index of the largest |g_i| -- whatever the sign of g_p
+    (`-max_value.signum()` of a magnitude, coordinate_descent.rs:43)."""
+    METHOD = A.COORDINATE_DESCENT
+
+    def grad_tol(self):
+        return self.tol()
+
+
+class PnormDescent(GradientDescent):
+    """steepest_descent/pnorm_descent.rs: d = (-inverse_p) * g with a dense n x n matrix that never changes (any matrix: neither symmetry nor
+    definiteness is tested).  One read-only stream of the matrix per iteration on the GPU; `reset` keeps it."""
+    METHOD = A.PNORM_DESCENT
+
+    def __init__(self, grad_tol, x0, inverse_p, ctx=None):
+        super().__init__(grad_tol, x0, ctx)
+        if inverse_p is not None:  # (None: qn_solver_create alone; minimize then answers ErrorInputParams until set_inverse_p)
+            self.set_inverse_p(inverse_p)
+
+    def set_inverse_p(self, inverse_p):
+        p = np.asfortranarray(inverse_p, dtype=np.float64)
+        if p.shape != (self.n, self.n):
+            raise ErrorInputParams("inverse_p must be n x n")
+        _check(A.lib().qn_solver_set_inverse_p(self.h, p.ctypes.data_as(A.dp)))
+
+    @classmethod
+    def new(cls, grad_tol, x0, inverse_p, ctx=None):
+        return cls(grad_tol, x0, inverse_p, ctx)
+
+    def grad_tol(self):
+        return self.tol()
+
+    def inverse_p(self):
+        out = np.zeros((self.n, self.n), order="F")
+        _check(A.lib().qn_solver_get_inverse_p(self.h, out.ctypes.data_as(A.dp)))
+        return np.ascontiguousarray(out)
 
 
 class _BoundedBase(_SolverBase):

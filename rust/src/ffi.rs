@@ -18,6 +18,7 @@ pub const QN_LS_BACKTRACKING: i32 = 1;
 pub const QN_LS_MORETHUENTE_B: i32 = 2;
 pub const QN_LS_BACKTRACKING_B: i32 = 3;
 pub const QN_LS_GLL_QUADRATIC: i32 = 4;
+pub const QN_LS_NO_SEARCH: i32 = 5;
 
 pub const QN_ORACLE_HOST: i32 = 0;
 pub const QN_ORACLE_DEVICE_FN: i32 = 1;
@@ -33,6 +34,8 @@ pub const QN_PROJECTED_GRADIENT: c_int = 6;
 pub const QN_PROJECTED_NEWTON: c_int = 7;
 pub const QN_SPECTRAL_PROJECTED_NEWTON: c_int = 8;
 pub const QN_BROYDEN: c_int = 9;
+pub const QN_COORDINATE_DESCENT: c_int = 10;
+pub const QN_PNORM_DESCENT: c_int = 11;
 
 // qn_option (ABI 5): what rounds 1-5 selected through negative codes of qn_solver_set_tiling; value != 0 on, 0 off
 pub const QN_OPT_GENERIC_KERNELS: c_int = 1;
@@ -58,6 +61,8 @@ pub const QN_OPT_EVAL_ZIGZAG: c_int = 20;
 pub const QN_OPT_TOUCH_H_ROWS: c_int = 21;
 pub const QN_OPT_TOUCH_Q_ROWS: c_int = 22;
 pub const QN_OPT_PNEWTON_REUSE_FACTOR: c_int = 23;
+pub const QN_OPT_PNORM_NONTEMPORAL: c_int = 24;
+pub const QN_OPT_PNORM_ROWS_PER_WAVE: c_int = 25;
 
 pub const QN_UNIQUE_ID_BYTES: usize = 128;
 pub const QN_TRACE_LS_MODIFIED: i32 = 1 << 30;
@@ -70,6 +75,7 @@ pub const QN_PATH_TILES1: u32 = 32;
 pub const QN_PATH_VECTOR: u32 = 64;
 pub const QN_PATH_PNEWTON: u32 = 128;
 pub const QN_PATH_RANK1: u32 = 256;
+pub const QN_PATH_PNORM: u32 = 512;
 
 #[repr(C)] pub struct qn_context { _p: [u8; 0] }
 #[repr(C)] pub struct qn_solver { _p: [u8; 0] }
@@ -203,6 +209,7 @@ extern "C" {
     pub fn qn_backtracking_b_new(ls: *mut qn_linesearch, c1: f64, beta: f64, lower_bound_host: *const f64, upper_bound_host: *const f64);
     pub fn qn_linesearch_with_lower_bound(ls: *mut qn_linesearch, lower_bound_host: *const f64);
     pub fn qn_linesearch_with_upper_bound(ls: *mut qn_linesearch, upper_bound_host: *const f64);
+    pub fn qn_nosearch_new(ls: *mut qn_linesearch);
     pub fn qn_gll_quadratic_new(ls: *mut qn_linesearch, c1: f64, m: usize);
     pub fn qn_gll_quadratic_with_sigmas(ls: *mut qn_linesearch, sigma1: f64, sigma2: f64);
 
@@ -218,6 +225,8 @@ extern "C" {
     pub fn qn_solver_create(ctx: *mut qn_context, method: c_int, tol: f64, x0_host: *const f64, n: usize, out: *mut *mut qn_solver) -> c_int;
     pub fn qn_solver_destroy(s: *mut qn_solver);
     pub fn qn_solver_set_bounds(s: *mut qn_solver, lower_bound_host: *const f64, upper_bound_host: *const f64) -> c_int;
+    pub fn qn_solver_set_inverse_p(s: *mut qn_solver, p_colmajor_host: *const f64) -> c_int;
+    pub fn qn_solver_get_inverse_p(s: *mut qn_solver, out_colmajor_host: *mut f64) -> c_int;
     pub fn qn_solver_set_spg_lambdas(s: *mut qn_solver, lambda_min: f64, lambda_max: f64) -> c_int;
     pub fn qn_solver_spg_lambda(s: *mut qn_solver, out: *mut f64, is_some: *mut c_int) -> c_int;
     pub fn qn_solver_newton_factorisations(s: *mut qn_solver, out: *mut usize) -> c_int;

@@ -272,6 +272,27 @@ impl GpuGLLQuadratic {
     }
 }
 impl_line_search!(GpuGLLQuadratic);
+
+/// `NoSearch` (nosearch.rs): `compute_step_len` returns 1.0 and never calls the oracle.  On the device it pairs with
+/// `GpuGradientDescent`, `GpuCoordinateDescent`, `GpuPnormDescent` (and Newton): the solvers on the trait's default update hook.
+#[derive(Clone, Debug)]
+pub struct GpuNoSearch {
+    ls: qn_linesearch,
+}
+
+impl GpuNoSearch {
+    pub fn new() -> Self {
+        let mut ls = unsafe { std::mem::zeroed::<qn_linesearch>() };
+        unsafe { qn_nosearch_new(&mut ls) };
+        GpuNoSearch { ls }
+    }
+}
+impl Default for GpuNoSearch {
+    fn default() -> Self {
+        Self::new()
+    }
+}
+impl_line_search!(GpuNoSearch);
 impl SufficientDecreaseCondition for GpuGLLQuadratic {
     fn c1(&self) -> Floating {
         self.ls.c1
@@ -628,6 +649,41 @@ gpu_solver!(
     /// Drop-in for `GradientDescent` (steepest_descent/gradient_descent.rs:7-82); `tol` is its `grad_tol`.
     GpuGradientDescent, QN_GRADIENT_DESCENT, false
 );
+
+gpu_solver!(
+    /// Drop-in for `CoordinateDescent` (steepest_descent/coordinate_descent.rs), as written: d = -e_p with p the first index of the largest
+    /// |g_i| -- whatever the sign of g_p (`-max_value.signum()` of a magnitude, coordinate_descent.rs:43).  `tol` is its `grad_tol`.
+    GpuCoordinateDescent, QN_COORDINATE_DESCENT, false
+);
+gpu_solver!(
+    /// Drop-in for `PnormDescent` (steepest_descent/pnorm_descent.rs): `new(grad_tol, x0).with_inverse_p(&inverse_p)` stands for
+    /// `new(grad_tol, x0, inverse_p)`; d = (-inverse_p) * g, one read-only stream of the matrix per iteration on the GPU (QN_PATH_PNORM).
+    GpuPnormDescent, QN_PNORM_DESCENT, false
+);
+impl GpuPnormDescent {
+    /// The constructor's third argument (pnorm_descent.rs:20): any n x n matrix, kept by the solver for its whole life.
+    pub fn with_inverse_p(self, inverse_p: &DMatrix<Floating>) -> Self {
+        assert_eq!((inverse_p.nrows(), inverse_p.ncols()), (self.core.n, self.core.n), "inverse_p must be n x n");
+        let code = unsafe { qn_solver_set_inverse_p(self.core.h, inverse_p.as_ptr()) }; // column-major, like DMatrix
+        assert_eq!(code, QN_OK, "qn_solver_set_inverse_p: {}", last_error());
+        self
+    }
+    /// `inverse_p()` of derive_getters (pnorm_descent.rs:11-17), downloaded.
+    pub fn inverse_p(&self) -> DMatrix<Floating> {
+        let mut m = DMatrix::<Floating>::zeros(self.core.n, self.core.n);
+        let code = unsafe { qn_solver_get_inverse_p(self.core.h, m.as_mut_ptr()) };
+        assert_eq!(code, QN_OK, "qn_solver_get_inverse_p: {}", last_error());
+        m
+    }
+    pub fn grad_tol(&self) -> &Floating {
+        &self.core.tol
+    }
+}
+impl GpuCoordinateDescent {
+    pub fn grad_tol(&self) -> &Floating {
+        &self.core.tol
+    }
+}
 
 gpu_solver!(
     /// Drop-in for `ProjectedGradientDescent` (steepest_descent/projected_gradient_descent.rs): `new(grad_tol, x0).with_bounds(lb, ub)`
