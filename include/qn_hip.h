@@ -150,7 +150,9 @@ void qn_gll_quadratic_with_sigmas(qn_linesearch* ls, double sigma1, double sigma
 typedef int (*qn_host_oracle_fn)(void* user, const double* x_host, size_t n, double* f, double* g_host);
 /* device closure: enqueue work on `stream` that reads x_dev[0..n) and writes *f_dev and g_dev[0..n). */
 typedef int (*qn_device_oracle_fn)(void* user, void* stream, const double* x_dev, size_t n, double* f_dev, double* g_dev);
-/* Newton only: the Hessian part of the FuncEval (func_eval.rs:8,27-33) at x, column-major n x n (like DMatrix). */
+/* Newton only: the Hessian part of the FuncEval (func_eval.rs:8,27-33) at x, column-major n x n (like DMatrix).  QN_NEWTON takes its
+ * Hessian from this closure, from a device quadratic (its own matrix: one step) or from a device log-sum-exp objective (formed on the
+ * device at every x_k, once per iteration at the loop top whatever `memoize` says: qn_objective_hessian); a device closure has none. */
 typedef int (*qn_host_hessian_fn)(void* user, const double* x_host, size_t n, double* h_colmajor_host);
 
 typedef struct qn_objective qn_objective; /* a device-resident objective owned by the library */
@@ -169,7 +171,7 @@ typedef struct {
     qn_device_oracle_fn device_fn;
     void* device_user;
     qn_objective* objective;
-    qn_host_hessian_fn host_hessian_fn; /* Newton with a host closure; device objectives supply their own Hessian */
+    qn_host_hessian_fn host_hessian_fn; /* Newton with a host closure; device objectives (quadratic, log-sum-exp) supply their own Hessian */
 } qn_oracle;
 
 /* Built-in benchmark objective (build-defined): f = 1/2 x'Qx - b'x, g = Qx - b.
@@ -188,6 +190,12 @@ void qn_objective_destroy(qn_objective* obj);
 int qn_objective_eval(qn_objective* obj, const double* x_host, double* f, double* g_host);
 /* download rows [row0,row0+nrows) of this rank's matrix shard (row-major, n columns); rows outside the shard fail */
 int qn_objective_get_rows(qn_objective* obj, size_t row0, size_t nrows, double* out_host);
+/* the Hessian at a host point, column-major n x n like DMatrix: the `hessian()` part of a FuncEval (func_eval.rs:8,27-33) for a binding to
+ * attach after qn_minimize.  A quadratic returns Q (x is not read).  A log-sum-exp objective returns
+ * A' (diag(p) - p p') A + mu I, p = softmax(A x + c), formed on the device by the kernel QN_NEWTON runs (csrc/qn_lse_hess.hip.h): symmetric
+ * bit for bit, the same bits for the same x.  The n_pad x n_pad device matrix is allocated by the first call.  h_colmajor_host == NULL: the
+ * launches run and are waited for, nothing is downloaded.  One rank (a row-sharded context: QN_ERROR_INPUT_PARAMS). */
+int qn_objective_hessian(qn_objective* obj, const double* x_host, double* h_colmajor_host);
 
 /* ---------------------------------------------------------------------------------------------
  * Solvers: BFGS (bfgs.rs:4-127), DFP (dfp.rs), Broyden (broyden.rs), GradientDescent (gradient_descent.rs:7-82), Newton (newton/mod.rs).

@@ -192,6 +192,35 @@ class Quadratic {
         check(qn_objective_eval(h_, x.data(), &f, g.data()));
         return FuncEvalMultivariate(f, std::move(g));
     }
+    DVector hessian(const DVector& x) const { // column-major n x n: Q itself
+        DVector h(n_ * n_);
+        check(qn_objective_hessian(h_, x.data(), h.data()));
+        return h;
+    }
+};
+
+// a device-resident objective f = log sum_i exp(a_i'x + c_i) + mu/2 ||x||^2 (A is m x n row-major).  Newton forms its Hessian on the device.
+class LogSumExp {
+    qn_objective* h_ = nullptr;
+    size_t n_;
+  public:
+    LogSumExp(const DVector& a_rowmajor, const DVector& c, size_t n, Floating mu, Context& ctx = Context::default_context()) : n_(n) {
+        check(qn_logsumexp_create(ctx.handle(), c.size(), n, a_rowmajor.data(), c.data(), mu, &h_));
+    }
+    LogSumExp(const LogSumExp&) = delete;
+    ~LogSumExp() { qn_objective_destroy(h_); }
+    qn_objective* handle() const { return h_; }
+    FuncEvalMultivariate operator()(const DVector& x) const {
+        DVector g(n_);
+        Floating f = 0;
+        check(qn_objective_eval(h_, x.data(), &f, g.data()));
+        return FuncEvalMultivariate(f, std::move(g));
+    }
+    DVector hessian(const DVector& x) const { // column-major n x n, A'(diag(p) - p p')A + mu I from the device kernel
+        DVector h(n_ * n_);
+        check(qn_objective_hessian(h_, x.data(), h.data()));
+        return h;
+    }
 };
 
 template <int METHOD>
@@ -222,7 +251,12 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
     bool next_iterate_too_close() const { int v; check(qn_solver_next_iterate_too_close(h_, &v)); return v != 0; }                   // bfgs.rs:15-20
     bool gradient_next_iterate_too_close() const { int v; check(qn_solver_gradient_next_iterate_too_close(h_, &v)); return v != 0; } // bfgs.rs:21-26
     DVector approx_inv_hessian() const { DVector m(n_ * n_); check(qn_solver_get_inv_hessian(h_, m.data(), 1)); return m; }          // column-major, like DMatrix
+    std::optional<Floating> decrement_squared() const { Floating v; int some; check(qn_solver_decrement_squared(h_, &v, &some)); return some ? std::optional<Floating>(v) : std::nullopt; } // newton/mod.rs:10
     bool has_converged(const FuncEvalMultivariate& eval) const { // bfgs.rs:64-76 / gradient_descent.rs:46-53
+        if (METHOD == QN_NEWTON) { // newton/mod.rs:62-68: half the squared decrement of the last direction; false before the first
+            const std::optional<Floating> d = decrement_squared();
+            return d ? *d * 0.5 < tol() : false;
+        }
         if (METHOD == QN_GRADIENT_DESCENT || METHOD == QN_COORDINATE_DESCENT || METHOD == QN_PNORM_DESCENT) { // (pnorm_descent.rs:52-59, coordinate_descent.rs:61-68)
             Floating acc = -INFINITY;
             for (Floating v : eval.g()) acc = std::fmax(std::fabs(v), acc);
@@ -235,7 +269,8 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
     }
 
     // minimize with a host closure: the reference's exact oracle-call sequence (ls_solver.rs:66-111)
-    template <class LS, class Oracle>
+    // (a device objective is callable too: without the constraint a non-const Quadratic / LogSumExp lvalue would bind here, as a host closure)
+    template <class LS, class Oracle, class = std::enable_if_t<!std::is_same_v<std::decay_t<Oracle>, Quadratic> && !std::is_same_v<std::decay_t<Oracle>, LogSumExp>>>
     Result minimize(LS& line_search, Oracle&& oracle, size_t max_iter_solver, size_t max_iter_line_search,
                     std::optional<std::function<void(const Self&)>> callback = std::nullopt) {
         using OracleT = std::remove_reference_t<Oracle>;
@@ -250,7 +285,7 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
         };
         struct Cb { Self* me; std::function<void(const Self&)>* f; } cb{this, callback ? &*callback : nullptr};
         auto cb_tramp = [](void* user, qn_solver*) { Cb* c = static_cast<Cb*>(user); (*c->f)(*c->me); };
-        auto htramp = [](void* user, const double* x, size_t n, double* h) -> int { // the Hessian part of the FuncEval (projected Newton solvers)
+        auto htramp = [](void* user, const double* x, size_t n, double* h) -> int { // the Hessian part of the FuncEval (Newton and the projected Newton solvers)
             Ctx* c = static_cast<Ctx*>(user);
             DVector xv(x, x + n);
             FuncEvalMultivariate ev = (*c->o)(xv);
@@ -263,7 +298,7 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
         o.memoize = 0;
         o.host_fn = tramp;
         o.host_user = &octx;
-        if (METHOD == QN_PROJECTED_NEWTON || METHOD == QN_SPECTRAL_PROJECTED_NEWTON) o.host_hessian_fn = htramp;
+        if (METHOD == QN_NEWTON || METHOD == QN_PROJECTED_NEWTON || METHOD == QN_SPECTRAL_PROJECTED_NEWTON) o.host_hessian_fn = htramp;
         const int st = qn_minimize(h_, &line_search.ffi(), &o, max_iter_solver, max_iter_line_search,
                                    callback ? static_cast<qn_callback_fn>(cb_tramp) : nullptr, &cb);
         return make_result(st);
@@ -278,12 +313,23 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
         o.objective = objective.handle();
         return make_result(qn_minimize(h_, &line_search.ffi(), &o, max_iter_solver, max_iter_line_search, nullptr, nullptr));
     }
+    template <class LS>
+    Result minimize(LS& line_search, const LogSumExp& objective, size_t max_iter_solver, size_t max_iter_line_search) {
+        qn_oracle o{};
+        o.kind = QN_ORACLE_OBJECTIVE;
+        o.memoize = 1;
+        o.objective = objective.handle();
+        return make_result(qn_minimize(h_, &line_search.ffi(), &o, max_iter_solver, max_iter_line_search, nullptr, nullptr));
+    }
 };
 
 using BFGS = LineSearchSolver<QN_BFGS>;                       // quasi_newton/bfgs.rs
 using DFP = LineSearchSolver<QN_DFP>;                         // quasi_newton/dfp.rs
 using GradientDescent = LineSearchSolver<QN_GRADIENT_DESCENT>; // steepest_descent/gradient_descent.rs
 using Broyden = LineSearchSolver<QN_BROYDEN>;                 // quasi_newton/broyden.rs
+// newton/mod.rs: d = -H^-1 g.  The closure returns FuncEvalMultivariate(f, g).with_hessian(h), or the oracle is a device objective: a Quadratic
+// (its own matrix) or a LogSumExp (the Hessian formed on the device at every x_k).
+using Newton = LineSearchSolver<QN_NEWTON>;
 
 using CoordinateDescent = LineSearchSolver<QN_COORDINATE_DESCENT>; // steepest_descent/coordinate_descent.rs: d = -e_p, p the first index of the largest |g_i|
 

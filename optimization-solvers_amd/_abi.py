@@ -108,6 +108,7 @@ SYMBOLS = [
     ("qn_objective_destroy", None, [C.c_void_p]),
     ("qn_objective_eval", C.c_int, [C.c_void_p, dp, dp, dp]),
     ("qn_objective_get_rows", C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, dp]),
+    ("qn_objective_hessian", C.c_int, [C.c_void_p, dp, dp]),
     ("qn_solver_create", C.c_int, [C.c_void_p, C.c_int, C.c_double, dp, C.c_size_t, C.POINTER(C.c_void_p)]),
     ("qn_solver_destroy", None, [C.c_void_p]),
     ("qn_solver_reset", C.c_int, [C.c_void_p, dp]),

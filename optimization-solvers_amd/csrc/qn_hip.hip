@@ -64,3 +64,5 @@ extern "C" const char* qn_status_string(int status) {
 // the first-order family (SPG, projected gradient, GLLQuadratic): its kernels are defined behind every existing one
 #include "qn_vec.hip.h"
 #include "qn_host_vec.hip.h"
+// the log-sum-exp Hessian (Newton on a device log-sum-exp objective): again behind every existing kernel
+#include "qn_lse_hess.hip.h"

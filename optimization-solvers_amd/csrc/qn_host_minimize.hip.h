@@ -44,7 +44,7 @@ static int plan_run(Run& r, qn_solver* s, qn_linesearch* ls, const qn_oracle* o,
     }
     if (s->method == QN_NEWTON) {
         if (c->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "Newton is single-GPU (SURVEY.md 8(f) row f2)");
-        if (!(r.obj && r.obj->kind == OBJ_QUADRATIC) && !(o->kind == QN_ORACLE_HOST && o->host_hessian_fn))
+        if (!(r.obj && (r.obj->kind == OBJ_QUADRATIC || r.obj->kind == OBJ_LOGSUMEXP)) && !(o->kind == QN_ORACLE_HOST && o->host_hessian_fn))
             return fail(QN_ERROR_INPUT_PARAMS, "Hessian not available in the oracle"); // newton/mod.rs:34 .expect(...)
         QNCHK(newton_alloc(s));
     }

@@ -379,14 +379,21 @@ static int enqueue_newton_lu(qn_solver* s, const double* hsrc, size_t ld_src) {
     return QN_OK;
 }
 
-// The Hessian at x_k on the device, row-major: a device objective's own matrix, or the host closure's (uploaded).  `symmetric`: H == H' bit for bit.
+// The Hessian at x_k on the device, row-major: a device quadratic's own matrix, a device log-sum-exp objective's (formed at x_k by
+// lse_hess_kernel, on the solver's stream), or the host closure's (uploaded).  `symmetric`: H == H' bit for bit.
 static int newton_stage_hessian(qn_solver* s, const qn_oracle* o, qn_objective* obj, const double** hsrc_out, size_t* ld_src_out, bool* symmetric_out) {
     hipStream_t st = s->ctx->stream;
     const int n = (int)s->n;
     const double* hsrc = nullptr;
     size_t ld_src = 0;
     bool symmetric = true; // the Cholesky path reads the lower triangle only: it needs H == H' bit for bit
-    if (obj) { hsrc = obj->Q; ld_src = (size_t)obj->T.n_pad; symmetric = obj->q_symmetric; }
+    if (obj && obj->kind == OBJ_LOGSUMEXP) { // (the mirrored store of lse_hess_kernel: symmetric by construction)
+        const size_t np = (size_t)obj->T.n_pad;
+        QNCHK(s->newton_hsrc.ensure(np * np));
+        QNCHK(lse_enqueue_hessian(obj, s->V.x, s->newton_hsrc, np));
+        s->stats.launches += 5;
+        hsrc = s->newton_hsrc; ld_src = np;
+    } else if (obj) { hsrc = obj->Q; ld_src = (size_t)obj->T.n_pad; symmetric = obj->q_symmetric; }
     else {
         QNCHK(s->newton_hsrc.ensure((size_t)n * n));
         s->newton_hhost.resize((size_t)n * n * 2);

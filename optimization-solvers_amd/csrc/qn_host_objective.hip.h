@@ -16,6 +16,7 @@ struct qn_objective {
     bool q_symmetric = true; // quadratic: Q == Q' bit for bit (checked at creation); the symmetric-storage evaluation needs it
     // scratch for qn_objective_eval
     DevBuf<double> ex, eq, eg, ef;
+    DevBuf<double> eh; // qn_objective_hessian: the n_pad x n_pad matrix on the device (allocated by the first call)
     // log-sum-exp: A rows are in Q ([mrpr][n_pad]), c in b (m_pad)
     size_t m = 0;
     QnTile TA{}; // row partition of A (m rows)
@@ -145,6 +146,34 @@ static int lse_launch_onepass(hipStream_t st, int G, const QnLseArgs& a, double*
     return nt ? lse_launch_onepass_nt<KCH, true>(st, G, a, wgms, wgg) : lse_launch_onepass_nt<KCH, false>(st, G, a, wgms, wgg);
 }
 
+// the first launches of the two-pass evaluation at x_dev: z = A_rows x, the softmax weights NORMALISED into `lw` (zero past row m), this rank's
+// column sums A'w into its block of `lgall`, f's terms into `lscal` -- what lse_finish_kernel needs, and what the Hessian needs (p and gbar)
+static int lse_enqueue_weights(qn_objective* o, const double* x_dev, QnLseArgs& a) {
+    qn_context* c = o->ctx;
+    hipStream_t st = c->stream;
+    // pass 1: z = A_rows x (the H-pass kernel in plain mat-vec mode)
+    QnHPassArgs h{};
+    h.H = o->Q; h.T = o->TA; h.T.n_pad = o->T.n_pad; h.T.n = (int)o->n; h.T.cs = 1;
+    h.T.rpr = o->TA.rpr; h.T.row_off = 0; // row guards are not needed for a read-only pass
+    h.hp = o->lz; h.expect_phase = -1; h.force_nrhs = 1; h.force_pending = 0; h.r0 = x_dev; h.r1 = x_dev;
+    h.sp = x_dev; h.up = x_dev;
+    launch_hpass<8>(st, h);
+    HIPCHK(hipGetLastError());
+    c->n_xchg_vector++;
+    QNCHK(exchange(c, o->lz, 2 * (size_t)o->TA.rpr));
+    a = QnLseArgs{};
+    a.A = o->Q; a.c = o->b; a.z = o->lz; a.w = o->lw; a.gpart = o->lgpart; a.gall = o->lgall; a.x = x_dev;
+    a.scal = o->lscal; a.mu = o->mu;
+    a.m = (int)o->m; a.m_pad = o->TA.n_pad; a.mrpr = o->TA.rpr; a.n = (int)o->n; a.n_pad = o->T.n_pad;
+    a.world = c->world; a.rank = c->rank; a.rs = o->lse_rs;
+    hipLaunchKernelGGL(lse_softmax_kernel, dim3(1), dim3(1024), 0, st, a);
+    // pass 2: column sums A'w over this rank's rows
+    hipLaunchKernelGGL(lse_colsum_kernel, dim3((a.n_pad + QN_CHUNK - 1) / QN_CHUNK, a.rs), dim3(QN_TPB), 0, st, a);
+    hipLaunchKernelGGL(lse_reduce_splits_kernel, dim3(std::min(1024, (a.n_pad + 255) / 256)), dim3(256), 0, st, a);
+    HIPCHK(hipGetLastError());
+    return QN_OK;
+}
+
 static int lse_enqueue_eval(qn_objective* o, const double* x_dev, double* f_dev, double* g_dev) {
     qn_context* c = o->ctx;
     hipStream_t st = c->stream;
@@ -171,31 +200,24 @@ static int lse_enqueue_eval(qn_objective* o, const double* x_dev, double* f_dev,
         HIPCHK(hipGetLastError());
         return QN_OK;
     }
-    // pass 1: z = A_rows x (the H-pass kernel in plain mat-vec mode)
-    QnHPassArgs h{};
-    h.H = o->Q; h.T = o->TA; h.T.n_pad = o->T.n_pad; h.T.n = (int)o->n; h.T.cs = 1;
-    h.T.rpr = o->TA.rpr; h.T.row_off = 0; // row guards are not needed for a read-only pass
-    h.hp = o->lz; h.expect_phase = -1; h.force_nrhs = 1; h.force_pending = 0; h.r0 = x_dev; h.r1 = x_dev;
-    h.sp = x_dev; h.up = x_dev;
-    launch_hpass<8>(st, h);
-    HIPCHK(hipGetLastError());
-    c->n_xchg_vector++;
-    QNCHK(exchange(c, o->lz, 2 * (size_t)o->TA.rpr));
     QnLseArgs a{};
-    a.A = o->Q; a.c = o->b; a.z = o->lz; a.w = o->lw; a.gpart = o->lgpart; a.gall = o->lgall; a.x = x_dev;
-    a.f_out = f_dev; a.g_out = g_dev; a.scal = o->lscal; a.mu = o->mu;
-    a.m = (int)o->m; a.m_pad = o->TA.n_pad; a.mrpr = o->TA.rpr; a.n = (int)o->n; a.n_pad = o->T.n_pad;
-    a.world = c->world; a.rank = c->rank; a.rs = o->lse_rs;
-    hipLaunchKernelGGL(lse_softmax_kernel, dim3(1), dim3(1024), 0, st, a);
-    // pass 2: column sums A'w over this rank's rows
-    hipLaunchKernelGGL(lse_colsum_kernel, dim3((a.n_pad + QN_CHUNK - 1) / QN_CHUNK, a.rs), dim3(QN_TPB), 0, st, a);
-    hipLaunchKernelGGL(lse_reduce_splits_kernel, dim3(std::min(1024, (a.n_pad + 255) / 256)), dim3(256), 0, st, a);
-    HIPCHK(hipGetLastError());
+    QNCHK(lse_enqueue_weights(o, x_dev, a));
+    a.f_out = f_dev; a.g_out = g_dev;
     c->n_xchg_vector++;
     QNCHK(exchange(c, o->lgall, (size_t)a.n_pad));
     hipLaunchKernelGGL(lse_finish_kernel, dim3(std::min(1024, (a.n_pad + 255) / 256)), dim3(256), 0, st, a);
     HIPCHK(hipGetLastError());
     return QN_OK;
+}
+
+// enqueue the Hessian of the log-sum-exp objective at x_dev (n_pad entries) into h_dev: n_pad x n_pad, row-major with leading dimension ld,
+// H == H' bit for bit (qn_lse_hess.hip.h).  One rank; everything on the context's stream, no host synchronisation.
+static int lse_hess_launch(hipStream_t st, const double* A, const double* p, const double* gbar, double mu, int m, int np, double* H, size_t ld);
+static int lse_enqueue_hessian(qn_objective* o, const double* x_dev, double* h_dev, size_t ld) {
+    if (o->ctx->world != 1) return fail(QN_ERROR_INPUT_PARAMS, "the log-sum-exp Hessian is single-GPU");
+    QnLseArgs a{};
+    QNCHK(lse_enqueue_weights(o, x_dev, a)); // p -> lw, gbar -> lgall (rank 0's block is the whole sum on one rank)
+    return lse_hess_launch(o->ctx->stream, o->Q, o->lw, o->lgall, o->mu, (int)o->m, o->T.n_pad, h_dev, ld);
 }
 
 extern "C" void qn_objective_destroy(qn_objective* o) {
@@ -277,5 +299,32 @@ extern "C" int qn_objective_eval(qn_objective* o, const double* x_host, double* 
     HIPCHK(hipMemcpyAsync(f, o->ef, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipMemcpyAsync(g_host, o->eg, o->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
+    return QN_OK;
+}
+
+extern "C" int qn_objective_hessian(qn_objective* o, const double* x_host, double* h_colmajor_host) {
+    if (!o || !x_host) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
+    qn_context* c = o->ctx;
+    if (c->world != 1) return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hessian is single-GPU");
+    HIPCHK(hipSetDevice(c->device));
+    const size_t n = o->n, np = o->T.n_pad;
+    if (o->kind == OBJ_QUADRATIC) { // Q itself, whatever x is
+        if (!h_colmajor_host) return QN_OK;
+        std::vector<double> rows(n * n);
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipMemcpy2D(rows.data(), n * sizeof(double), o->Q, np * sizeof(double), n * sizeof(double), n, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n; ++i)
+            for (size_t j = 0; j < n; ++j) h_colmajor_host[i + j * n] = rows[i * n + j];
+        return QN_OK;
+    }
+    if (o->kind != OBJ_LOGSUMEXP) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
+    QNCHK(o->ex.ensure(2 * np, c->stream));
+    QNCHK(o->eh.ensure(np * np));
+    HIPCHK(hipMemcpyAsync(o->ex, x_host, n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    QNCHK(lse_enqueue_hessian(o, o->ex, o->eh, np));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (!h_colmajor_host) return QN_OK; // (the launches alone: what tools/bench_lse_hessian.py times)
+    // H == H' bit for bit: its rows are its columns
+    HIPCHK(hipMemcpy2D(h_colmajor_host, n * sizeof(double), o->eh, np * sizeof(double), n * sizeof(double), n, hipMemcpyDeviceToHost));
     return QN_OK;
 }

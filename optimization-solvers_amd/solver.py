@@ -481,6 +481,19 @@ class Objective:
         _check(A.lib().qn_objective_eval(self.h, _dp(x), C.byref(f), _dp(g)))
         return FuncEvalMultivariate(f.value, g)
 
+    def hessian(self, x, download=True):
+        """The Hessian at x, n x n (`FuncEval::hessian()`): Q for a quadratic; for LogSumExp the matrix the device kernel forms for Newton.
+        download=False: the launches run and are waited for, nothing comes back (timing)."""
+        x = _f64(x)
+        if x.size != self.n:
+            raise ErrorInputParams(f"x has {x.size} entries, the objective has {self.n}")
+        if not download:
+            _check(A.lib().qn_objective_hessian(self.h, _dp(x), None))
+            return None
+        out = np.empty((self.n, self.n), order="F")
+        _check(A.lib().qn_objective_hessian(self.h, _dp(x), out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
     def rows(self, row0, nrows):
         out = np.empty((nrows, self.n))
         _check(A.lib().qn_objective_get_rows(self.h, row0, nrows, _dp(out)))

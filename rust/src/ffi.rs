@@ -220,6 +220,7 @@ extern "C" {
     pub fn qn_objective_destroy(obj: *mut qn_objective);
     pub fn qn_objective_eval(obj: *mut qn_objective, x_host: *const f64, f: *mut f64, g_host: *mut f64) -> c_int;
     pub fn qn_objective_get_rows(obj: *mut qn_objective, row0: usize, nrows: usize, out_host: *mut f64) -> c_int;
+    pub fn qn_objective_hessian(obj: *mut qn_objective, x_host: *const f64, h_colmajor_host: *mut f64) -> c_int;
 
     // ---- solvers ----
     pub fn qn_solver_create(ctx: *mut qn_context, method: c_int, tol: f64, x0_host: *const f64, n: usize, out: *mut *mut qn_solver) -> c_int;

@@ -357,6 +357,16 @@ impl DeviceObjective {
         status_to_result(unsafe { qn_objective_eval(self.h, x.as_ptr(), &mut f, g.as_mut_ptr()) })?;
         Ok(FuncEvalMultivariate::new(f, g))
     }
+    /// The Hessian at a host point (`FuncEvalMultivariate::hessian()` after `minimize`): Q for a quadratic, for log-sum-exp the matrix
+    /// the device kernel forms for `GpuNewton` (A'(diag(p) - p p')A + mu I, symmetric bit for bit).
+    pub fn hessian(&self, x: &DVector<Floating>) -> Result<DMatrix<Floating>, SolverError> {
+        if x.len() != self.n {
+            return Err(SolverError::ErrorInputParams);
+        }
+        let mut m = DMatrix::<Floating>::zeros(self.n, self.n);
+        status_to_result(unsafe { qn_objective_hessian(self.h, x.as_ptr(), m.as_mut_ptr()) })?; // column-major, like DMatrix
+        Ok(m)
+    }
 }
 
 impl Drop for DeviceObjective {
@@ -513,7 +523,7 @@ macro_rules! gpu_solver {
                         f(&*env.me)
                     }
                 }
-                let o = host_oracle(&mut oracle, false, $method == QN_PROJECTED_NEWTON || $method == QN_SPECTRAL_PROJECTED_NEWTON);
+                let o = host_oracle(&mut oracle, false, $method == QN_NEWTON || $method == QN_PROJECTED_NEWTON || $method == QN_SPECTRAL_PROJECTED_NEWTON);
                 let has_callback = callback.is_some();
                 let mut env = CallbackEnv { me: self as *mut $name, f: &mut callback };
                 let core = &mut self.core as *mut Core; // (`env.me` aliases self for the duration of the call)
@@ -650,6 +660,12 @@ gpu_solver!(
     GpuGradientDescent, QN_GRADIENT_DESCENT, false
 );
 
+gpu_solver!(
+    /// Drop-in for `Newton` (newton/mod.rs:8-69): d = -H^-1 g from a blocked Cholesky on the f64 matrix cores (a pivoted LU when the Hessian is not
+    /// positive definite).  The closure's `FuncEvalMultivariate` carries the Hessian (`with_hessian`), or the oracle is a device objective
+    /// (`minimize_objective`): a quadratic's own matrix, or the log-sum-exp Hessian formed on the device at every x_k.
+    GpuNewton, QN_NEWTON, false
+);
 gpu_solver!(
     /// Drop-in for `CoordinateDescent` (steepest_descent/coordinate_descent.rs), as written: d = -e_p with p the first index of the largest
     /// |g_i| -- whatever the sign of g_p (`-max_value.signum()` of a magnitude, coordinate_descent.rs:43).  `tol` is its `grad_tol`.
