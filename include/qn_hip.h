@@ -244,7 +244,22 @@ enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton
         * one: QN_ERROR_INPUT_PARAMS).  ONE read-only stream of the matrix per iteration -- 8 n^2 bytes, csrc/qn_pnorm.hip.h (QN_PATH_PNORM) -- whose launch
         * also leaves g.d and ||g||_inf; n <= 5: the reference's literal column sweep.  h_passes / h_bytes of qn_stats count those streams. */
        QN_COORDINATE_DESCENT = 10 /* CoordinateDescent, steepest_descent/coordinate_descent.rs */,
-       QN_PNORM_DESCENT = 11 /* PnormDescent, steepest_descent/pnorm_descent.rs */ };
+       QN_PNORM_DESCENT = 11 /* PnormDescent, steepest_descent/pnorm_descent.rs */,
+       /* Limited-memory BFGS (ProjectedLBFGS once qn_solver_set_bounds is called): the quasi-Newton method whose state is O(m n) and not O(n^2) -- the last
+        * m pairs (s, y), m = 5 by default as Lbfgsb::new (quasi_newton/lbfgsb.rs:91), 1 <= m <= QN_LBFGS_MAX_M (qn_solver_set_lbfgs_memory).  It runs on the
+        * first-order family's machine (QN_PATH_VECTOR | QN_PATH_LBFGS) and takes that family's line searches (QN_LS_GLL_QUADRATIC, QN_LS_BACKTRACKING,
+        * QN_LS_BACKTRACKING_B; More-Thuente: QN_ERROR_INPUT_PARAMS), box, loop top (||projected gradient||_inf < tol; no s_norm / y_norm tests), trace
+        * (gnorm = that norm, s_norm = ||s||, updated = the pair was committed), callbacks and warm restarts (the memory survives calls; qn_solver_reset
+        * empties it); every oracle kind, memoize 0 / 1, one rank.  The direction is d = P(x - z) - x with z = H_k g from the COMPACT FORM of Byrd, Nocedal
+        * and Schnabel (1994): two streams of the memory and one small solve per iteration (csrc/qn_lbfgs.hip.h), gamma = s_k.y_k / y_k.y_k
+        * (QN_OPT_LBFGS_UNIT_SCALING: gamma = 1).  A pair is kept only when s.y > DBL_EPSILON y.y; when g.z <= 0 or is not finite the memory is cleared
+        * and z = g (counted: qn_solver_lbfgs_state).  Profiling mode times this method's three direction launches apart: t_hpass_ms = the Gram kernel, t_hreduce_ms = the
+        * apply kernel, t_ereduce_ms = vec_dir_kernel on z.  y needs the gradient at the accepted point: the oracle is called there as for QN_SPG.
+        * THIS IS NOT THE REFERENCE'S `Lbfgsb` (an optional binding to the Fortran L-BFGS-B library): there is no generalised Cauchy point and no
+        * subspace minimisation.  The bounded variant follows this library's own BFGSB convention, d = P(x - H g) - x (bfgs_b.rs:72-75); with an active
+        * box that direction is no more guaranteed to descend than BFGSB's is.  qn_solver_compute_direction: QN_ERROR_INPUT_PARAMS (use qn_minimize). */
+       QN_LBFGS = 12 /* limited-memory BFGS; no counterpart in the reference's default feature set */ };
+#define QN_LBFGS_MAX_M 32
 typedef struct qn_solver qn_solver;
 
 /* BFGS::new(tol, x0) / DFP::new / GradientDescent::new(grad_tol, x0): H = I (no identity copy is kept) */
@@ -265,6 +280,12 @@ int qn_solver_spg_lambda(qn_solver* s, double* out, int* is_some);
  * (The count comes back through a size_t*, like every other count in this header, and not through a uint64_t*: the ABI check that compares this
  * header with the Python and Rust mirrors knows the pointer types the header already used.  Both are 64 bits wide on every platform ROCm runs on.) */
 int qn_solver_newton_factorisations(qn_solver* s, size_t* out);
+/* QN_LBFGS: the memory m (pairs kept at most; 5 after qn_solver_create).  Outside 1 .. QN_LBFGS_MAX_M, or on another method: QN_ERROR_INPUT_PARAMS.
+ * The stored pairs are dropped.  The vectors -- 2 (m + 1) n_pad doubles -- are allocated by the next qn_minimize. */
+int qn_solver_set_lbfgs_memory(qn_solver* s, size_t m);
+/* QN_LBFGS: m, the pairs stored now, the scaling gamma of the last direction (1 before the first pair), and how often the safeguard g.z > 0 has
+ * cleared the memory since qn_solver_create / qn_solver_reset.  Any pointer may be NULL.  Other methods: QN_ERROR_INPUT_PARAMS. */
+int qn_solver_lbfgs_state(qn_solver* s, size_t* m, size_t* stored, double* gamma, size_t* resets);
 /* QN_PNORM_DESCENT: inverse_p of PnormDescent::new(grad_tol, x0, inverse_p) (pnorm_descent.rs:20-27) and its getter; column-major n x n, like DMatrix
  * and like qn_solver_set_inv_hessian.  ANY matrix is accepted: the reference tests neither symmetry nor definiteness.  It is a constructor argument,
  * not state: qn_solver_reset keeps it.  Other methods: QN_ERROR_INPUT_PARAMS. */
@@ -373,6 +394,7 @@ typedef struct {
 #define QN_PATH_PNEWTON 128u   /* ... with the direction from a Cholesky solve: QN_PROJECTED_NEWTON, QN_SPECTRAL_PROJECTED_NEWTON (set beside QN_PATH_VECTOR) */
 #define QN_PATH_RANK1 256u     /* QN_BROYDEN's H passes: the square-tile kernel of csrc/qn_rank1.hip.h (non-symmetric rank-1 update, row AND column sums in one stream of H) */
 #define QN_PATH_PNORM 512u     /* QN_PNORM_DESCENT's directions: pnorm_dir_kernel of csrc/qn_pnorm.hip.h (one read-only stream of inverse_p, with g.d and ||g||_inf in the same launch) */
+#define QN_PATH_LBFGS 1024u    /* QN_LBFGS: the direction from the compact form of L-BFGS, two streams of the memory per iteration (csrc/qn_lbfgs.hip.h); set beside QN_PATH_VECTOR */
 int qn_solver_get_stats(qn_solver* s, qn_stats* out);
 /* profiling != 0: bracket every launch with HIP events on the solver's stream (slower; for roofline reports) */
 int qn_solver_set_profiling(qn_solver* s, int on);
@@ -410,7 +432,8 @@ typedef enum {
     QN_OPT_TOUCH_Q_ROWS = 22,              /* [6] ... and the update-reduce launch for the evaluation launch behind it (rows of Q's tiles) */
     QN_OPT_PNEWTON_REUSE_FACTOR = 23,      /* [1] ProjectedNewton / SpectralProjectedNewton on a device quadratic: the Hessian's Cholesky factor is kept between iterations (the matrix does not change); 0: factorise in every iteration -- the same bits */
     QN_OPT_PNORM_NONTEMPORAL = 24,         /* [-1] PnormDescent: inverse_p through non-temporal loads; 1 / 0 force it on / off, -1 (a NUMBER): by size -- on once the matrix is past the Infinity Cache's reach (~230 MB, n ~ 5400) -- the same bits */
-    QN_OPT_PNORM_ROWS_PER_WAVE = 25        /* [0] ... rows a wave of its direction kernel holds in flight: 2 or 4 (a NUMBER); 0: by size (2 up to n = 8192) -- the same bits */
+    QN_OPT_PNORM_ROWS_PER_WAVE = 25,       /* [0] ... rows a wave of its direction kernel holds in flight: 2 or 4 (a NUMBER); 0: by size (2 up to n = 8192) -- the same bits */
+    QN_OPT_LBFGS_UNIT_SCALING = 26         /* [0] L-BFGS: gamma = 1 in every iteration (H0 = I): the iterates of dense BFGS from H = I while no pair has been dropped */
 } qn_option;
 int qn_solver_set_option(qn_solver* s, int option, int value);
 

@@ -460,4 +460,27 @@ class SpectralProjectedNewton : public ProjectedSolver<QN_SPECTRAL_PROJECTED_NEW
     size_t newton_factorisations() const { size_t v = 0; check(qn_solver_newton_factorisations(this->handle(), &v)); return v; }
 };
 
+// Limited-memory BFGS in a box: new(tol, x0, lower_bound, upper_bound).with_memory(m); d = P(x - H_k g) - x, H_k g from the last m pairs (s, y) by the
+// compact form (two streams of the memory and one small solve per iteration on the GPU).  NOT the reference's Fortran-backed Lbfgsb: no generalised
+// Cauchy point, no subspace minimisation -- the bounded variant follows BFGSB's convention (bfgs_b.rs:72-75).
+class ProjectedLBFGS : public ProjectedSolver<QN_LBFGS> {
+  public:
+    using ProjectedSolver<QN_LBFGS>::ProjectedSolver;
+    static ProjectedLBFGS new_(Floating tol, const DVector& x0, DVector lb, DVector ub) { return ProjectedLBFGS(tol, x0, std::move(lb), std::move(ub)); }
+    ProjectedLBFGS with_memory(size_t m) && { check(qn_solver_set_lbfgs_memory(this->handle(), m)); return std::move(*this); }
+    size_t memory() const { size_t v = 0; check(qn_solver_lbfgs_state(this->handle(), &v, nullptr, nullptr, nullptr)); return v; }
+    size_t stored_pairs() const { size_t v = 0; check(qn_solver_lbfgs_state(this->handle(), nullptr, &v, nullptr, nullptr)); return v; }
+    Floating gamma() const { Floating v = 0; check(qn_solver_lbfgs_state(this->handle(), nullptr, nullptr, &v, nullptr)); return v; }
+    size_t resets() const { size_t v = 0; check(qn_solver_lbfgs_state(this->handle(), nullptr, nullptr, nullptr, &v)); return v; }
+};
+
+// Limited-memory BFGS: new(tol, x0).with_memory(m); d = -H_k g.  The same solver with the box left at (-inf, +inf).
+class LBFGS : public ProjectedLBFGS {
+  public:
+    LBFGS(Floating tol, const DVector& x0, Context& ctx = Context::default_context())
+        : ProjectedLBFGS(tol, x0, DVector(x0.size(), -INFINITY), DVector(x0.size(), INFINITY), ctx) {}
+    static LBFGS new_(Floating tol, const DVector& x0) { return LBFGS(tol, x0); }
+    LBFGS with_memory(size_t m) && { check(qn_solver_set_lbfgs_memory(this->handle(), m)); return std::move(*this); }
+};
+
 } // namespace optimization_solvers

@@ -13,6 +13,8 @@ ORACLE_HOST, ORACLE_DEVICE_FN, ORACLE_OBJECTIVE = 0, 1, 2
 BFGS, DFP, GRADIENT_DESCENT, NEWTON, SR1, SPG, PROJECTED_GRADIENT, PROJECTED_NEWTON, SPECTRAL_PROJECTED_NEWTON = 0, 1, 2, 3, 4, 5, 6, 7, 8
 BROYDEN = 9  # quasi_newton/broyden.rs (BroydenB once bounds are set)
 COORDINATE_DESCENT, PNORM_DESCENT = 10, 11  # steepest_descent/coordinate_descent.rs, pnorm_descent.rs
+LBFGS = 12  # limited-memory BFGS (ProjectedLBFGS once bounds are set); not the reference's Fortran-backed Lbfgsb
+LBFGS_MAX_M = 32
 UNIQUE_ID_BYTES = 128
 
 dp = C.POINTER(C.c_double)
@@ -63,6 +65,7 @@ class Stats(C.Structure):
 PATH_FUSED, PATH_SYM, PATH_SYM_GENERIC, PATH_PIPELINED, PATH_SYM2, PATH_TILES1, PATH_VECTOR, PATH_PNEWTON = 1, 2, 4, 8, 16, 32, 64, 128
 PATH_RANK1 = 256
 PATH_PNORM = 512
+PATH_LBFGS = 1024
 
 
 # every symbol include/qn_hip.h declares: (name, restype, argtypes)
@@ -118,6 +121,8 @@ SYMBOLS = [
     ("qn_solver_set_spg_lambdas", C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     ("qn_solver_spg_lambda", C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int)]),
     ("qn_solver_newton_factorisations", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
+    ("qn_solver_set_lbfgs_memory", C.c_int, [C.c_void_p, C.c_size_t]),
+    ("qn_solver_lbfgs_state", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), dp, C.POINTER(C.c_size_t)]),
     ("qn_minimize", C.c_int, [C.c_void_p, C.POINTER(LineSearchStruct), C.POINTER(OracleStruct), C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("qn_compute_step_len", C.c_int, [C.c_void_p, C.POINTER(LineSearchStruct), dp, C.c_double, dp, dp, C.c_size_t, C.POINTER(OracleStruct), C.c_size_t,
                              C.POINTER(C.c_double)]),

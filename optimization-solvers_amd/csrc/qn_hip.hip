@@ -66,3 +66,6 @@ extern "C" const char* qn_status_string(int status) {
 #include "qn_host_vec.hip.h"
 // the log-sum-exp Hessian (Newton on a device log-sum-exp objective): again behind every existing kernel
 #include "qn_lse_hess.hip.h"
+// limited-memory BFGS on the first-order family's machine: the two streaming kernels of its compact form, behind every existing kernel
+#include "qn_lbfgs.hip.h"
+#include "qn_host_lbfgs.hip.h"

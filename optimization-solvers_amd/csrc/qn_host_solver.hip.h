@@ -109,6 +109,7 @@ struct qn_solver {
     uint64_t pn_factor_serial = 0;
     int pn_reuse = 1;
     uint64_t pn_factorisations = 0;
+    DevBuf<double> lb_ring, lb_part, lb_small; // QN_LBFGS (qn_lbfgs.hip.h): S and Y, [2][lb_m + 1][n_pad]; the Gram kernel's shares; Gram matrices and coefficients
     DevBuf<double> bounds_block; // lb, ub (solver), llb, lub (bounded line search): 4 n_pad vectors
     int bounded = 0;
     DevBuf<double> fused_block; // X0[2], S0[2], G, GT, Y, UN, UP, VV (10 n_pad vectors)
@@ -361,6 +362,7 @@ static int solver_alloc_sym2(qn_solver* s) {
 
 static bool vec_method(int method);
 static int vec_state_alloc(qn_solver* s);
+static int lbfgs_set_unit_scaling(qn_solver* s, bool on); // QN_LBFGS: qn_host_lbfgs.hip.h
 static void vec_state_reset(qn_solver* s);
 static int vec_compute_direction(qn_solver* s, const double* g_host, double* d_host);
 static int bounds_alloc(qn_solver* s);
@@ -386,7 +388,7 @@ extern "C" int qn_solver_create(qn_context* ctx, int method, double tol, const d
         return fail(QN_ERROR_INPUT_PARAMS, "unknown method");
     if (steep_method(method) && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "CoordinateDescent / PnormDescent run on one rank");
     if (method == QN_BROYDEN && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "Broyden runs on one rank: its non-symmetric H needs column sums, which a row-sharded context (world > 1) does not have");
-    if (vec_method(method) && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient / projected Newton run on one rank");
+    if (vec_method(method) && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient / projected Newton / L-BFGS run on one rank");
     if (n > (size_t)1 << 30) return fail(QN_ERROR_INPUT_PARAMS, "n too large");
     HIPCHK(hipSetDevice(ctx->device));
     qn_solver* s = new qn_solver();
@@ -511,6 +513,9 @@ extern "C" int qn_solver_set_option(qn_solver* s, int option, int value) {
     case QN_OPT_BTB_PROJECT_IN_EVAL: s->no_projfold = !on; return QN_OK;
     case QN_OPT_EVAL_ZIGZAG: s->zig = on ? 1 : 0; return QN_OK;
     case QN_OPT_PNEWTON_REUSE_FACTOR: s->pn_reuse = on ? 1 : 0; s->pn_factor_serial = 0; return QN_OK;
+    case QN_OPT_LBFGS_UNIT_SCALING:
+        if (s->method != QN_LBFGS) return fail(QN_ERROR_INPUT_PARAMS, "unit scaling belongs to an L-BFGS solver");
+        return lbfgs_set_unit_scaling(s, on);
     case QN_OPT_PNORM_NONTEMPORAL:
         if (value < -1 || value > 1) return fail(QN_ERROR_INPUT_PARAMS, "non-temporal loads of inverse_p: 0 (plain), 1 (non-temporal) or -1 (by size)");
         s->pnorm_nt = value;
@@ -615,7 +620,7 @@ static int bounds_upload(qn_solver* s, double* dst, const double* src_host, doub
 extern "C" int qn_solver_set_bounds(qn_solver* s, const double* lb_host, const double* ub_host) { // BFGSB::new, bfgs_b.rs:43-63
     if (!s || !lb_host || !ub_host) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
     if (s->method != QN_BFGS && s->method != QN_DFP && s->method != QN_SR1 && s->method != QN_BROYDEN && !vec_method(s->method))
-        return fail(QN_ERROR_INPUT_PARAMS, "bounds need a BFGS / DFP / SR1 / Broyden / SPG / projected-gradient solver");
+        return fail(QN_ERROR_INPUT_PARAMS, "bounds need a BFGS / DFP / SR1 / Broyden / SPG / projected-gradient / L-BFGS solver");
     HIPCHK(hipSetDevice(s->ctx->device));
     QNCHK(bounds_alloc(s));
     QNCHK(bounds_upload(s, s->bounds_block, lb_host, -INFINITY));

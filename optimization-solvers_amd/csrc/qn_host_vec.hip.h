@@ -17,7 +17,11 @@ extern "C" void qn_gll_quadratic_with_sigmas(qn_linesearch* ls, double sigma1, d
 
 static bool pn_method(int method) { return method == QN_PROJECTED_NEWTON || method == QN_SPECTRAL_PROJECTED_NEWTON; }
 static bool spectral_method(int method) { return method == QN_SPG || method == QN_SPECTRAL_PROJECTED_NEWTON; }
-static bool vec_method(int method) { return method == QN_SPG || method == QN_PROJECTED_GRADIENT || pn_method(method); }
+static bool vec_method(int method) { return method == QN_SPG || method == QN_PROJECTED_GRADIENT || pn_method(method) || method == QN_LBFGS; }
+struct VecRun;
+static int lbfgs_state_alloc(qn_solver* s); // QN_LBFGS: qn_host_lbfgs.hip.h
+static int lbfgs_enqueue_direction(VecRun& r);
+static int lbfgs_enqueue_accept(VecRun& r);
 static int vec_grid(size_t np) { // a function of n alone: four 16-byte accesses per thread until 4 workgroups per CU are out
     const size_t per = (size_t)QN_VEC_TPB * 2 * 4;
     return (int)std::min<size_t>(QN_VEC_MAXG, std::max<size_t>(1, (np + per - 1) / per));
@@ -32,12 +36,14 @@ static int vec_state_alloc(qn_solver* s) {
     s->hvctl->lambda_min = 1e-3; s->hvctl->lambda_max = 1e3; // spg.rs:36-37
     QNCHK(s->vpart.alloc_zero((size_t)QN_VEC_NPART * QN_VEC_MAXG, st));
     QNCHK(bounds_alloc(s)); // the box is (-inf, +inf) until qn_solver_set_bounds
+    if (s->method == QN_LBFGS) QNCHK(lbfgs_state_alloc(s));
     return QN_OK;
 }
 static void vec_state_reset(qn_solver* s) { // back to the state right after ::new: no lambda, an empty f_previous, no memo
     if (!s->hvctl) return;
     QnVecCtl* h = s->hvctl;
     h->has_lambda = 0; h->lambda = 0.0; h->have_eval = 0; h->ring_len = 0; h->k = 0; h->n_iter = 0;
+    h->lb_kmem = 0; h->lb_head = 0; h->lb_gamma = 1.0; h->lb_resets = 0; // QN_LBFGS: an empty memory (lb_m and the scaling switch are settings: kept)
     h->has_sy = 0; h->s_norm = 0.0; h->y_norm = 0.0; // (the Cholesky factor of a device quadratic's Hessian is kept: it is keyed on the objective)
 }
 
@@ -64,6 +70,7 @@ extern "C" int qn_solver_spg_lambda(qn_solver* s, double* out, int* is_some) {
 static int vec_compute_direction(qn_solver* s, const double* g_host, double* d_host) {
     const size_t n = s->n, np = s->T.n_pad;
     if (pn_method(s->method)) return fail(QN_ERROR_INPUT_PARAMS, "the projected Newton direction needs the oracle's Hessian: use qn_minimize");
+    if (s->method == QN_LBFGS) return fail(QN_ERROR_INPUT_PARAMS, "the L-BFGS direction is formed from the device-resident memory: use qn_minimize");
     if (s->method == QN_SPG && !s->hvctl->has_lambda) return fail(QN_ERROR_INPUT_PARAMS, "lambda0 needs the oracle: the first qn_minimize evaluates it");
     std::vector<double> x(n), lb(n), ub(n);
     QNCHK(qn_solver_get_x(s, x.data()));
@@ -190,13 +197,13 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
                         qn_callback_fn callback, void* callback_user, int ls_only, double ls_f0) {
     qn_context* c = s->ctx;
     HIPCHK(hipSetDevice(c->device));
-    if (c->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient / projected Newton run on one rank");
-    const bool pn = pn_method(s->method);
+    if (c->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient / projected Newton / L-BFGS run on one rank");
+    const bool pn = pn_method(s->method), lbfgs = s->method == QN_LBFGS;
     VecRun r{s, o, nullptr, {}};
     QNCHK(check_oracle(c, s->n, o, &r.obj));
     if (r.obj && r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_LOGSUMEXP) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
     if (ls->kind == QN_LS_MORETHUENTE || ls->kind == QN_LS_MORETHUENTE_B)
-        return fail(QN_ERROR_INPUT_PARAMS, "More-Thuente with SPG / projected gradient is out of scope: use GLLQuadratic, BackTracking or BackTrackingB");
+        return fail(QN_ERROR_INPUT_PARAMS, "More-Thuente with SPG / projected gradient / projected Newton / L-BFGS is out of scope: use GLLQuadratic, BackTracking or BackTrackingB");
     if (ls->kind != QN_LS_GLL_QUADRATIC && ls->kind != QN_LS_BACKTRACKING && ls->kind != QN_LS_BACKTRACKING_B)
         return fail(QN_ERROR_INPUT_PARAMS, "unknown line search");
     if (ls->kind == QN_LS_GLL_QUADRATIC && (ls->_pad < 1 || ls->_pad > QN_GLL_MAX_M))
@@ -241,6 +248,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     a.lb = s->V.lb; a.ub = s->V.ub; a.llb = s->V.llb; a.lub = s->V.lub;
     a.z = s->V.y; a.part = s->vpart; a.ctl = s->vctl; a.f_dev = s->f_dev; a.trace = s->V.trace; a.xtrace = s->V.xtrace;
     a.n = (int)s->n; a.np = (int)np; a.G = vec_grid(np);
+    a.zw = s->V.y; a.lsmall = s->lb_small; // (the ring and the share buffer: lbfgs_enqueue_direction, on first use)
     const int G = a.G;
     const bool host_oracle = o->kind == QN_ORACLE_HOST;
     const size_t vb = np * sizeof(double);
@@ -259,7 +267,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         s->stats.obj_bytes = 0;
         if (r.obj && r.obj->kind == OBJ_QUADRATIC) s->stats.obj_bytes = h->n_evals * (uint64_t)r.obj->T.rpr * (uint64_t)r.obj->T.n_pad * 8ull;
         stats_add_totals(s); // (no update passes, one rank: total_h_* and total_xchg_* stay)
-        s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u);
+        s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u) | (lbfgs ? QN_PATH_LBFGS : 0u);
         if (s->method == QN_PROJECTED_NEWTON) { // s_norm() / y_norm() (projected_newton.rs:10-11) through the getters every solver answers
             s->hctl->has_s_norm = h->has_sy; s->hctl->has_y_norm = h->has_sy; s->hctl->s_norm = h->s_norm; s->hctl->y_norm = h->y_norm;
         }
@@ -288,7 +296,9 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
                 done = h->phase == QN_VP_DONE;
                 continue;
             }
-        } else if (ph == QN_VP_NSOLVE) {
+            // QN_LBFGS: gram, mid, apply, then the direction and the loop top's second half -- all predicated on QN_VP_NSOLVE, no peek in between
+            if (lbfgs) QNCHK(lbfgs_enqueue_direction(r));
+        } else if (ph == QN_VP_NSOLVE && pn) { // (QN_LBFGS never starts a batch here: no peek falls between its loop top and its direction)
             // the one n x n work matrix (Newton's), for the first iteration that wants a direction: a converged start, a cap of 0 and the
             // constructor's lambda0 batch never come here
             QNCHK(newton_alloc(s));
@@ -312,7 +322,8 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
             QNCHK(vec_enqueue_eval(r));
         }
         VEC_LAUNCH(vec_decide_kernel, 1);
-        VEC_LAUNCH(vec_accept_kernel, G);
+        if (lbfgs) QNCHK(lbfgs_enqueue_accept(r));
+        else VEC_LAUNCH(vec_accept_kernel, G);
         VEC_LAUNCH(vec_post_kernel, 1);
         QNCHK(vec_peek(r, false));
         if (callback && h->k != k_seen) { // ls_solver.rs:105-107: after k += 1 (one iteration per batch at most)

@@ -18,6 +18,7 @@
 // The dot products multiply and add with two roundings, as the reference does (no FMA: these kernels are bound by memory, and at n = 2 --
 // the reference's own tests -- the sums then ARE the reference's, bit for bit).
 #pragma once
+#include <float.h>
 
 #define QN_VEC_TPB 256
 #define QN_VEC_MAXG 1024 // 4 workgroups per CU on 256 CUs
@@ -34,13 +35,16 @@ enum QnVecPhase : int32_t {
     QN_VP_LS_ONLY = 6, // qn_compute_step_len: g.d for the caller's direction, then the line search alone
     QN_VP_DONE = 7,
     QN_VP_NSOLVE = 8 // ProjectedNewton / SpectralProjectedNewton: the loop top let the iteration through; the host enqueues z = H^-1 g, then the direction
+                     // (QN_LBFGS: z = H_k g from the last pairs (s, y), qn_lbfgs.hip.h)
 };
 
 // the second-order variants (newton/projected_newton.rs, newton/spn.rs): the same machine, with z = H^-1 g where the first-order family has g
 __device__ __forceinline__ bool vec_newton(int method) { return method == QN_PROJECTED_NEWTON || method == QN_SPECTRAL_PROJECTED_NEWTON; }
 __device__ __forceinline__ bool vec_spectral(int method) { return method == QN_SPG || method == QN_SPECTRAL_PROJECTED_NEWTON; }
 // update_next_iterate calls the oracle at the accepted point, for y (spg.rs:130, spn.rs:135, projected_newton.rs:134)
-__device__ __forceinline__ bool vec_needs_y(int method) { return vec_spectral(method) || method == QN_PROJECTED_NEWTON; }
+__device__ __forceinline__ bool vec_needs_y(int method) { return vec_spectral(method) || method == QN_PROJECTED_NEWTON || method == QN_LBFGS; }
+// the direction is P(x - z) - x with a z that arrives from outside this file, in phase QN_VP_NSOLVE
+__device__ __forceinline__ bool vec_nsolve(int method) { return vec_newton(method) || method == QN_LBFGS; }
 
 struct QnVecCtl {
     // ---- configuration (host, per call) ----
@@ -70,6 +74,11 @@ struct QnVecCtl {
     // ---- ProjectedNewton: s_norm / y_norm (projected_newton.rs:10-11; survive calls, None after ::new) ----
     double s_norm, y_norm;
     int32_t has_sy, _pad2;
+    // ---- QN_LBFGS (qn_lbfgs.hip.h): the memory's bookkeeping; survives calls like lambda ----
+    int32_t lb_m, lb_unit;    // pairs kept at most; QN_OPT_LBFGS_UNIT_SCALING
+    int32_t lb_kmem, lb_head; // live pairs, slot of the oldest (the ring has lb_m + 1 slots)
+    double lb_gamma;          // the scaling of the last direction
+    uint64_t lb_resets;       // times the safeguard g.z > 0 cleared the memory
 };
 
 struct QnVecArgs {
@@ -82,6 +91,8 @@ struct QnVecArgs {
     QnTraceRec* trace;
     double* xtrace;
     int n, np, G;
+    // QN_LBFGS: the ring S[lb_m + 1][np], Y[lb_m + 1][np], the Gram kernel's shares, the small block (Gram matrices, u, gamma v), z for writing
+    double *lS, *lY, *lpart, *lsmall, *zw;
 };
 
 __device__ __forceinline__ double vec_block_max(double v, double* lds) { return ctl_block_fmax(v, lds); }
@@ -197,7 +208,7 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_top_kernel(const QnVecArgs a) 
             return;
         }
         if (vec_loop_top(c, pg)) return;
-        if (vec_newton(c->method)) { c->phase = QN_VP_NSOLVE; return; } // the direction needs the factorisation: the host enqueues it for this phase only
+        if (vec_nsolve(c->method)) { c->phase = QN_VP_NSOLVE; return; } // the direction needs the factorisation (QN_LBFGS: the two streams of its memory): enqueued for this phase only
     }
     c->gd = gd;
     if (c->ls_kind == QN_LS_GLL_QUADRATIC) { // gll_quadratic.rs:62-64: append_new_f, then f_max once
@@ -359,12 +370,20 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_post_kernel(const QnVecArgs a)
     const double sy = vec_sum_parts(a.part, 2, a.G, lds);
     const double ss = vec_sum_parts(a.part, 3, a.G, lds);
     const bool second = vec_newton(c->method) && c->gt_valid;
+    const bool lbfgs = c->method == QN_LBFGS; // (lbfgs_accept_kernel ran in vec_accept_kernel's place)
     double pgn = 0.0, yy = 0.0;
     if (second) {
         pgn = vec_max_parts(a.part, 4, a.G, lds);
         yy = vec_sum_parts(a.part, 5, a.G, lds);
     }
+    if (lbfgs) yy = vec_sum_parts(a.part, 5, a.G, lds);
     if (threadIdx.x != 0) return;
+    int committed = 0;
+    if (lbfgs && sy > DBL_EPSILON * yy) { // the pair in the staging slot joins the memory; otherwise the memory stays as it was
+        committed = 1;
+        if (c->lb_kmem == c->lb_m) c->lb_head = (c->lb_head + 1) % (c->lb_m + 1); // (the oldest pair's slot is the next staging slot)
+        else c->lb_kmem++;
+    }
     if (c->method == QN_PROJECTED_NEWTON) { c->s_norm = sqrt(ss); c->y_norm = sqrt(yy); c->has_sy = 1; } // projected_newton.rs:132-135
     if (vec_spectral(c->method)) { // spg.rs:135-143, spn.rs:140-147
         if (sy <= 0.0) c->lambda = c->lambda_max;
@@ -372,9 +391,9 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_post_kernel(const QnVecArgs a)
     }
     if (a.trace && (int64_t)c->n_iter < c->trace_cap) {
         QnTraceRec r;
-        r.f = c->tr_f; r.gnorm = c->tr_gnorm; r.t = c->t; r.s_norm = (vec_spectral(c->method) || c->method == QN_PROJECTED_NEWTON) ? sqrt(ss) : 0.0;
+        r.f = c->tr_f; r.gnorm = c->tr_gnorm; r.t = c->t; r.s_norm = (vec_spectral(c->method) || c->method == QN_PROJECTED_NEWTON || lbfgs) ? sqrt(ss) : 0.0;
         r.y_norm = c->method == QN_PROJECTED_NEWTON ? sqrt(yy) : 0.0;
-        r.n_evals = c->tr_n_evals; r.ls_iters = c->tr_ls_iters; r.ls_cases = 0; r.updated = 0;
+        r.n_evals = c->tr_n_evals; r.ls_iters = c->tr_ls_iters; r.ls_cases = 0; r.updated = committed;
         a.trace[c->n_iter] = r;
     }
     c->have_eval = c->gt_valid;

@@ -63,6 +63,7 @@ OPTIONS = {
     "pnewton_reuse_factor": 23,
     "pnorm_nontemporal": 24,
     "pnorm_rows_per_wave": 25,
+    "lbfgs_unit_scaling": 26,
 }
 OPT_GENERIC_KERNELS = 1
 OPT_DEFERRED_UPDATE_STEP = 2
@@ -89,6 +90,7 @@ OPT_TOUCH_Q_ROWS = 22
 OPT_PNEWTON_REUSE_FACTOR = 23
 OPT_PNORM_NONTEMPORAL = 24
 OPT_PNORM_ROWS_PER_WAVE = 25
+OPT_LBFGS_UNIT_SCALING = 26
 
 
 class SolverError(Exception):
@@ -960,6 +962,60 @@ class SpectralProjectedNewton(SpectralProjectedGradient):
     METHOD = A.SPECTRAL_PROJECTED_NEWTON
 
     newton_factorisations = ProjectedNewton.newton_factorisations
+
+
+class ProjectedLBFGS(_ProjectedBase):
+    """Limited-memory BFGS in a box: `new(tol, x0, lower_bound, upper_bound, m=5)`; d = P(x - H_k g) - x with H_k g from the last m pairs (s, y)
+    in the compact form (two streams of the memory and one small solve per iteration on the GPU).  NOT the reference's `Lbfgsb` (the Fortran
+    L-BFGS-B: no generalised Cauchy point, no subspace minimisation here): the bounded variant follows BFGSB's convention (bfgs_b.rs:72-75), and
+    with an active box its direction is no more guaranteed to descend than BFGSB's."""
+    METHOD = A.LBFGS
+
+    def __init__(self, tol, x0, lower_bound, upper_bound, m=5, ctx=None, memoize=None):
+        super().__init__(tol, x0, lower_bound, upper_bound, ctx)
+        self.memoize = memoize
+        if m != 5:
+            self.set_memory(m)
+
+    @classmethod
+    def new(cls, tol, x0, lower_bound, upper_bound, m=5, ctx=None, memoize=None):
+        return cls(tol, x0, lower_bound, upper_bound, m, ctx, memoize)
+
+    def set_memory(self, m):
+        """qn_solver_set_lbfgs_memory: 1 <= m <= 32; the stored pairs are dropped"""
+        if not 0 <= int(m) < 2 ** 63:
+            raise ErrorInputParams("L-BFGS: the memory m must be 1 .. 32")
+        _check(A.lib().qn_solver_set_lbfgs_memory(self.h, int(m)))
+
+    def _lbfgs_state(self):
+        m, stored, resets, gamma = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_double()
+        _check(A.lib().qn_solver_lbfgs_state(self.h, C.byref(m), C.byref(stored), C.byref(gamma), C.byref(resets)))
+        return m.value, stored.value, gamma.value, resets.value
+
+    @property
+    def memory(self):
+        return self._lbfgs_state()[0]
+
+    def stored_pairs(self):
+        return self._lbfgs_state()[1]
+
+    def gamma(self):
+        return self._lbfgs_state()[2]
+
+    def resets(self):
+        return self._lbfgs_state()[3]
+
+
+class LBFGS(ProjectedLBFGS):
+    """Limited-memory BFGS: `new(tol, x0, m=5)`; d = -H_k g.  The same solver with the box left at (-inf, +inf)."""
+
+    def __init__(self, tol, x0, m=5, ctx=None, memoize=None):
+        n = _f64(x0).size
+        super().__init__(tol, x0, np.full(n, -np.inf), np.full(n, np.inf), m, ctx, memoize)
+
+    @classmethod
+    def new(cls, tol, x0, m=5, ctx=None, memoize=None):
+        return cls(tol, x0, m, ctx, memoize)
 
 
 class Newton(_SolverBase):

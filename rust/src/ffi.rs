@@ -36,6 +36,8 @@ pub const QN_SPECTRAL_PROJECTED_NEWTON: c_int = 8;
 pub const QN_BROYDEN: c_int = 9;
 pub const QN_COORDINATE_DESCENT: c_int = 10;
 pub const QN_PNORM_DESCENT: c_int = 11;
+pub const QN_LBFGS: c_int = 12;
+pub const QN_LBFGS_MAX_M: usize = 32;
 
 // qn_option (ABI 5): what rounds 1-5 selected through negative codes of qn_solver_set_tiling; value != 0 on, 0 off
 pub const QN_OPT_GENERIC_KERNELS: c_int = 1;
@@ -63,6 +65,7 @@ pub const QN_OPT_TOUCH_Q_ROWS: c_int = 22;
 pub const QN_OPT_PNEWTON_REUSE_FACTOR: c_int = 23;
 pub const QN_OPT_PNORM_NONTEMPORAL: c_int = 24;
 pub const QN_OPT_PNORM_ROWS_PER_WAVE: c_int = 25;
+pub const QN_OPT_LBFGS_UNIT_SCALING: c_int = 26;
 
 pub const QN_UNIQUE_ID_BYTES: usize = 128;
 pub const QN_TRACE_LS_MODIFIED: i32 = 1 << 30;
@@ -76,6 +79,7 @@ pub const QN_PATH_VECTOR: u32 = 64;
 pub const QN_PATH_PNEWTON: u32 = 128;
 pub const QN_PATH_RANK1: u32 = 256;
 pub const QN_PATH_PNORM: u32 = 512;
+pub const QN_PATH_LBFGS: u32 = 1024;
 
 #[repr(C)] pub struct qn_context { _p: [u8; 0] }
 #[repr(C)] pub struct qn_solver { _p: [u8; 0] }
@@ -231,6 +235,8 @@ extern "C" {
     pub fn qn_solver_set_spg_lambdas(s: *mut qn_solver, lambda_min: f64, lambda_max: f64) -> c_int;
     pub fn qn_solver_spg_lambda(s: *mut qn_solver, out: *mut f64, is_some: *mut c_int) -> c_int;
     pub fn qn_solver_newton_factorisations(s: *mut qn_solver, out: *mut usize) -> c_int;
+    pub fn qn_solver_set_lbfgs_memory(s: *mut qn_solver, m: usize) -> c_int;
+    pub fn qn_solver_lbfgs_state(s: *mut qn_solver, m: *mut usize, stored: *mut usize, gamma: *mut f64, resets: *mut usize) -> c_int;
     pub fn qn_solver_reset(s: *mut qn_solver, x0_host: *const f64) -> c_int;
     pub fn qn_minimize(s: *mut qn_solver, ls: *mut qn_linesearch, oracle: *const qn_oracle, max_iter_solver: usize, max_iter_line_search: usize, callback: qn_callback_fn, callback_user: *mut c_void) -> c_int;
     pub fn qn_compute_step_len(ctx: *mut qn_context, ls: *mut qn_linesearch, x_k_host: *const f64, f_k: f64, g_k_host: *const f64, direction_host: *const f64, n: usize, oracle: *const qn_oracle, max_iter: usize, step_out: *mut f64) -> c_int;

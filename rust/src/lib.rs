@@ -726,6 +726,38 @@ gpu_solver!(
     GpuSpectralProjectedNewton, QN_SPECTRAL_PROJECTED_NEWTON, false
 );
 
+gpu_solver!(
+    /// Limited-memory BFGS in a box: `new(tol, x0).with_bounds(lb, ub).with_memory(m)`; d = P(x - H_k g) - x with H_k g from the last m pairs
+    /// (s, y) in the compact form -- two streams of the memory and one small solve per iteration on the GPU (QN_PATH_LBFGS).  NOT the reference's
+    /// `Lbfgsb` (the Fortran L-BFGS-B: no generalised Cauchy point, no subspace minimisation here); the bounded variant follows `BFGSB`'s
+    /// convention (bfgs_b.rs:72-75).  Drive it with `minimize_on_device` / `minimize_objective`: the memory lives on the device.
+    GpuProjectedLbfgs, QN_LBFGS, false
+);
+gpu_solver!(
+    /// Limited-memory BFGS: `new(tol, x0).with_memory(m)`; d = -H_k g.  `GpuProjectedLbfgs` with the box left at (-inf, +inf).
+    GpuLbfgs, QN_LBFGS, false
+);
+
+macro_rules! lbfgs_memory {
+    ($name:ident) => {
+        impl $name {
+            /// 1 <= m <= 32 (default 5, as `Lbfgsb::new`, lbfgsb.rs:91); the stored pairs are dropped
+            pub fn with_memory(self, m: usize) -> Self {
+                assert_eq!(unsafe { qn_solver_set_lbfgs_memory(self.core.h, m) }, QN_OK, "{}", last_error());
+                self
+            }
+            /// (m, pairs stored, gamma of the last direction, times the safeguard g.z > 0 cleared the memory)
+            pub fn lbfgs_state(&self) -> (usize, usize, Floating, usize) {
+                let (mut m, mut stored, mut gamma, mut resets) = (0usize, 0usize, 0.0, 0usize);
+                assert_eq!(unsafe { qn_solver_lbfgs_state(self.core.h, &mut m, &mut stored, &mut gamma, &mut resets) }, QN_OK, "{}", last_error());
+                (m, stored, gamma, resets)
+            }
+        }
+    };
+}
+lbfgs_memory!(GpuLbfgs);
+lbfgs_memory!(GpuProjectedLbfgs);
+
 macro_rules! bounded_first_order {
     ($name:ident) => {
         impl $name {
@@ -759,6 +791,7 @@ bounded_first_order!(GpuProjectedGradientDescent);
 bounded_first_order!(GpuSpectralProjectedGradient);
 bounded_first_order!(GpuProjectedNewton);
 bounded_first_order!(GpuSpectralProjectedNewton);
+bounded_first_order!(GpuProjectedLbfgs);
 bounded_first_order!(GpuBroydenB); // (the same `with_bounds` / `HasBounds`; `grad_tol()` is its `tol`)
 
 macro_rules! newton_factorisations {
