@@ -110,7 +110,8 @@ void* qn_context_stream(qn_context* ctx); /* hipStream_t */
 enum { QN_LS_MORETHUENTE = 0, QN_LS_BACKTRACKING = 1,
        QN_LS_MORETHUENTE_B = 2 /* MoreThuenteB, morethuente_b.rs */, QN_LS_BACKTRACKING_B = 3 /* BackTrackingB, backtracking_b.rs */,
        QN_LS_GLL_QUADRATIC = 4 /* GLLQuadratic, gll_quadratic.rs: the non-monotone search of Grippo, Lampariello, Lucidi; QN_SPG / QN_PROJECTED_GRADIENT only */,
-       QN_LS_NO_SEARCH = 5 /* NoSearch, nosearch.rs: constant step 1.0 */ };
+       QN_LS_NO_SEARCH = 5 /* NoSearch, nosearch.rs: constant step 1.0 */,
+       QN_LS_STRONG_WOLFE = 6 /* StrongWolfe: MINPACK-2 dcsrch; the first-order family, the projected Newton pair and QN_LBFGS only */ };
 typedef struct {
     int32_t kind;
     int32_t _pad;
@@ -141,6 +142,25 @@ void qn_linesearch_with_upper_bound(qn_linesearch* ls, const double* upper_bound
 void qn_nosearch_new(qn_linesearch* ls);                               /* NoSearch, nosearch.rs:3 */
 void qn_gll_quadratic_new(qn_linesearch* ls, double c1, size_t m);                      /* GLLQuadratic::new, gll_quadratic.rs:13-23: sigma1 = 0.1, sigma2 = 0.9 */
 void qn_gll_quadratic_with_sigmas(qn_linesearch* ls, double sigma1, double sigma2);     /* :24-28 */
+/* StrongWolfe (QN_LS_STRONG_WOLFE; no counterpart among the reference's line searches): the strong-Wolfe search as published -- MINPACK-2 `dcsrch` / `dcstep`
+ * (More' and Thuente, ACM TOMS 20, 1994; the search the Fortran L-BFGS-B runs) -- for QN_SPG, QN_PROJECTED_GRADIENT, QN_PROJECTED_NEWTON,
+ * QN_SPECTRAL_PROJECTED_NEWTON and QN_LBFGS; every other method: QN_ERROR_INPUT_PARAMS.  ONE oracle call per trial: the bracket keeps (f, f') of its
+ * end points (the reference's More-Thuente transcription evaluates two or three points per inner iteration, morethuente.rs:181-294).  It travels in
+ * the fields above: kind = QN_LS_STRONG_WOLFE, c1 = ftol (1e-4), c2 = gtol (0.9), delta = xtol (0.1), t_min = stpmin (0), t_max = stpmax (1e10);
+ * qn_morethuente_with_t_min / _with_t_max set the last two.  qn_minimize checks 0 < c1 < c2 < 1, xtol >= 0 and 0 <= t_min <= t_max
+ * (QN_ERROR_INPUT_PARAMS).  The first trial is min(max(1, stpmin), stpmax).  The search ends on the strong-Wolfe conditions, on stp = stpmax with
+ * sufficient decrease and a derivative <= c1 g.d, on stp = stpmin, on the xtol test and on the rounding-error test; the returned step is then the one
+ * just evaluated.  When max_iter_line_search runs out the next step is returned unevaluated, as by this family's other searches.
+ * A trial whose f (or directional derivative) is NOT FINITE counts as "sufficient decrease fails, derivative positive": the bracket shrinks onto
+ * [best step, this step] and the next trial bisects it (dcsrch has no rule for that case).
+ * g.d >= 0 at the start of a search (dcsrch's input error) ends qn_minimize with QN_ABNORMAL_TERMINATION, "not a descent direction", x at x_k:
+ * ProjectedLBFGS with an active box can meet it (d = P(x - H g) - x need not descend).
+ * BOXED FORM: once qn_linesearch_with_lower_bound / _with_upper_bound gave it a box of its own (as the *_B searches hold one), every search runs
+ * with stpmax = min(t_max, min_i ratio_i), the ratio of morethuente_b.rs:185-197.  The clip is recomputed per search and NOT written back into
+ * t_max (the struct is not modified).  trace: ls_cases holds dcstep's case (1 .. 4; 5: a non-finite trial; 0: returned) per trial, base 8, and
+ * bit 30 when the search switched to its second stage.  qn_compute_step_len: QN_ERROR_INPUT_PARAMS for this kind. */
+void qn_strong_wolfe_new(qn_linesearch* ls, double c1, double c2);
+int qn_strong_wolfe_with_xtol(qn_linesearch* ls, double xtol);
 
 /* ---------------------------------------------------------------------------------------------
  * Oracle: `impl FnMut(&DVector<f64>) -> FuncEvalMultivariate` (ls_solver.rs:69, func_eval.rs:4-41).
@@ -203,7 +223,7 @@ int qn_objective_hessian(qn_objective* obj, const double* x_host, double* h_colm
 enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton/mod.rs:8-69, SURVEY.md 8(f) row f2 */,
        QN_SR1 = 4 /* sr1_b.rs (row f4; SR1B once qn_solver_set_bounds is called) */,
        /* The first-order family: O(n) state (no inverse Hessian), one rank, every vector operation on a device-wide grid (QN_PATH_VECTOR).
-        * Line searches: QN_LS_GLL_QUADRATIC, QN_LS_BACKTRACKING, QN_LS_BACKTRACKING_B (More-Thuente: QN_ERROR_INPUT_PARAMS).  The box is
+        * Line searches: QN_LS_GLL_QUADRATIC, QN_LS_BACKTRACKING, QN_LS_BACKTRACKING_B, QN_LS_STRONG_WOLFE (More-Thuente: QN_ERROR_INPUT_PARAMS).  The box is
         * qn_solver_set_bounds' (-inf, +inf without it).  trace: gnorm = ||projected gradient||_inf (ls_solver.rs:121-133), s_norm = ||s|| (SPG).
         * qn_solver_reset projects x0 onto the box, as ::new does (spg.rs:35).  qn_solver_compute_direction on these methods is a HOST utility for
         * bindings (it downloads x and the box and forms P(x - lambda g) - x in a host loop); qn_minimize forms its directions on the device.
@@ -213,7 +233,7 @@ enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton
         * (none for a run that ends on the iteration cap, none for SPG's constructor evaluation).  Host closures are called only for points the solver asked for. */
        QN_SPG = 5 /* SpectralProjectedGradient, steepest_descent/spg.rs */,
        QN_PROJECTED_GRADIENT = 6 /* ProjectedGradientDescent, steepest_descent/projected_gradient_descent.rs */,
-       /* The second-order box-constrained pair (newton/projected_newton.rs, newton/spn.rs): the first-order family's machine, line searches, box,
+       /* The second-order box-constrained pair (newton/projected_newton.rs, newton/spn.rs): the first-order family's machine, line searches (QN_LS_STRONG_WOLFE among them), box,
         * trace, callbacks and warm restarts, with z = H^-1 g where that family has g: d = P(x - z) - x, and d = P(x - lambda z) - x with SPG's
         * lambda (qn_solver_set_spg_lambdas / qn_solver_spg_lambda answer for QN_SPECTRAL_PROJECTED_NEWTON too).  z is `hessian.cholesky().unwrap()
         * .solve(g)`: one blocked Cholesky (Newton's, on the f64 matrix cores) and one pair of triangular solves per iteration; ONLY THE LOWER
@@ -248,7 +268,8 @@ enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton
        /* Limited-memory BFGS (ProjectedLBFGS once qn_solver_set_bounds is called): the quasi-Newton method whose state is O(m n) and not O(n^2) -- the last
         * m pairs (s, y), m = 5 by default as Lbfgsb::new (quasi_newton/lbfgsb.rs:91), 1 <= m <= QN_LBFGS_MAX_M (qn_solver_set_lbfgs_memory).  It runs on the
         * first-order family's machine (QN_PATH_VECTOR | QN_PATH_LBFGS) and takes that family's line searches (QN_LS_GLL_QUADRATIC, QN_LS_BACKTRACKING,
-        * QN_LS_BACKTRACKING_B; More-Thuente: QN_ERROR_INPUT_PARAMS), box, loop top (||projected gradient||_inf < tol; no s_norm / y_norm tests), trace
+        * QN_LS_BACKTRACKING_B, and QN_LS_STRONG_WOLFE -- the search that keeps s.y > 0 on a free problem, so that every pair is committed;
+        * More-Thuente: QN_ERROR_INPUT_PARAMS), box, loop top (||projected gradient||_inf < tol; no s_norm / y_norm tests), trace
         * (gnorm = that norm, s_norm = ||s||, updated = the pair was committed), callbacks and warm restarts (the memory survives calls; qn_solver_reset
         * empties it); every oracle kind, memoize 0 / 1, one rank.  The direction is d = P(x - z) - x with z = H_k g from the COMPACT FORM of Byrd, Nocedal
         * and Schnabel (1994): two streams of the memory and one small solve per iteration (csrc/qn_lbfgs.hip.h), gamma = s_k.y_k / y_k.y_k

@@ -163,6 +163,33 @@ class GLLQuadratic {
     qn_linesearch& ffi() { return s_; }
 };
 
+// StrongWolfe (QN_LS_STRONG_WOLFE): MINPACK-2 dcsrch for the O(n) solvers (SPG, projected gradient, the projected Newton pair, LBFGS / ProjectedLBFGS),
+// one oracle call per trial; with a box of its own every search's stpmax is clipped to it (t_max itself is never modified).  0 < c1 < c2 < 1 is
+// checked by minimize.  Keeps its own copies of the bounds.
+class StrongWolfe {
+    qn_linesearch s_;
+    DVector lb_, ub_;
+    void rebind() {
+        if (!lb_.empty()) qn_linesearch_with_lower_bound(&s_, lb_.data());
+        if (!ub_.empty()) qn_linesearch_with_upper_bound(&s_, ub_.data());
+    }
+  public:
+    explicit StrongWolfe(Floating c1 = 1e-4, Floating c2 = 0.9) { qn_strong_wolfe_new(&s_, c1, c2); }
+    StrongWolfe(const StrongWolfe& o) : s_(o.s_), lb_(o.lb_), ub_(o.ub_) { rebind(); }
+    StrongWolfe& operator=(const StrongWolfe& o) { s_ = o.s_; lb_ = o.lb_; ub_ = o.ub_; rebind(); return *this; }
+    static StrongWolfe new_(Floating c1 = 1e-4, Floating c2 = 0.9) { return StrongWolfe(c1, c2); }
+    StrongWolfe with_xtol(Floating v) && { check(qn_strong_wolfe_with_xtol(&s_, v)); return *this; }
+    StrongWolfe with_t_min(Floating v) && { check(qn_morethuente_with_t_min(&s_, v)); return *this; }
+    StrongWolfe with_t_max(Floating v) && { check(qn_morethuente_with_t_max(&s_, v)); return *this; }
+    StrongWolfe with_lower_bound(const DVector& lb) && { lb_ = lb; rebind(); return *this; }
+    StrongWolfe with_upper_bound(const DVector& ub) && { ub_ = ub; rebind(); return *this; }
+    Floating c1() const { return s_.c1; }
+    Floating c2() const { return s_.c2; }
+    Floating xtol() const { return s_.delta; }
+    Floating t_max() const { return s_.t_max; }
+    qn_linesearch& ffi() { return s_; }
+};
+
 // backtracking_b.rs: projected trial points; keeps its own copies of the box
 class BackTrackingB {
     qn_linesearch s_;

@@ -9,6 +9,7 @@ LIB_PATH = os.environ.get("QN_HIP_LIB") or os.path.join(_HERE, "lib", "libqn_hip
 OK, MAX_ITER_REACHED, OUT_OF_DOMAIN, ERROR_INPUT_PARAMS, ABNORMAL_TERMINATION = range(5)
 LS_MORETHUENTE, LS_BACKTRACKING, LS_MORETHUENTE_B, LS_BACKTRACKING_B, LS_GLL_QUADRATIC = 0, 1, 2, 3, 4
 LS_NO_SEARCH = 5  # line_search/nosearch.rs
+LS_STRONG_WOLFE = 6  # MINPACK-2 dcsrch on the vector machine (no counterpart among the reference's searches)
 ORACLE_HOST, ORACLE_DEVICE_FN, ORACLE_OBJECTIVE = 0, 1, 2
 BFGS, DFP, GRADIENT_DESCENT, NEWTON, SR1, SPG, PROJECTED_GRADIENT, PROJECTED_NEWTON, SPECTRAL_PROJECTED_NEWTON = 0, 1, 2, 3, 4, 5, 6, 7, 8
 BROYDEN = 9  # quasi_newton/broyden.rs (BroydenB once bounds are set)
@@ -105,6 +106,8 @@ SYMBOLS = [
     ("qn_nosearch_new", None, [C.POINTER(LineSearchStruct)]),
     ("qn_gll_quadratic_new", None, [C.POINTER(LineSearchStruct), C.c_double, C.c_size_t]),
     ("qn_gll_quadratic_with_sigmas", None, [C.POINTER(LineSearchStruct), C.c_double, C.c_double]),
+    ("qn_strong_wolfe_new", None, [C.POINTER(LineSearchStruct), C.c_double, C.c_double]),
+    ("qn_strong_wolfe_with_xtol", C.c_int, [C.POINTER(LineSearchStruct), C.c_double]),
     ("qn_quadratic_create", C.c_int, [C.c_void_p, C.c_size_t, dp, dp, C.POINTER(C.c_void_p)]),
     ("qn_quadratic_create_synthetic", C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, dp, dp, C.POINTER(C.c_void_p)]),
     ("qn_logsumexp_create", C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, dp, dp, C.c_double, C.POINTER(C.c_void_p)]),

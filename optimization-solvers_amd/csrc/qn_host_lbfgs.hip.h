@@ -51,7 +51,7 @@ extern "C" int qn_solver_lbfgs_state(qn_solver* s, size_t* m, size_t* stored, do
 // phase QN_VP_NSOLVE: z = H_k g into V.y by the two streams and the small kernel between them, then the direction and the rest of the loop top.
 // The Gram kernel's second grid dimension comes from the host's copy of the pair count: it is the device's, because the only kernel that
 // raises it (vec_post_kernel) runs in front of the batch's peek.
-static int lbfgs_enqueue_direction(VecRun& r) {
+static int lbfgs_enqueue_direction(VecRun& r, bool wolfe_clip) {
     qn_solver* s = r.s;
     hipStream_t st = s->ctx->stream;
     QNCHK(lbfgs_ring_alloc(s));
@@ -79,6 +79,12 @@ static int lbfgs_enqueue_direction(VecRun& r) {
         ProfScope ps(s, KC_EREDUCE);
         hipLaunchKernelGGL(vec_dir_kernel, dim3(r.a.G), dim3(QN_VEC_TPB), 0, st, r.a);
         HIPCHK(hipGetLastError());
+    }
+    if (wolfe_clip) { // StrongWolfe's boxed form: the ratio's minima behind the direction (qn_vec_wolfe.hip.h)
+        ProfScope ps(s, KC_CTL);
+        hipLaunchKernelGGL(wolfe_clip_kernel, dim3(r.a.G), dim3(QN_VEC_TPB), 0, st, r.a);
+        HIPCHK(hipGetLastError());
+        s->stats.launches++;
     }
     {
         ProfScope ps(s, KC_CTL);

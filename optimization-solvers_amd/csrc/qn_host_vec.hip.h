@@ -1,5 +1,5 @@
-// qn_host_vec.hip.h -- host side of the first-order family (QN_SPG, QN_PROJECTED_GRADIENT; kernels: qn_vec.hip.h): GLLQuadratic's builders,
-// the SPG setters, and the pump.  The pump takes no decision: it enqueues one iteration's kernels -- every one predicated on QnVecCtl.phase --
+// qn_host_vec.hip.h -- host side of the first-order family (QN_SPG, QN_PROJECTED_GRADIENT; kernels: qn_vec.hip.h): GLLQuadratic's and StrongWolfe's
+// builders, the SPG setters, and the pump.  The pump takes no decision: it enqueues one iteration's kernels -- every one predicated on QnVecCtl.phase --
 // and reads the control block back with one small copy per batch (a 700-byte hipMemcpyAsync into pinned memory in front of the one
 // synchronisation the batch needs anyway: no second mapping to keep coherent, no fence in the one-workgroup kernels).
 #pragma once
@@ -15,12 +15,26 @@ extern "C" void qn_gll_quadratic_with_sigmas(qn_linesearch* ls, double sigma1, d
     ls->delta_min = sigma1; ls->delta_max = sigma2;
 }
 
+// StrongWolfe (QN_LS_STRONG_WOLFE, kernels: qn_vec_wolfe.hip.h): MINPACK-2 dcsrch; ftol = c1, gtol = c2, xtol in `delta`, stpmin = t_min, stpmax = t_max
+extern "C" void qn_strong_wolfe_new(qn_linesearch* ls, double c1, double c2) {
+    memset(ls, 0, sizeof(*ls));
+    ls->kind = QN_LS_STRONG_WOLFE;
+    ls->c1 = c1; ls->c2 = c2; // (0 < c1 < c2 < 1 is checked by qn_minimize: this constructor returns nothing)
+    ls->delta = 0.1; ls->t_min = 0.0; ls->t_max = 1e10;
+}
+extern "C" int qn_strong_wolfe_with_xtol(qn_linesearch* ls, double xtol) {
+    if (!ls || ls->kind != QN_LS_STRONG_WOLFE) return fail(QN_ERROR_INPUT_PARAMS, "xtol belongs to a StrongWolfe line search");
+    if (!(xtol >= 0.0)) return fail(QN_ERROR_INPUT_PARAMS, "StrongWolfe: xtol must not be negative");
+    ls->delta = xtol;
+    return QN_OK;
+}
+
 static bool pn_method(int method) { return method == QN_PROJECTED_NEWTON || method == QN_SPECTRAL_PROJECTED_NEWTON; }
 static bool spectral_method(int method) { return method == QN_SPG || method == QN_SPECTRAL_PROJECTED_NEWTON; }
 static bool vec_method(int method) { return method == QN_SPG || method == QN_PROJECTED_GRADIENT || pn_method(method) || method == QN_LBFGS; }
 struct VecRun;
 static int lbfgs_state_alloc(qn_solver* s); // QN_LBFGS: qn_host_lbfgs.hip.h
-static int lbfgs_enqueue_direction(VecRun& r);
+static int lbfgs_enqueue_direction(VecRun& r, bool wolfe_clip);
 static int lbfgs_enqueue_accept(VecRun& r);
 static int vec_grid(size_t np) { // a function of n alone: four 16-byte accesses per thread until 4 workgroups per CU are out
     const size_t per = (size_t)QN_VEC_TPB * 2 * 4;
@@ -204,8 +218,17 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     if (r.obj && r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_LOGSUMEXP) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
     if (ls->kind == QN_LS_MORETHUENTE || ls->kind == QN_LS_MORETHUENTE_B)
         return fail(QN_ERROR_INPUT_PARAMS, "More-Thuente with SPG / projected gradient / projected Newton / L-BFGS is out of scope: use GLLQuadratic, BackTracking or BackTrackingB");
-    if (ls->kind != QN_LS_GLL_QUADRATIC && ls->kind != QN_LS_BACKTRACKING && ls->kind != QN_LS_BACKTRACKING_B)
+    const bool wolfe = ls->kind == QN_LS_STRONG_WOLFE;
+    if (ls->kind != QN_LS_GLL_QUADRATIC && ls->kind != QN_LS_BACKTRACKING && ls->kind != QN_LS_BACKTRACKING_B && !wolfe)
         return fail(QN_ERROR_INPUT_PARAMS, "unknown line search");
+    if (wolfe) {
+        if (ls_only) return fail(QN_ERROR_INPUT_PARAMS, "StrongWolfe: compute_step_len on its own is not built: use qn_minimize");
+        if (!(ls->c1 > 0.0 && ls->c1 < ls->c2 && ls->c2 < 1.0)) return fail(QN_ERROR_INPUT_PARAMS, "StrongWolfe: 0 < c1 < c2 < 1");
+        if (!(ls->delta >= 0.0)) return fail(QN_ERROR_INPUT_PARAMS, "StrongWolfe: xtol must not be negative");
+        if (!(ls->t_min >= 0.0 && ls->t_max >= ls->t_min)) return fail(QN_ERROR_INPUT_PARAMS, "StrongWolfe: 0 <= t_min <= t_max");
+    }
+    // StrongWolfe holds a box of its own once one of its bounds is set, as the *_B searches do
+    const bool wolfe_boxed = wolfe && (ls->lower_bound_host || ls->upper_bound_host);
     if (ls->kind == QN_LS_GLL_QUADRATIC && (ls->_pad < 1 || ls->_pad > QN_GLL_MAX_M))
         return fail(QN_ERROR_INPUT_PARAMS, "GLLQuadratic: the look-back m must be 1 .. 64 (the history is a fixed device ring)");
     if (pn) {
@@ -216,7 +239,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     QNCHK(vec_state_alloc(s));
     hipStream_t st = c->stream;
     const size_t np = s->T.n_pad;
-    if (ls->kind == QN_LS_BACKTRACKING_B) {
+    if (ls->kind == QN_LS_BACKTRACKING_B || wolfe_boxed) {
         QNCHK(bounds_upload(s, s->bounds_block + 2 * np, ls->lower_bound_host, -INFINITY));
         QNCHK(bounds_upload(s, s->bounds_block + 3 * np, ls->upper_bound_host, INFINITY));
     }
@@ -227,7 +250,9 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     h->max_iter_ls = (int64_t)std::min<size_t>(max_iter_line_search, (size_t)1 << 62);
     h->method = s->method; h->ls_kind = ls->kind; h->memoize = o->memoize ? 1 : 0; h->ls_only = ls_only;
     if (ls->kind == QN_LS_GLL_QUADRATIC) { h->c1 = ls->c1; h->m = ls->_pad; h->sigma1 = ls->delta_min; h->sigma2 = ls->delta_max; h->beta = 0.0; }
+    else if (wolfe) { h->c1 = ls->c1; h->w_c2 = ls->c2; h->w_xtol = ls->delta; h->w_tmin = ls->t_min; h->w_tmax = ls->t_max; h->beta = 0.0; h->m = 0; }
     else { h->c1 = ls->bt_c1; h->beta = ls->bt_beta; h->m = 0; }
+    h->w_boxed = wolfe_boxed ? 1 : 0; h->w_err = 0; h->tr_ls_cases = 0; h->tr_ndigits = 0;
     h->trace_cap = (int64_t)s->trace_cap; h->trace_x = s->trace_x;
     h->k = 0; h->ls_i = 0; h->status = -1; // ls_solver.rs:74
     h->n_calls = 0; h->n_evals = 0; h->n_iter = 0; h->tr_n_evals = 0; h->tr_ls_iters = 0;
@@ -287,6 +312,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         }
         if (ph == QN_VP_EVAL_X || ph == QN_VP_DIR || ph == QN_VP_LS_ONLY) {
             VEC_LAUNCH(vec_dir_kernel, G);
+            if (wolfe_boxed && !pn && !lbfgs) VEC_LAUNCH(wolfe_clip_kernel, G); // (those two form the direction the search follows in phase QN_VP_NSOLVE: the clip runs there)
             VEC_LAUNCH(vec_top_kernel, 1);
             // the constructor's batch (spg.rs:40-46, spn.rs:40-46) ends here: no trial is wanted yet.  So does the second-order variants' loop top
             // when it ran as a batch of its own (the first iteration, or an oracle that is not memoised): the factorisation is enqueued only
@@ -297,7 +323,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
                 continue;
             }
             // QN_LBFGS: gram, mid, apply, then the direction and the loop top's second half -- all predicated on QN_VP_NSOLVE, no peek in between
-            if (lbfgs) QNCHK(lbfgs_enqueue_direction(r));
+            if (lbfgs) QNCHK(lbfgs_enqueue_direction(r, wolfe_boxed));
         } else if (ph == QN_VP_NSOLVE && pn) { // (QN_LBFGS never starts a batch here: no peek falls between its loop top and its direction)
             // the one n x n work matrix (Newton's), for the first iteration that wants a direction: a converged start, a cap of 0 and the
             // constructor's lambda0 batch never come here
@@ -309,6 +335,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
                 return rc;
             }
             VEC_LAUNCH(vec_dir_kernel, G);
+            if (wolfe_boxed) VEC_LAUNCH(wolfe_clip_kernel, G);
             VEC_LAUNCH(vec_top_kernel, 1);
         } else if (ph != QN_VP_TRIAL && ph != QN_VP_REEVAL) {
             return fail(QN_ABNORMAL_TERMINATION, "vector pump: control block in an unexpected phase");
@@ -321,7 +348,12 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         } else {
             QNCHK(vec_enqueue_eval(r));
         }
-        VEC_LAUNCH(vec_decide_kernel, 1);
+        if (wolfe) { // phi'(t) = gt . d, then one dcsrch step in vec_decide_kernel's place (qn_vec_wolfe.hip.h)
+            VEC_LAUNCH(wolfe_phi_kernel, G);
+            VEC_LAUNCH(wolfe_decide_kernel, 1);
+        } else {
+            VEC_LAUNCH(vec_decide_kernel, 1);
+        }
         if (lbfgs) QNCHK(lbfgs_enqueue_accept(r));
         else VEC_LAUNCH(vec_accept_kernel, G);
         VEC_LAUNCH(vec_post_kernel, 1);
@@ -335,6 +367,9 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     }
     const int status = h->status;
     epilogue();
+    if (status == QN_ABNORMAL_TERMINATION && h->w_err) // dcsrch's START errors; the loop top ran, x is x_k
+        return fail(QN_ABNORMAL_TERMINATION, h->w_err == 1 ? "StrongWolfe: not a descent direction (g.d >= 0 at the start of the search); x is left at x_k"
+                                                           : "StrongWolfe: not a descent direction the search can follow (the box leaves stpmax < stpmin); x is left at x_k");
     if (status < 0 || status == QN_ABNORMAL_TERMINATION) return fail(QN_ABNORMAL_TERMINATION, "vector pump: the machine stopped without a status");
     return status;
 }

@@ -10,6 +10,8 @@
 //   vec_decide_kernel  (1 workgroup) the line search's decision: accept, or the next t
 //   vec_accept_kernel  predicated on the accept: x_next = x + t d, s, y, partials s.y, s.s; x <- x_next, g <- gt
 //   vec_post_kernel    (1 workgroup) the Barzilai-Borwein scalar, the trace record, k += 1, the iteration cap
+// (QN_LS_STRONG_WOLFE: wolfe_clip_kernel behind vec_dir_kernel, wolfe_phi_kernel behind the oracle, wolfe_decide_kernel in vec_decide_kernel's place:
+// qn_vec_wolfe.hip.h)
 //
 // REDUCTIONS are two-stage and fixed: workgroup b leaves its share in part[q * QN_VEC_MAXG + b]; the one-workgroup kernels add the G
 // shares in index order (thread j takes b = j, j + 256, ..., then the block sum in wave order).  The grid is a function of n alone, no
@@ -22,7 +24,7 @@
 
 #define QN_VEC_TPB 256
 #define QN_VEC_MAXG 1024 // 4 workgroups per CU on 256 CUs
-#define QN_VEC_NPART 6 // (4, 5: the second-order variants' accept kernel -- ||pg(x_next)||_inf and y.y)
+#define QN_VEC_NPART 8 // (4, 5: the second-order variants' accept kernel -- ||pg(x_next)||_inf and y.y; 6, 7: StrongWolfe's clip and phi', qn_vec_wolfe.hip.h)
 #define QN_GLL_MAX_M 64
 
 enum QnVecPhase : int32_t {
@@ -79,6 +81,12 @@ struct QnVecCtl {
     int32_t lb_kmem, lb_head; // live pairs, slot of the oldest (the ring has lb_m + 1 slots)
     double lb_gamma;          // the scaling of the last direction
     uint64_t lb_resets;       // times the safeguard g.z > 0 cleared the memory
+    // ---- QN_LS_STRONG_WOLFE (qn_vec_wolfe.hip.h): gtol, xtol, stpmin, the configured stpmax; then dcsrch's state between two trials ----
+    double w_c2, w_xtol, w_tmin, w_tmax;
+    double w_stpmax; // of this search: min(w_tmax, the box clip)
+    double w_finit, w_ginit, w_gtest, w_width, w_width1, w_stx, w_fx, w_gx, w_sty, w_fy, w_gy, w_stmin, w_stmax;
+    int32_t w_boxed, w_brackt, w_stage, w_err; // w_err: 1 = g.d >= 0 at the start, 2 = stpmax < stpmin
+    int32_t tr_ls_cases, tr_ndigits;           // trace scratch: dcstep's cases of this iteration's search, base 8
 };
 
 struct QnVecArgs {
@@ -96,6 +104,9 @@ struct QnVecArgs {
 };
 
 __device__ __forceinline__ double vec_block_max(double v, double* lds) { return ctl_block_fmax(v, lds); }
+// QN_LS_STRONG_WOLFE's part of the loop top (qn_vec_wolfe.hip.h)
+__device__ __forceinline__ double wolfe_min_parts(const double* part, int q, int G, double* lds);
+__device__ __forceinline__ bool wolfe_start(QnVecCtl* c, double gd, double clip);
 
 // d = P(x - lambda g) - x, three roundings per element in that order (spg.rs:81-83); PGD: x - g (projected_gradient_descent.rs:56-58).
 // Before SPG has its lambda the same kernel forms P(x0 - g0) - x0, whose infinity norm gives lambda0 (spg.rs:41-46).
@@ -196,6 +207,8 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_top_kernel(const QnVecArgs a) 
     const double pg = vec_max_parts(a.part, 0, a.G, lds);
     const double gd = vec_sum_parts(a.part, 1, a.G, lds);
     const double dm = vec_max_parts(a.part, 2, a.G, lds);
+    double clip = INFINITY; // StrongWolfe's boxed form: the largest step that stays inside the search's box (wolfe_clip_kernel's shares)
+    if (c->ls_kind == QN_LS_STRONG_WOLFE && c->w_boxed && ph != QN_VP_LS_ONLY) clip = wolfe_min_parts(a.part, 6, a.G, lds);
     if (threadIdx.x != 0) return;
     if (ph == QN_VP_EVAL_X) { c->f_cur = *a.f_dev; c->have_eval = 1; c->n_evals++; }
     if (ph != QN_VP_LS_ONLY && ph != QN_VP_NSOLVE) {
@@ -223,6 +236,7 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_top_kernel(const QnVecArgs a) 
     }
     c->t = 1.0;
     c->ls_i = 0;
+    if (c->ls_kind == QN_LS_STRONG_WOLFE && !wolfe_start(c, gd, clip)) return; // dcsrch's START: stpmax of this search, the first trial into c->t
     if (c->max_iter_ls <= 0) vec_ls_return(c, false);
     else c->phase = QN_VP_TRIAL;
 }
@@ -393,12 +407,12 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_post_kernel(const QnVecArgs a)
         QnTraceRec r;
         r.f = c->tr_f; r.gnorm = c->tr_gnorm; r.t = c->t; r.s_norm = (vec_spectral(c->method) || c->method == QN_PROJECTED_NEWTON || lbfgs) ? sqrt(ss) : 0.0;
         r.y_norm = c->method == QN_PROJECTED_NEWTON ? sqrt(yy) : 0.0;
-        r.n_evals = c->tr_n_evals; r.ls_iters = c->tr_ls_iters; r.ls_cases = 0; r.updated = committed;
+        r.n_evals = c->tr_n_evals; r.ls_iters = c->tr_ls_iters; r.ls_cases = c->tr_ls_cases; r.updated = committed;
         a.trace[c->n_iter] = r;
     }
     c->have_eval = c->gt_valid;
     if (c->gt_valid) c->f_cur = c->f_t;
-    c->tr_n_evals = 0; c->tr_ls_iters = 0;
+    c->tr_n_evals = 0; c->tr_ls_iters = 0; c->tr_ls_cases = 0; c->tr_ndigits = 0;
     c->k++; c->n_iter++; // ls_solver.rs:104
     if (c->k >= c->max_iter) { c->status = QN_MAX_ITER_REACHED; c->phase = QN_VP_DONE; return; } // :78, :110
     c->phase = (c->have_eval && c->memoize) ? QN_VP_DIR : QN_VP_EVAL_X;

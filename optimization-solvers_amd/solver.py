@@ -469,6 +469,57 @@ class GLLQuadratic(_LineSearch):
         return self.s._pad
 
 
+class StrongWolfe(_LineSearch, _WolfeConditions):
+    """The strong-Wolfe line search of the O(n) solvers (SpectralProjectedGradient, ProjectedGradientDescent, ProjectedNewton, SpectralProjectedNewton,
+    LBFGS / ProjectedLBFGS): MINPACK-2 `dcsrch` / `dcstep` (More' and Thuente 1994), one oracle call per trial.  c1 = ftol, c2 = gtol; xtol 0.1,
+    t_min 0, t_max 1e10.  0 < c1 < c2 < 1 is checked by `minimize` (ErrorInputParams).  With a box of its own (`with_lower_bound` / `with_upper_bound`)
+    every search is clipped to it: stpmax = min(t_max, the largest step that stays inside); `t_max` itself is never modified.  On a free L-BFGS run
+    the curvature condition keeps s.y > 0, so every pair is committed.  g.d >= 0 at the start of a search: AbnormalTermination, x unchanged."""
+
+    def __init__(self, c1=1e-4, c2=0.9):
+        self.s = A.LineSearchStruct()
+        A.lib().qn_strong_wolfe_new(C.byref(self.s), float(c1), float(c2))
+        self._lb = self._ub = None
+
+    @classmethod
+    def new(cls, c1=1e-4, c2=0.9):
+        return cls(c1, c2)
+
+    def with_xtol(self, xtol):
+        _check(A.lib().qn_strong_wolfe_with_xtol(C.byref(self.s), float(xtol)))
+        return self
+
+    def with_t_min(self, t_min):
+        _check(A.lib().qn_morethuente_with_t_min(C.byref(self.s), float(t_min)))
+        return self
+
+    def with_t_max(self, t_max):
+        _check(A.lib().qn_morethuente_with_t_max(C.byref(self.s), float(t_max)))
+        return self
+
+    def with_lower_bound(self, lb):
+        self._lb = _f64(lb)
+        A.lib().qn_linesearch_with_lower_bound(C.byref(self.s), self._lb.ctypes.data)
+        return self
+
+    def with_upper_bound(self, ub):
+        self._ub = _f64(ub)
+        A.lib().qn_linesearch_with_upper_bound(C.byref(self.s), self._ub.ctypes.data)
+        return self
+
+    def c1(self):
+        return self.s.c1
+
+    def xtol(self):
+        return self.s.delta
+
+    def t_min(self):
+        return self.s.t_min
+
+    def t_max(self):
+        return self.s.t_max
+
+
 class Objective:
     """A device-resident objective owned by the library."""
 

@@ -19,6 +19,7 @@ pub const QN_LS_MORETHUENTE_B: i32 = 2;
 pub const QN_LS_BACKTRACKING_B: i32 = 3;
 pub const QN_LS_GLL_QUADRATIC: i32 = 4;
 pub const QN_LS_NO_SEARCH: i32 = 5;
+pub const QN_LS_STRONG_WOLFE: i32 = 6;
 
 pub const QN_ORACLE_HOST: i32 = 0;
 pub const QN_ORACLE_DEVICE_FN: i32 = 1;
@@ -216,6 +217,8 @@ extern "C" {
     pub fn qn_nosearch_new(ls: *mut qn_linesearch);
     pub fn qn_gll_quadratic_new(ls: *mut qn_linesearch, c1: f64, m: usize);
     pub fn qn_gll_quadratic_with_sigmas(ls: *mut qn_linesearch, sigma1: f64, sigma2: f64);
+    pub fn qn_strong_wolfe_new(ls: *mut qn_linesearch, c1: f64, c2: f64);
+    pub fn qn_strong_wolfe_with_xtol(ls: *mut qn_linesearch, xtol: f64) -> c_int;
 
     // ---- device-resident objectives ----
     pub fn qn_quadratic_create(ctx: *mut qn_context, n: usize, q_rowmajor_host: *const f64, b_host: *const f64, out: *mut *mut qn_objective) -> c_int;

@@ -273,6 +273,87 @@ impl GpuGLLQuadratic {
 }
 impl_line_search!(GpuGLLQuadratic);
 
+/// The strong-Wolfe search of the O(n) solvers (QN_LS_STRONG_WOLFE): MINPACK-2 `dcsrch`, one oracle call per trial; no counterpart among the
+/// reference's line searches.  `c1` = ftol, `c2` = gtol (0 < c1 < c2 < 1, checked by `minimize`); xtol 0.1, t_min 0, t_max 1e10.  With bounds of
+/// its own every search is clipped to the box; `t_max` is never modified.  The trait's `compute_step_len` on its own is not built for this kind
+/// (it panics with the library's message): use it through `minimize`.
+#[derive(Clone, Debug)]
+pub struct GpuStrongWolfe {
+    ls: qn_linesearch,
+    lb: Option<DVector<Floating>>,
+    ub: Option<DVector<Floating>>,
+}
+
+impl GpuStrongWolfe {
+    pub fn new(c1: Floating, c2: Floating) -> Self {
+        let mut ls = unsafe { std::mem::zeroed::<qn_linesearch>() };
+        unsafe { qn_strong_wolfe_new(&mut ls, c1, c2) };
+        GpuStrongWolfe { ls, lb: None, ub: None }
+    }
+    pub fn with_xtol(mut self, xtol: Floating) -> Self {
+        assert_eq!(unsafe { qn_strong_wolfe_with_xtol(&mut self.ls, xtol) }, QN_OK, "{}", last_error());
+        self
+    }
+    pub fn with_t_min(mut self, t_min: Floating) -> Self {
+        assert_eq!(unsafe { qn_morethuente_with_t_min(&mut self.ls, t_min) }, QN_OK, "{}", last_error());
+        self
+    }
+    pub fn with_t_max(mut self, t_max: Floating) -> Self {
+        assert_eq!(unsafe { qn_morethuente_with_t_max(&mut self.ls, t_max) }, QN_OK, "{}", last_error());
+        self
+    }
+    pub fn with_lower_bound(mut self, lb: DVector<Floating>) -> Self {
+        self.lb = Some(lb);
+        self
+    }
+    pub fn with_upper_bound(mut self, ub: DVector<Floating>) -> Self {
+        self.ub = Some(ub);
+        self
+    }
+    /// the bounds live in this value: their addresses are bound right before every call (a moved value keeps no stale pointer)
+    fn bind(&mut self) -> &mut qn_linesearch {
+        if let Some(lb) = &self.lb {
+            unsafe { qn_linesearch_with_lower_bound(&mut self.ls, lb.as_ptr()) };
+        }
+        if let Some(ub) = &self.ub {
+            unsafe { qn_linesearch_with_upper_bound(&mut self.ls, ub.as_ptr()) };
+        }
+        &mut self.ls
+    }
+}
+impl Default for GpuStrongWolfe {
+    fn default() -> Self {
+        Self::new(1e-4, 0.9)
+    }
+}
+impl LineSearch for GpuStrongWolfe {
+    fn compute_step_len(
+        &mut self,
+        x_k: &DVector<Floating>,
+        eval_x_k: &FuncEvalMultivariate,
+        direction_k: &DVector<Floating>,
+        oracle: &mut impl FnMut(&DVector<Floating>) -> FuncEvalMultivariate,
+        max_iter: usize,
+    ) -> Floating {
+        step_len_on_device(self.bind(), x_k, eval_x_k, direction_k, oracle, max_iter)
+    }
+}
+impl GpuLineSearch for GpuStrongWolfe {
+    fn ffi(&mut self) -> &mut qn_linesearch {
+        self.bind()
+    }
+}
+impl SufficientDecreaseCondition for GpuStrongWolfe {
+    fn c1(&self) -> Floating {
+        self.ls.c1
+    }
+}
+impl CurvatureCondition for GpuStrongWolfe {
+    fn c2(&self) -> Floating {
+        self.ls.c2
+    }
+}
+
 /// `NoSearch` (nosearch.rs): `compute_step_len` returns 1.0 and never calls the oracle.  On the device it pairs with
 /// `GpuGradientDescent`, `GpuCoordinateDescent`, `GpuPnormDescent` (and Newton): the solvers on the trait's default update hook.
 #[derive(Clone, Debug)]
