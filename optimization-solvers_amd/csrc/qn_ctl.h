@@ -146,4 +146,5 @@ struct QnCtl {
 
     // ---- counters ----
     uint64_t n_oracle_calls, n_oracle_evals, n_hpasses, n_hpass_rw, n_iterations;
+    uint64_t n_fast_steps; // sym2: steps of the machine taken straight-line in a prologue (qn_sym2.hip.h qn_s2_fast_step); zeroed by the host per call
 };

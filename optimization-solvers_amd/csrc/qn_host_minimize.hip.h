@@ -143,6 +143,7 @@ static int plan_run(Run& r, qn_solver* s, qn_linesearch* ls, const qn_oracle* o,
         if (r.sym2 && !r.gobj && getenv("QN_S2_GEN1_TILES")) r.tiles1 = atoi(getenv("QN_S2_GEN1_TILES")) != 0;
     }
     h->serviced = 0; h->ev_par = 0; h->ev_kind = QN_REQ_X; h->ev_t = 0.0; h->spec_tiles = 0;
+    h->n_fast_steps = 0;
     h->defer_u = 0;
     h->no_defer = s->no_defer;
     if (!r.fused) QNCHK(fused_export(s)); // another path takes over: it works on the canonical buffers
@@ -227,6 +228,7 @@ static int plan_s2_args(Run& r) {
         a.ring = (a.pair && s->ring && s->s2_nb * (s->s2_nb - 1) / 2 >= s->s2_G) ? 1 : 0;
         a.zig = (a.ring && s->zig) ? 1 : 0;
     }
+    a.fast = (s->fast_steps && c->world == 1 && !r.gobj && !r.bnd) ? 1 : 0; // (the instantiations that hold the straight-line steps: qn_s2_fast_step)
     // BackTrackingB's projection INSIDE the evaluation kernel (round 6, s2_evalr_kernel<true>): no s2_proj_kernel launch per trial -- the trial point is clamped
     // where it is formed, the shares of ||P(x + t d) - x||^2 leave the launch as column 6 of its table.  The same bits as the launch-per-trial flow.
     a.projfold = (r.btb && a.pair && a.ring && !s->no_projfold) ? 1 : 0;
@@ -470,6 +472,7 @@ static void finish_stats(Run& r) {
     s->stats.oracle_calls = h->n_oracle_calls;
     s->stats.oracle_evals = h->n_oracle_evals;
     s->stats.h_passes = h->n_hpasses;
+    s->stats.fast_machine_steps = h->n_fast_steps;
     uint64_t shard = (uint64_t)s->T.rpr * (uint64_t)s->T.n_pad * 8ull;
     const uint64_t full_shard = shard;
     if (r.sym || r.sym_generic) shard = (uint64_t)s->sym_nb * (uint64_t)(s->sym_nb + 1) / 2ull * (uint64_t)QN_TB * QN_TB * 8ull; // the streamed tiles

@@ -45,6 +45,7 @@ struct qn_solver {
     bool no_pair = false;      // diagnostics: the general evaluation kernel where the two-items-and-a-sliver instance would run
     int ring = (getenv("QN_S2_RING") && atoi(getenv("QN_S2_RING")) == 0) ? 0 : 1; // the pair instance's evaluation as mover + multiplier waves (qn_sym2r.hip.h); QN_OPT_EVAL_MOVER_MULTIPLIER
     int zig = (getenv("QN_S2_ZIGZAG") && atoi(getenv("QN_S2_ZIGZAG")) == 0) ? 0 : 1; // ... its two tiles in the other order in launches of odd parity (the L2 across evaluation launches); QN_OPT_EVAL_ZIGZAG
+    int fast_steps = 1; // the steady iteration's machine steps as straight-line code in the accept-reduce's and the update tiles' prologues (qn_s2_fast_step); QN_OPT_MACHINE_FAST_STEPS
     int touch = getenv("QN_S2_TOUCH") ? atoi(getenv("QN_S2_TOUCH")) : 8;    // TOUCH workgroups in the accept-reduce: rows per wave of H's tiles (0, 4, 6, 8, 10, 12, 16); QN_OPT_TOUCH_H_ROWS
     int touchq = getenv("QN_S2_TOUCHQ") ? atoi(getenv("QN_S2_TOUCHQ")) : 6; // ... in the update-reduce: rows of Q's tiles; QN_OPT_TOUCH_Q_ROWS
     int touch_delay = getenv("QN_S2_TOUCH_DELAY") ? atoi(getenv("QN_S2_TOUCH_DELAY")) : 32; // ... units of 64 clocks the accept-reduce's touching workgroups sleep first
@@ -512,6 +513,7 @@ extern "C" int qn_solver_set_option(qn_solver* s, int option, int value) {
     case QN_OPT_LU_FORCE_WAIT_EXPIRY: s->newton_lu_force_timeout = on ? 1 : 0; return QN_OK;
     case QN_OPT_BTB_PROJECT_IN_EVAL: s->no_projfold = !on; return QN_OK;
     case QN_OPT_EVAL_ZIGZAG: s->zig = on ? 1 : 0; return QN_OK;
+    case QN_OPT_MACHINE_FAST_STEPS: s->fast_steps = on ? 1 : 0; return QN_OK;
     case QN_OPT_PNEWTON_REUSE_FACTOR: s->pn_reuse = on ? 1 : 0; s->pn_factor_serial = 0; return QN_OK;
     case QN_OPT_LBFGS_UNIT_SCALING:
         if (s->method != QN_LBFGS) return fail(QN_ERROR_INPUT_PARAMS, "unit scaling belongs to an L-BFGS solver");

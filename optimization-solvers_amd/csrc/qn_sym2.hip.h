@@ -135,6 +135,8 @@ struct QnS2Args {
     int touch_delay, touchq_delay; // ... units of 64 clocks the accept-reduce's / the update-reduce's touching workgroups sleep before their first load
     int zig;                 // round 6: s2_evalr_kernel streams its two tiles in the other order in launches of odd parity (what the XCD's L2 still holds of the
                              // evaluation launch in front comes first: qn_sym2r.hip.h, ZIG-ZAG) -- the same bits
+    int fast;                // the steady iteration's two machine steps straight-line in the accept-reduce's and the update tiles' prologues (qn_s2_fast_step;
+                             // QN_OPT_MACHINE_FAST_STEPS) -- the same bits
 #ifdef QN_S2_STAMPS
     unsigned long long* dbg; // diagnostic build: dbg[((slot % 64) * 256 + workgroup) * 16 + k] = wall clock (10 ns) at stamp k
     int slot;
@@ -166,10 +168,49 @@ struct QnS2Lds {
 // (Measured again and dropped, round 3: the machine as ONE out-of-line function, now called from wave 0's prologue where no tile
 // window is live -- one copy of its code for the five kernels instead of five.  The call frame lives in scratch memory (400 bytes
 // per lane) and the machine then takes 8.4 us instead of 4-5: 11.0 k it/s against 12.3 k inlined, same box.)
+// what a serviced request leaves in the control block, one function per kind of request: qn_s2_advance and the straight-line steps of the
+// steady iteration (qn_s2_fast_step) consume through the same code
+template <bool BND = false> // returns false when the caller wanted the vectors of the point too (the machine does not run: QN_PH_REQ_VEC)
+__device__ __forceinline__ bool qn_s2_take_eval(QnCtl& c, const double* tot) {
+    const double f = 0.5 * tot[0] - tot[1]; // f = 1/2 xt'(Q xt) - b'xt
+    const double gd = tot[2] - tot[3];      // g(xt)'d = d'(Q xt) - b'd
+    c.st_gd0 = tot[4]; c.st_dnf = tot[5];
+    // (BND: a PROJECTED trial -- BackTrackingB, s2_proj_kernel -- was evaluated at a stored point, with d = 0: it says nothing about
+    // g'd, and it is not the point x + t d the memo speaks of)
+    const bool proj = BND && c.req_project != 0;
+    if (c.req_kind == QN_REQ_T && !c.gd0_valid && !proj) { c.gd0 = tot[4]; c.d_finite = tot[5] == 0.0; c.gd0_valid = 1; }
+    c.f_e = f; c.gd_e = gd;
+    c.n_oracle_evals++;
+    c.ev_par ^= 1; c.ev_kind = c.req_kind; c.ev_t = c.req_t;
+    if (c.req_kind == QN_REQ_T && !proj) { c.last_valid = 1; c.last_t = c.req_t; c.f_last = f; c.gd_last = gd; }
+    else c.last_valid = 0;
+    if (BND) c.last_projected = proj ? 1 : 0;
+    if (c.req_need_vectors) { c.phase = QN_PH_REQ_VEC; return false; } // the caller wants g+, y, s of this point too
+    return true;
+}
+__device__ __forceinline__ void qn_s2_take_vec(QnCtl& c, const double* tot) {
+    c.st_yy = tot[0]; c.st_ys = tot[1]; c.st_gg = tot[2]; c.st_ss = tot[3]; c.hp_sg = tot[4];
+}
+// Folded accept-reduce: the launch that formed g+, y, s of the accepted point ran the update tiles as well, BEFORE the machine
+// had seen ||s||, ||y|| (the tiles only need the vectors and the coefficients of the PENDING update, all known then).  Now that
+// the machine has consumed those sums: if it asks for exactly that pass, its tiles are done (the reduce launch is what is left);
+// if it does not (step or gradient change below tol: bfgs.rs:106-112 -- the run then ends at the next loop top), the tiles
+// have still applied the pending update to the stored matrix, which is all `pending` stands for.
+// (spec_tiles = the number of right-hand sides the tiles ran with: 2 = [y, g+] after an accepted step, 1 = g after the evaluation
+// at x that opens a run.)
+__device__ __forceinline__ void qn_s2_spec_tiles_settle(QnCtl& c) {
+    if (c.spec_tiles && c.phase != QN_PH_RUNNING && c.phase != QN_PH_REQ_VEC) {
+        const int ran = c.spec_tiles;
+        c.spec_tiles = 0;
+        if (c.phase == QN_PH_REQ_HPASS && c.serviced == 0 && c.hp_nrhs == ran) c.serviced = 1;
+        else if (c.pending) { c.pending = 0; c.n_hpasses++; c.n_hpass_rw++; }
+    }
+}
+
 template <bool BND = false> // (BND: the bounded variants' machine -- LEAN == 2, qn_ctl_step.hip.h -- and their QN_PH_REQ_DIR)
 __device__ __forceinline__ void qn_s2_advance(QnCtl& c, const double* tot, const QnVecs& V, const bool leader, double* scratch, const bool resume) {
     const int ph = c.phase;
-    bool run = resume; // (resume: the machine had stopped for the x-trace copy)
+    bool run = resume; // (resume: the machine had stopped for the x-trace copy, or a straight-line step has left it running)
     if (!resume) {
         if (ph == QN_PH_DONE) return;
         if (ph == QN_PH_IDLE) {
@@ -181,23 +222,10 @@ __device__ __forceinline__ void qn_s2_advance(QnCtl& c, const double* tot, const
             if (c.serviced != 2) return; // the request is still pending, or its tiles wait for their reduce launch
             c.serviced = 0;
             if (ph == QN_PH_REQ_EVAL) {
-                const double f = 0.5 * tot[0] - tot[1]; // f = 1/2 xt'(Q xt) - b'xt
-                const double gd = tot[2] - tot[3];      // g(xt)'d = d'(Q xt) - b'd
-                c.st_gd0 = tot[4]; c.st_dnf = tot[5];
-                // (BND: a PROJECTED trial -- BackTrackingB, s2_proj_kernel -- was evaluated at a stored point, with d = 0: it says nothing about
-                // g'd, and it is not the point x + t d the memo speaks of)
-                const bool proj = BND && c.req_project != 0;
-                if (c.req_kind == QN_REQ_T && !c.gd0_valid && !proj) { c.gd0 = tot[4]; c.d_finite = tot[5] == 0.0; c.gd0_valid = 1; }
-                c.f_e = f; c.gd_e = gd;
-                c.n_oracle_evals++;
-                c.ev_par ^= 1; c.ev_kind = c.req_kind; c.ev_t = c.req_t;
-                if (c.req_kind == QN_REQ_T && !proj) { c.last_valid = 1; c.last_t = c.req_t; c.f_last = f; c.gd_last = gd; }
-                else c.last_valid = 0;
-                if (BND) c.last_projected = proj ? 1 : 0;
-                if (c.req_need_vectors) { c.phase = QN_PH_REQ_VEC; return; } // the caller wants g+, y, s of this point too
+                if (!qn_s2_take_eval<BND>(c, tot)) return;
                 c.state = c.after_state;
             } else if (ph == QN_PH_REQ_VEC) {
-                c.st_yy = tot[0]; c.st_ys = tot[1]; c.st_gg = tot[2]; c.st_ss = tot[3]; c.hp_sg = tot[4];
+                qn_s2_take_vec(c, tot);
                 c.state = c.after_state;
             } else if (ph == QN_PH_REQ_HPASS) {
                 if (c.hp_nrhs == 2) { c.hp_yu = tot[0]; c.hp_ug = tot[1]; if (BND) c.hp_den = tot[2]; } // (hp_den: SR1's denominator, third column of its update-reduce)
@@ -215,19 +243,51 @@ __device__ __forceinline__ void qn_s2_advance(QnCtl& c, const double* tot, const
         }
     }
     if (run) ctl_scalar_run<BND ? 2 : 1>(c, V, scratch, leader); // (ONE call site: the machine is inlined, and it is large; LEAN: qn_ctl_step.hip.h)
-    // Folded accept-reduce: the launch that formed g+, y, s of the accepted point ran the update tiles as well, BEFORE the machine
-    // had seen ||s||, ||y|| (the tiles only need the vectors and the coefficients of the PENDING update, all known then).  Now that
-    // the machine has consumed those sums: if it asks for exactly that pass, its tiles are done (the reduce launch is what is left);
-    // if it does not (step or gradient change below tol: bfgs.rs:106-112 -- the run then ends at the next loop top), the tiles
-    // have still applied the pending update to the stored matrix, which is all `pending` stands for.
-    // (spec_tiles = the number of right-hand sides the tiles ran with: 2 = [y, g+] after an accepted step, 1 = g after the evaluation
-    // at x that opens a run.)
-    if (c.spec_tiles && c.phase != QN_PH_RUNNING && c.phase != QN_PH_REQ_VEC) {
-        const int ran = c.spec_tiles;
-        c.spec_tiles = 0;
-        if (c.phase == QN_PH_REQ_HPASS && c.serviced == 0 && c.hp_nrhs == ran) c.serviced = 1;
-        else if (c.pending) { c.pending = 0; c.n_hpasses++; c.n_hpass_rw++; }
+    qn_s2_spec_tiles_settle(c);
+}
+
+// THE STEADY ITERATION'S TWO STEPS, STRAIGHT-LINE.  The accept-reduce's and the update tiles' prologues are where the workgroup waits
+// for one lane's run of the machine, and in a steady iteration each of them sees ONE succession of states:
+//   accept-reduce: the trial's evaluation -> qn_st_mt_after_t (the Wolfe test) -> qn_st_after_ls -> req_eval_t's memo hit -> QN_PH_REQ_VEC
+//   update tiles:  the five sums of the accepted point -> qn_st_after_next -> QN_PH_REQ_HPASS
+// The generic machine -- dispatcher, guard loop, every other state's chained copies: ~4000 instructions inlined -- gets there too, at ~5 cycles per
+// issued instruction (tools/icache_probe.hip).  Here the control block as it arrives names the succession, so the same state functions are called one
+// after the other with the state a compile-time constant: the `state == X` tests fold, the stores are forwarded, and the code lies at the head of the
+// prologue.  One source: what is consumed is consumed by qn_s2_advance's own functions, what is decided is decided by qn_ctl_step.hip.h's.  A step that
+// leaves the machine RUNNING (the trial was not accepted and the next one is answered from the memo; a step below tol: QN_ST_ITER_END) hands over to
+// the generic loop, which resumes it; every other incoming state never leaves the generic path.
+// MEASURED (profiles/r07_a_*, against the parent commit, alternating on one box): in-kernel stamps -- the machine's run 1.6 -> 0.8 us in the accept-reduce, 2.2 -> 0.7 us
+// in the update tiles; rocprofv3 averages at n = 4096 -- accept-reduce 5.84 -> 5.38 us, update tiles 22.17 -> 21.97 (inside the parent's own range, and the same with the
+// accept-reduce's step alone: the fabric is busy with the first tile in front of that barrier; at n = 1024, where it is not, the update tiles' step is 0.4 us of 9);
+// headline median of 12 fresh processes 16 191 -> 16 557 it/s.  Not built: the accept-reduce's slot sums by waves 1..7 in front of the barrier (what they would hide
+// behind is now 0.8 us).
+// WHICH: 1 = an evaluation behind QN_ST_MT_AFTER_T (the accept-reduce), 2 = the accepted point's sums behind QN_ST_AFTER_NEXT (the update tiles),
+// 3 = either (the synchronous mode's one-workgroup launch, which runs every prologue's machine).
+template <int WHICH>
+__device__ __forceinline__ bool qn_s2_fast_trigger(const QnS2Args& a, const QnCtl& c) { // (uniform: every lane reads the same words)
+    if (!a.fast || c.serviced != 2) return false;
+    if ((WHICH & 1) && c.phase == QN_PH_REQ_EVAL && c.after_state == QN_ST_MT_AFTER_T && !c.req_need_vectors) return true;
+    if ((WHICH & 2) && !a.fold && c.phase == QN_PH_REQ_VEC && c.after_state == QN_ST_AFTER_NEXT) return true;
+    return false;
+}
+template <int WHICH> // (one lane; the trigger holds)
+__device__ __forceinline__ void qn_s2_fast_step(QnCtl& c, const double* tot) {
+    c.n_fast_steps++;
+    c.serviced = 0;
+    if ((WHICH & 1) && (!(WHICH & 2) || c.phase == QN_PH_REQ_EVAL)) {
+        if (qn_s2_take_eval<false>(c, tot)) {
+            c.state = QN_ST_MT_AFTER_T;
+            c.phase = QN_PH_RUNNING;
+            qn_st_mt_after_t<1>(c);
+            if (c.phase == QN_PH_RUNNING && c.state == QN_ST_AFTER_LS) qn_st_after_ls<1>(c);
+        }
+    } else {
+        qn_s2_take_vec(c, tot);
+        c.state = QN_ST_AFTER_NEXT;
+        c.phase = QN_PH_RUNNING;
+        qn_st_after_next<1>(c);
     }
+    qn_s2_spec_tiles_settle(c);
 }
 
 // a wave-uniform double out of lane `l` (uniform) of a per-lane value: the row-side inputs of a tile (x_i, d_i, s_i, u_i, y_i,
@@ -282,6 +342,10 @@ struct QnS2NoEarly { __device__ __forceinline__ void operator()() const {} };
 // GOBJ (generic objectives, qn_sym2g.hip.h): an evaluation's sums come from its combine launch -- a.gw rows -- which has ALSO staged the
 // vectors of the evaluated point (g+, y, x+, s) and their five sums (table columns QN_S2_VCOL ..): when the machine accepts the point
 // and asks for them (QN_PH_REQ_VEC), this prologue hands them over at once and lets the machine go on -- no launch in between.
+// (Measured and dropped, profiles/r07_a_*: the update-reduce with touch workgroups -- s2_hreduce_kernel<false, false, 32>, which plan_s2_args never combines with
+// the folded accept-reduce -- told at COMPILE time that it has nothing to decide, so that the kernel holds no copy of the machine: 27.5 -> 6.6 KB of code, in-kernel
+// stamps barrier 2.9 -> 1.9 us after entry -- and the launch's rocprofv3 average 4.84 us with the machine's code, 4.88 without, the parent's 4.97, five alternating
+// repetitions each on one box: the launch is not waiting for its code.)
 template <int KIND, bool SHARD = false, class Early = QnS2NoEarly, bool GOBJ = false, bool BND = false>
 __device__ __forceinline__ void qn_s2_prologue_w0(const QnS2Args& a, QnS2Lds& L, Early&& early = Early()) {
     static_assert(!(BND && (SHARD || GOBJ)), "the bounded variants run on one rank, on the quadratic");
@@ -480,16 +544,27 @@ __device__ __forceinline__ void qn_s2_prologue_w0(const QnS2Args& a, QnS2Lds& L,
         if (lane == 0) c.bt_diff2 = d2; // (backtracking_b.rs:33-34; the evaluation this launch may run is AT the stored projected point)
     }
     QN_S2_STAMP(10);
+    // the steady iteration's step of this prologue, straight-line (qn_s2_fast_step).  0: not taken, 1: taken and a request is out, 2: taken and the
+    // machine is still running -- the generic loop below resumes it
+    constexpr int kFast = (BND || GOBJ || SHARD) ? 0 : (KIND == QN_S2_VEC ? 1 : (KIND == QN_S2_HTILE ? 2 : (KIND == QN_S2_ADVANCE ? 3 : 0)));
+    int fast = 0;
+    if constexpr (kFast != 0) {
+        if (qn_s2_fast_trigger<kFast>(a, c)) { // (uniform)
+            int running = 0;
+            if (lane == 0) { qn_s2_fast_step<kFast>(c, tot); running = c.phase == QN_PH_RUNNING; }
+            fast = 1 + __builtin_amdgcn_readfirstlane(running);
+        }
+    }
     QnVecs V{};
     V.n = a.n; V.n_pad = a.np; V.trace = a.trace;
     // (two copies of the loop on purpose: the generic-objective one -- a second entry into the machine with the staged sums -- runs in
     // one-workgroup launches only; written as one loop with run-time flags it changed the code of EVERY kernel's prologue, and the two
     // small kernels of the benchmark iteration, whose critical path is the machine, measured 0.3-0.65 us slower: profiles/r05_f_*)
     if constexpr (!GOBJ) {
-        for (int guard = 0; guard < 64; ++guard) { // (the n <= 5 reference-order code of the machine is never reached on this path: no scratch)
+        for (int guard = 0; guard < 64 && fast != 1; ++guard) { // (the n <= 5 reference-order code of the machine is never reached on this path: no scratch)
             int need_x = 0;
             if (lane == 0) {
-                qn_s2_advance<BND>(c, tot, V, leader, &L.red[0][0], guard > 0);
+                qn_s2_advance<BND>(c, tot, V, leader, &L.red[0][0], guard > 0 || fast == 2);
                 need_x = c.phase == QN_PH_RUNNING && c.state == QN_ST_ITER_END;
             }
             need_x = __builtin_amdgcn_readfirstlane(need_x);

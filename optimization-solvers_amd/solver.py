@@ -64,6 +64,7 @@ OPTIONS = {
     "pnorm_nontemporal": 24,
     "pnorm_rows_per_wave": 25,
     "lbfgs_unit_scaling": 26,
+    "machine_fast_steps": 27,
 }
 OPT_GENERIC_KERNELS = 1
 OPT_DEFERRED_UPDATE_STEP = 2
@@ -91,6 +92,7 @@ OPT_PNEWTON_REUSE_FACTOR = 23
 OPT_PNORM_NONTEMPORAL = 24
 OPT_PNORM_ROWS_PER_WAVE = 25
 OPT_LBFGS_UNIT_SCALING = 26
+OPT_MACHINE_FAST_STEPS = 27
 
 
 class SolverError(Exception):
