@@ -406,6 +406,11 @@ typedef struct {
     /* second-generation path, last qn_minimize call: steps of the state machine that a kernel's prologue took as the straight-line code of the steady
      * iteration instead of the generic machine (QN_OPT_MACHINE_FAST_STEPS; one in the accept-reduce and one in the update tiles per steady iteration) */
     uint64_t fast_machine_steps;
+    /* second-generation path, last qn_minimize call: update passes that applied the pending update in registers and did NOT store the matrix
+     * (QN_OPT_HPASS_STORE_SKIP: the pass behind them applies two updates and stores), and the bytes of H the call's passes really read and wrote --
+     * h_bytes stays the algorithmic size, every pass counted as one read and one write of the streamed tiles */
+    uint64_t n_hpass_nostore;
+    uint64_t h_bytes_moved;
 } qn_stats;
 #define QN_PATH_FUSED 1u       /* fused fast path (device quadratic, memoised): no kernel but the streaming ones touches an n-vector */
 #define QN_PATH_SYM 2u         /* ... on the symmetric half of H and Q only */
@@ -458,7 +463,8 @@ typedef enum {
     QN_OPT_PNORM_NONTEMPORAL = 24,         /* [-1] PnormDescent: inverse_p through non-temporal loads; 1 / 0 force it on / off, -1 (a NUMBER): by size -- on once the matrix is past the Infinity Cache's reach (~230 MB, n ~ 5400) -- the same bits */
     QN_OPT_PNORM_ROWS_PER_WAVE = 25,       /* [0] ... rows a wave of its direction kernel holds in flight: 2 or 4 (a NUMBER); 0: by size (2 up to n = 8192) -- the same bits */
     QN_OPT_LBFGS_UNIT_SCALING = 26,        /* [0] L-BFGS: gamma = 1 in every iteration (H0 = I): the iterates of dense BFGS from H = I while no pair has been dropped */
-    QN_OPT_MACHINE_FAST_STEPS = 27         /* [1] second-generation path: the accept-reduce's and the update tiles' prologues run the steady iteration's step of the state machine as straight-line code in front of the generic machine (csrc/qn_sym2.hip.h, qn_s2_fast_step); 0: the generic machine alone -- the same bits */
+    QN_OPT_MACHINE_FAST_STEPS = 27,        /* [1] second-generation path: the accept-reduce's and the update tiles' prologues run the steady iteration's step of the state machine as straight-line code in front of the generic machine (csrc/qn_sym2.hip.h, qn_s2_fast_step); 0: the generic machine alone -- the same bits */
+    QN_OPT_HPASS_STORE_SKIP = 28           /* [1] second-generation path, one rank, BFGS / DFP unbounded, without the folded accept-reduce and the tail reduce: an update pass that finds ONE update pending applies it in registers and does not store H; the next pass applies that update and the newer one to the stored H and stores (csrc/qn_sym2.hip.h, s2_hpass_kernel; qn_stats.n_hpass_nostore, h_bytes_moved); 0: every pass stores -- the same bits.  Read once per qn_minimize call */
 } qn_option;
 int qn_solver_set_option(qn_solver* s, int option, int value);
 

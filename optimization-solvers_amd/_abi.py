@@ -61,7 +61,7 @@ class Stats(C.Structure):
                 ("t_hreduce_ms", C.c_double), ("t_ereduce_ms", C.c_double), ("n_hreduce_timed", C.c_uint64), ("n_ereduce_timed", C.c_uint64),
                 ("total_xchg_vector", C.c_uint64), ("total_xchg_scalar", C.c_uint64),
                 ("t_newton_ms", C.c_double), ("n_newton_timed", C.c_uint64), ("newton_lu_sync_timeouts", C.c_uint64),
-                ("fast_machine_steps", C.c_uint64)]
+                ("fast_machine_steps", C.c_uint64), ("n_hpass_nostore", C.c_uint64), ("h_bytes_moved", C.c_uint64)]
 
 
 PATH_FUSED, PATH_SYM, PATH_SYM_GENERIC, PATH_PIPELINED, PATH_SYM2, PATH_TILES1, PATH_VECTOR, PATH_PNEWTON = 1, 2, 4, 8, 16, 32, 64, 128

@@ -121,10 +121,16 @@ struct QnCtl {
 
     // ---- pending symmetric rank-2 update: H_true = H_stored + c_su (sp up' + up sp') + c_ss sp sp' + c_uu up up'
     //      (QN_METHOD_BROYDEN: the rank-1, non-symmetric H_true = H_stored + c_ss sp up' with sp = a = s - H y, up = w = H' s, c_ss = 1 / s.y)
+    //      `pending` counts the updates that are not in the stored H yet: 0, 1, or -- where the update tiles skip every second store (hskip) -- 2.
+    //      The NEWEST one is (S0[sc], UN, c_ss / c_su / c_uu): what the evaluations form the lazy direction from.  With two pending the OLDER one
+    //      is (SO, UO, o_ss / o_su / o_uu): the update-reduce of a pass that did not store moves the vectors there before it overwrites UN.
     int32_t pending;
     int32_t spec_tiles; // sym2, folded accept-reduce: the launch that formed the vectors of the accepted point ran the update tiles of the
                         // pass the machine is about to ask for (qn_sym2.hip.h, s2_hpass_kernel); cleared when that request is met
     double c_ss, c_su, c_uu;
+    double o_ss, o_su, o_uu; // the older pending update's coefficients (pending == 2)
+    int32_t hskip;           // this run's update tiles do not store a pass that finds ONE update pending (s2_hpass_kernel, QN_OPT_HPASS_STORE_SKIP; set by the host per call)
+    int32_t hskip_pad;
 
     // ---- evaluation results / memo ----
     double f_e, gd_e;            // result handed to the state machine
@@ -146,5 +152,6 @@ struct QnCtl {
 
     // ---- counters ----
     uint64_t n_oracle_calls, n_oracle_evals, n_hpasses, n_hpass_rw, n_iterations;
+    uint64_t n_hpass_nostore; // update passes of this call that left the stored H as it was (hskip): the update they applied in registers stays pending
     uint64_t n_fast_steps; // sym2: steps of the machine taken straight-line in a prologue (qn_sym2.hip.h qn_s2_fast_step); zeroed by the host per call
 };

@@ -71,7 +71,7 @@ __device__ __forceinline__ void qn_st_begin(QnCtl& c) { // ls_solver.rs:74-76: o
     // known: the last accepted evaluation IS f, g at x_k, and the direction is pending in its lazy form.
     if (!c.warm) { c.have_cur_eval = 0; c.have_dir = 0; c.last_valid = 0; c.gg_valid = 0; }
     else c.last_valid = 0;
-    c.n_oracle_calls = 0; c.n_oracle_evals = 0; c.n_hpasses = 0; c.n_hpass_rw = 0; c.n_iterations = 0;
+    c.n_oracle_calls = 0; c.n_oracle_evals = 0; c.n_hpasses = 0; c.n_hpass_rw = 0; c.n_hpass_nostore = 0; c.n_iterations = 0;
     c.status = -1;
     c.state = QN_ST_LOOP_TOP;
 }
@@ -161,10 +161,16 @@ __device__ __forceinline__ bool qn_st_after_u(QnCtl& c) { // coefficients of bfg
     const double yu = c.hp_yu;
     double c_ss, c_su, c_uu;
     qn_update_coeffs(c.method, c.ys, yu, c_ss, c_su, c_uu, c.hp_den);
-    c.c_ss = c_ss; c.c_su = c_su; c.c_uu = c_uu;
     c.n_hpasses++;
     if (c.pending) c.n_hpass_rw++;
-    c.pending = 1;
+    if (c.hskip && c.pending == 1) { // the pass applied the pending update in registers and did not store (s2_hpass_kernel's read pass): it stays pending
+        c.o_ss = c.c_ss; c.o_su = c.c_su; c.o_uu = c.c_uu; // as the OLDER of two (its vectors: SO, UO -- moved there by the pass's update-reduce)
+        c.pending = 2;
+        c.n_hpass_nostore++;
+    } else {
+        c.pending = 1; // (nothing was pending, one update was and has been stored, or two were: the write pass)
+    }
+    c.c_ss = c_ss; c.c_su = c_su; c.c_uu = c_uu;
     c.sc ^= 1; // the staged s becomes the pending s; the new u is already in UN
     c.dir_mode = 1; c.dir_ug = c.hp_ug; c.dir_sg = c.hp_sg; // next direction formed on the fly by the evaluations
     c.gd0_valid = 0; c.d_finite = 0;

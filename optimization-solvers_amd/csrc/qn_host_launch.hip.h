@@ -391,7 +391,7 @@ static int place_h(Run& r) {
     QnCtl* pc = s->hrep; // (pinned, device-mapped; the report area is free between calls)
     memcpy(pc, s->hctl, sizeof(QnCtl));
     pc->phase = QN_PH_REQ_HPASS; pc->serviced = 0; pc->hp_nrhs = 1; pc->pending = 0; pc->after_state = QN_ST_AFTER_DIR; pc->sym2 = 1; pc->fused = 1;
-    pc->spec_tiles = 0; pc->sc = 0; pc->xc = 0;
+    pc->spec_tiles = 0; pc->sc = 0; pc->xc = 0; pc->hskip = 0;
     // ... and, in front of every timed pass, what an iteration has in front of it: two evaluations (Q's half streamed twice).  Timed
     // alone on H the update kernel showed the same 24.4 us on allocations where, in the run, it then took 29.6-30.3 us (2-3 processes
     // in 20, tools/modes_ab.sh): the slow mode is H sharing the Infinity Cache with Q, not H by itself.

@@ -117,6 +117,8 @@ static int plan_run(Run& r, qn_solver* s, qn_linesearch* ls, const qn_oracle* o,
     }
     r.sym2 = r.sym && (s2_shape || s2sh_shape);
     h->sym2 = r.sym2 ? 1 : 0;
+    h->hskip = 0; // (plan_s2_args: the second-generation path's plain single-rank runs)
+    if (!r.sym2) QNCHK(flush_older(s)); // (two updates pending is a state of that path alone)
     r.bnd = r.sym2 && (s->bounded || ls_bounded || s->method == QN_SR1); // (SR1: the BND prologues also carry its third update-reduce column)
     if ((s->bounded || ls_bounded) && r.fused && !r.bnd) return fail(QN_ABNORMAL_TERMINATION, "bounded run on a fused path that is not the second-generation one");
     if (s->method == QN_SR1 && r.fused && !r.sym2) return fail(QN_ABNORMAL_TERMINATION, "SR1 on a fused path that is not the second-generation one");
@@ -262,6 +264,16 @@ static int plan_s2_args(Run& r) {
     s2_cache_policy(c->world > 1 ? (size_t)s->T.rpr * s->T.n_pad * 8 / 2 : (size_t)s->T.n_pad * s->T.n_pad * 8 / 2, &a.nt, &a.ntq);
     if (getenv("QN_S2_NT")) a.nt = atoi(getenv("QN_S2_NT"));    // (diagnostics: tools/README.md)
     if (getenv("QN_S2_NTQ")) a.ntq = atoi(getenv("QN_S2_NTQ"));
+    // EVERY SECOND UPDATE PASS STORES (s2_hpass_kernel's read and write passes; QN_OPT_HPASS_STORE_SKIP, read here once per call): the plain single-rank
+    // instances alone -- not row-sharded, bounded or SR1 runs, the folded accept-reduce, the tail reduce, the first-generation tiles or the generic
+    // objectives' kernels, which all keep at most one update pending.  A call of those that finds two applies the older one first.
+    {
+        QnCtl* h = s->hctl;
+        const bool skip = s->hpass_skip && c->world == 1 && !r.gobj && !r.bnd && !r.tiles1 && !a.fold && !a.tred && s->method != QN_SR1;
+        if (!skip) QNCHK(flush_older(s));
+        h->hskip = skip ? 1 : 0;
+        a.so = fused_so(s); a.uo = fused_uo(s);
+    }
     // (nothing is uploaded here: the FIRST launch of the call reads the control block from the pinned, device-mapped mirror
     // itself -- QnS2Args.ctl_first.  Round 3 went from hipMemcpyAsync (~8 us in front of the first kernel of every call) to a
     // one-workgroup upload launch (~4 us); now there is neither.  The host does not write the mirror again before the batch's
@@ -473,6 +485,7 @@ static void finish_stats(Run& r) {
     s->stats.oracle_evals = h->n_oracle_evals;
     s->stats.h_passes = h->n_hpasses;
     s->stats.fast_machine_steps = h->n_fast_steps;
+    s->stats.n_hpass_nostore = h->n_hpass_nostore;
     uint64_t shard = (uint64_t)s->T.rpr * (uint64_t)s->T.n_pad * 8ull;
     const uint64_t full_shard = shard;
     if (r.sym || r.sym_generic) shard = (uint64_t)s->sym_nb * (uint64_t)(s->sym_nb + 1) / 2ull * (uint64_t)QN_TB * QN_TB * 8ull; // the streamed tiles
@@ -485,7 +498,9 @@ static void finish_stats(Run& r) {
         shard = (nt - nbl) * (uint64_t)QN_TB * QN_TB * 8ull + nbl * 73728ull;
     }
     s->stats.h_bytes = (h->n_hpasses + h->n_hpass_rw) * shard;
-    if (r.sym2) s->stats.h_bytes = 2 * h->n_hpasses * shard; // (its one branch-free body writes every pass back, pending update or not)
+    if (r.sym2) s->stats.h_bytes = 2 * h->n_hpasses * shard; // (the ALGORITHMIC size of a pass -- every tile read and written once -- whether the pass stored or not:
+                                                             //  what the roofline fractions are quoted against; h_bytes_moved below is what went over the fabric)
+    s->stats.h_bytes_moved = s->stats.h_bytes - h->n_hpass_nostore * shard; // (a pass that did not store moved its tiles once: s2_hpass_kernel's read pass)
     s->stats.obj_bytes = (r.oracle_tpl == QN_ORACLE_QUAD) ? h->n_oracle_evals * (r.sym ? shard : full_shard) : 0;
     if (r.obj && r.obj->kind == OBJ_LOGSUMEXP) // one pass over this rank's rows of A per evaluation (two for n > 16384)
         s->stats.obj_bytes = h->n_oracle_evals * (uint64_t)r.obj->TA.rpr * (uint64_t)r.obj->T.n_pad * 8ull * ((r.obj->lse_kch && !r.obj->lse_two_pass) ? 1ull : 2ull);

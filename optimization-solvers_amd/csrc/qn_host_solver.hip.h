@@ -45,6 +45,7 @@ struct qn_solver {
     bool no_pair = false;      // diagnostics: the general evaluation kernel where the two-items-and-a-sliver instance would run
     int ring = (getenv("QN_S2_RING") && atoi(getenv("QN_S2_RING")) == 0) ? 0 : 1; // the pair instance's evaluation as mover + multiplier waves (qn_sym2r.hip.h); QN_OPT_EVAL_MOVER_MULTIPLIER
     int zig = (getenv("QN_S2_ZIGZAG") && atoi(getenv("QN_S2_ZIGZAG")) == 0) ? 0 : 1; // ... its two tiles in the other order in launches of odd parity (the L2 across evaluation launches); QN_OPT_EVAL_ZIGZAG
+    int hpass_skip = 1; // the update tiles store every second pass and apply two pending updates in registers in between (s2_hpass_kernel, QnCtl.hskip); QN_OPT_HPASS_STORE_SKIP
     int fast_steps = 1; // the steady iteration's machine steps as straight-line code in the accept-reduce's and the update tiles' prologues (qn_s2_fast_step); QN_OPT_MACHINE_FAST_STEPS
     int touch = getenv("QN_S2_TOUCH") ? atoi(getenv("QN_S2_TOUCH")) : 8;    // TOUCH workgroups in the accept-reduce: rows per wave of H's tiles (0, 4, 6, 8, 10, 12, 16); QN_OPT_TOUCH_H_ROWS
     int touchq = getenv("QN_S2_TOUCHQ") ? atoi(getenv("QN_S2_TOUCHQ")) : 6; // ... in the update-reduce: rows of Q's tiles; QN_OPT_TOUCH_Q_ROWS
@@ -113,7 +114,7 @@ struct qn_solver {
     DevBuf<double> lb_ring, lb_part, lb_small; // QN_LBFGS (qn_lbfgs.hip.h): S and Y, [2][lb_m + 1][n_pad]; the Gram kernel's shares; Gram matrices and coefficients
     DevBuf<double> bounds_block; // lb, ub (solver), llb, lub (bounded line search): 4 n_pad vectors
     int bounded = 0;
-    DevBuf<double> fused_block; // X0[2], S0[2], G, GT, Y, UN, UP, VV (10 n_pad vectors)
+    DevBuf<double> fused_block; // X0[2], S0[2], G, GT, Y, UN, UP, VV (10 n_pad vectors), then the older of two pending updates' s and u (fused_so, fused_uo)
     DevBuf<double> fused_evp, fused_hpp;
     int fused_nblk = 0;
     DevBuf<QnCtl> ctl;     // device
@@ -197,7 +198,7 @@ static void prof_collect(qn_solver* s) {
 static int solver_alloc_fused(qn_solver* s, bool sym) {
     const size_t np = s->T.n_pad;
     hipStream_t st = s->ctx->stream;
-    QNCHK(s->fused_block.ensure(10 * np, st));
+    QNCHK(s->fused_block.ensure(12 * np, st)); // (the last two: fused_so / fused_uo)
     const int nblk = sym ? (int)(np / QN_TB) : s->T.rpr / s->R; // partial-sum rows: 128-row blocks or R-row workgroups
     if (sym) {
         QNCHK(s->sym_part.ensure((size_t)nblk * nblk * 2 * QN_TB, st));
@@ -514,6 +515,7 @@ extern "C" int qn_solver_set_option(qn_solver* s, int option, int value) {
     case QN_OPT_BTB_PROJECT_IN_EVAL: s->no_projfold = !on; return QN_OK;
     case QN_OPT_EVAL_ZIGZAG: s->zig = on ? 1 : 0; return QN_OK;
     case QN_OPT_MACHINE_FAST_STEPS: s->fast_steps = on ? 1 : 0; return QN_OK;
+    case QN_OPT_HPASS_STORE_SKIP: s->hpass_skip = on ? 1 : 0; return QN_OK; // (read once per call: plan_s2_args)
     case QN_OPT_PNEWTON_REUSE_FACTOR: s->pn_reuse = on ? 1 : 0; s->pn_factor_serial = 0; return QN_OK;
     case QN_OPT_LBFGS_UNIT_SCALING:
         if (s->method != QN_LBFGS) return fail(QN_ERROR_INPUT_PARAMS, "unit scaling belongs to an L-BFGS solver");
@@ -563,9 +565,32 @@ extern "C" size_t qn_solver_n(const qn_solver* s) { return s->n; }
 extern "C" size_t qn_solver_k(const qn_solver* s) { return (size_t)s->hctl->k; }
 extern "C" double qn_solver_tol(const qn_solver* s) { return s->tol; }
 
+// TWO UPDATES PENDING (QnCtl.pending == 2: a call whose last update pass did not store -- s2_hpass_kernel's read pass).  Only the second-generation
+// path's plain single-rank kernels know that state; everything else -- the canonical buffers, the getters, the other paths, a run with the option
+// off -- knows at most one.  So whoever is about to look applies the OLDER update to the stored H first: the pass every other flush is (H += the
+// rank-2 term, the same per-element expression as the tiles'), with the older update's vectors and coefficients.  The newer one stays pending.
+static double* fused_so(qn_solver* s) { return (double*)s->fused_block + 10 * (size_t)s->T.n_pad; }
+static double* fused_uo(qn_solver* s) { return (double*)s->fused_block + 11 * (size_t)s->T.n_pad; }
+static int ensure_full_h(qn_solver* s);
+static int launch_hpass_R(qn_solver* s, const QnHPassArgs& a);
+static QnHPassArgs hpass_args(qn_solver* s, int expect_phase);
+static int poke_ctl(qn_solver* s);
+static int flush_older(qn_solver* s) {
+    if (s->hctl->pending != 2) return QN_OK;
+    QNCHK(ensure_full_h(s));
+    QnHPassArgs a = hpass_args(s, -1);
+    a.sp = fused_so(s); a.up = fused_uo(s);
+    a.force_nrhs = 0; a.force_pending = 1;
+    a.c_ss = s->hctl->o_ss; a.c_su = s->hctl->o_su; a.c_uu = s->hctl->o_uu;
+    QNCHK(launch_hpass_R(s, a));
+    s->hctl->pending = 1;
+    return poke_ctl(s);
+}
+
 // canonical buffers <- fused buffers (the lazy half of qn_minimize's export)
 static int fused_export(qn_solver* s) {
     s->warm_obj = 0; // whoever asks for the canonical buffers may change them: the next call starts from scratch
+    QNCHK(flush_older(s)); // (the canonical state holds one pending update)
     if (!s->fused_live) return QN_OK;
     qn_context* c = s->ctx;
     const QnCtl* h = s->hctl;

@@ -142,6 +142,8 @@ struct QnS2Args {
     int slot;
     int swz;                 // diagnostic build: workgroup g takes the items of workgroup g ^ swz (which XCD streams which tiles: QN_S2_SWZ)
 #endif
+    double *so, *uo;         // the OLDER of two pending updates' s and u (QnCtl.pending == 2; s2_hpass_kernel's read pass, QN_OPT_HPASS_STORE_SKIP): written by the
+                             // update-reduce of a pass that did not store, read by the next pass's tiles -- behind everything else: nothing in front moves
 };
 #ifdef QN_S2_STAMPS
 #define QN_S2_WG(a) ((int)blockIdx.x ^ (a).swz)
@@ -1504,6 +1506,18 @@ __global__ __launch_bounds__(QN_S2_TPB, 2) void s2_hpass_kernel(const QnS2Args a
     QnS2HVec v0;
     double s1_r, y_r;
     v2d s1_c, y_c;
+    // EVERY SECOND PASS STORES (the plain single-rank instances; QnCtl.hskip).  The stored H has to be current only when somebody reads it, and the
+    // only reader in a run is this kernel.  A pass that finds ONE update pending applies it in registers, forms its sums on the result and does not
+    // store (the read pass: half the bytes); the update it leaves unstored becomes the OLDER of two, and the next pass applies the older and then the
+    // newer one to the same stored H -- per element the operations of two storing passes in the same order, a store and a load of an f64 in between
+    // being the identity -- and stores (the write pass).  Which kind a pass is the control block says, behind the barrier: a uniform branch, one kernel.
+    // w0: the older update's entries of the first item, requested with the others (used by the write pass alone).
+    constexpr bool PLAIN = !FOLD && !SHARD && !TRED && !SR1;
+    // (they wait in LDS, a private place per lane: held in registers from one item to the next they were live through the other passes' row loops too)
+    // (Measured and dropped, profiles/r08_a_headline_ab.txt: the first item's older entries requested IN FRONT of the barrier -- waves 1..7 with their other entries, wave 0
+    // behind its prologue -- instead of behind it by the write pass alone: no scratch either, and 17 427 against 17 483 it/s, medians of 8 alternating processes.)
+    __shared__ v2d wo_c[2][PLAIN ? QN_S2_TPB : 1];
+    __shared__ double wo_r[2][PLAIN ? QN_S2_TPB : 1];
     auto vec_spec = [&]() {
         const int ir = I * QN_TB + wave * QN_S2_RPW + (lane & 15), jc = J * QN_TB + qn_s2_col(I == J, lane, wave);
         QnS2HReq spec;
@@ -1608,8 +1622,19 @@ __global__ __launch_bounds__(QN_S2_TPB, 2) void s2_hpass_kernel(const QnS2Args a
     const bool fold = FOLD && mine == 2; // (uniform)
     QnS2HReq q;
     bool nrhs2;
+    bool two = false, nost = false; // (uniform) the write pass: two updates pending; the read pass: one, not stored
+    double o_ss = 0.0, o_su = 0.0, o_uu = 0.0;
     {
         const QnCtl& c = L.c;
+        if (PLAIN) {
+            two = __builtin_amdgcn_readfirstlane(c.pending == 2) != 0;
+            nost = __builtin_amdgcn_readfirstlane(c.hskip != 0 && c.pending == 1 && c.hp_nrhs == 2) != 0;
+            o_ss = c.o_ss; o_su = c.o_su; o_uu = c.o_uu;
+            if (two) { // (uniform)
+                const int ir = I * QN_TB + wave * QN_S2_RPW + (lane & 15), jc = J * QN_TB + qn_s2_col(I == J, lane, wave);
+                wo_r[0][tid] = a.so[ir]; wo_r[1][tid] = a.uo[ir]; wo_c[0][tid] = ld2(a.so + jc); wo_c[1][tid] = ld2(a.uo + jc);
+            }
+        }
         q.pending = c.pending != 0;
         q.c_ss = c.c_ss; q.c_su = c.c_su; q.c_uu = c.c_uu;
         q.sp = a.F.S0 + (size_t)c.sc * np;
@@ -1682,10 +1707,30 @@ __global__ __launch_bounds__(QN_S2_TPB, 2) void s2_hpass_kernel(const QnS2Args a
         const size_t rstride = has_next ? np : 0; // (none left: every lane re-reads one 16-byte word -- of this item, or the sliver's row)
         double c0x = 0.0, c0y = 0.0, c1x = 0.0, c1y = 0.0;
         double racc[QN_S2_RPW];
+        // (three straight-line copies of the sixteen rows -- the write pass, the read pass, every other pass: as uniform branches inside ONE copy the
+        // two differences cut it into blocks across which the rows' broadcast scalars no longer fit the scalar registers)
+        auto rows = [&](auto two_c, auto st_c) __attribute__((always_inline)) {
+        constexpr bool TWO = decltype(two_c)::value, ST = decltype(st_c)::value;
+        double sro = 0.0, uro = 0.0; // (the write pass: the older update's entries)
+        v2d sjo = {0.0, 0.0}, ujo = {0.0, 0.0};
+        if constexpr (TWO) { sro = wo_r[0][PLAIN ? tid : 0]; uro = wo_r[1][PLAIN ? tid : 0]; sjo = wo_c[0][PLAIN ? tid : 0]; ujo = wo_c[1][PLAIN ? tid : 0]; }
 #pragma unroll
         for (int r = 0; r < QN_S2_RPW; ++r) { // row r of the wave's 16
             v2d hn = h[r];
             h[r] = qn_sym_ld<NT>(hnext + (size_t)r * rstride); // the register this row frees takes the same row of the next item at once
+            if constexpr (TWO) { // the older update first: what the pass that did not store applied
+                const double si = qn_lane_bcast(sro, r), ui = qn_lane_bcast(uro, r);
+                if (BFGS || SR1) {
+                    hn.x = hn.x + o_su * (si * ujo.x + ui * sjo.x);
+                    hn.y = hn.y + o_su * (si * ujo.y + ui * sjo.y);
+                }
+                hn.x = hn.x + o_ss * (si * sjo.x);
+                hn.y = hn.y + o_ss * (si * sjo.y);
+                if (!BFGS || SR1) {
+                    hn.x = hn.x + o_uu * (ui * ujo.x);
+                    hn.y = hn.y + o_uu * (ui * ujo.y);
+                }
+            }
             const double si = qn_lane_bcast(sr, r), ui = qn_lane_bcast(ur, r);
             if (BFGS || SR1) {
                 hn.x = hn.x + c_su * (si * uj.x + ui * sj.x);
@@ -1697,7 +1742,7 @@ __global__ __launch_bounds__(QN_S2_TPB, 2) void s2_hpass_kernel(const QnS2Args a
                 hn.x = hn.x + c_uu * (ui * uj.x);
                 hn.y = hn.y + c_uu * (ui * uj.y);
             }
-            qn_sym_st<NT>(hbase + (size_t)r * np, hn);
+            if constexpr (ST) qn_sym_st<NT>(hbase + (size_t)r * np, hn); // (the read pass leaves the stored row as it is)
             const double y0 = qn_lane_bcast(y0r, r), y1 = qn_lane_bcast(y1r, r);
             double t0 = hn.x * a0.x;
             t0 = __builtin_fma(hn.y, a0.y, t0);
@@ -1716,11 +1761,20 @@ __global__ __launch_bounds__(QN_S2_TPB, 2) void s2_hpass_kernel(const QnS2Args a
             c1x = __builtin_fma(hn.x, y1, c1x);
             c1y = __builtin_fma(hn.y, y1, c1y);
         }
+        };
+        if constexpr (PLAIN) {
+            if (two) rows(std::true_type{}, std::true_type{}); // (uniform)
+            else if (nost) rows(std::false_type{}, std::false_type{});
+            else rows(std::false_type{}, std::true_type{});
+        } else rows(std::false_type{}, std::true_type{});
         if (!qn_s2_col_on(diag, lane, wave)) { c0x = 0.0; c0y = 0.0; c1x = 0.0; c1y = 0.0; }
         // the next item's vector entries go out now: they fly while this item's sums are folded, exchanged and stored
+        double nso_r = 0.0, nuo_r = 0.0; // (the write pass: the older update's entries of the next item, on their way to LDS)
+        v2d nso_c = {0.0, 0.0}, nuo_c = {0.0, 0.0};
         if (has_next) {
             const int irn = In * QN_TB + wave * QN_S2_RPW + (lane & 15), ccn = qn_s2_col(In == Jn, lane, wave);
             qn_s2_hvec_load<!FOLD>(q, irn, Jn * QN_TB + ccn, v0);
+            if (PLAIN && two) { nso_r = a.so[irn]; nuo_r = a.uo[irn]; nso_c = ld2(a.so + Jn * QN_TB + ccn); nuo_c = ld2(a.uo + Jn * QN_TB + ccn); }
             if (FOLD) { // (blocks 2 (it + 1), 2 (it + 1) + 1 of the list)
                 const int rr = wave * QN_S2_RPW + (lane & 15), bI = 2 * (it + 1), bJ = bI + 1;
                 v0.y0_r = fv[bI][0][rr]; v0.y1_r = fv[bI][1][rr];
@@ -1731,6 +1785,7 @@ __global__ __launch_bounds__(QN_S2_TPB, 2) void s2_hpass_kernel(const QnS2Args a
             unsigned r = sl.D * QN_TB + sl.row, c = sl.D * QN_TB + 2 * lane;
             asm volatile("" : "+v"(r), "+v"(c));
             qn_s2_hvec_load<true>(q, r, c, v0);
+            if (PLAIN && two) { nso_r = a.so[r]; nuo_r = a.uo[r]; nso_c = ld2(a.so + c); nuo_c = ld2(a.uo + c); }
         }
         if (it == 0) { qn_keepalive(racc[0]); QN_S2_STAMP(3); QN_S2_STAMP_T(12, 448); }
         if (it == 1) { qn_keepalive(racc[0]); QN_S2_STAMP(6); QN_S2_STAMP_T(13, 448); }
@@ -1754,12 +1809,27 @@ __global__ __launch_bounds__(QN_S2_TPB, 2) void s2_hpass_kernel(const QnS2Args a
             else qn_s2_slot_st<TRED>(a.part + (unsigned)(((J * a.nb + I) * 2 + crhs) * QN_TB + c), acc);
         }
         if (it == 0) QN_S2_STAMP(5);
+        if (PLAIN && two) { wo_r[0][PLAIN ? tid : 0] = nso_r; wo_r[1][PLAIN ? tid : 0] = nuo_r; wo_c[0][PLAIN ? tid : 0] = nso_c; wo_c[1][PLAIN ? tid : 0] = nuo_c; } // (uniform)
         if (!has_next) break;
         I = In; J = Jn; hbase = hnext;
         __syncthreads(); // the LDS staging areas are rewritten by the next item
     }
     if (slv) { // row sl.row of the diagonal tile (D, D), all 128 columns: the update in place, and the row's two sums (no column part)
         v2d hn = h[0]; // (the window holds the row sixteen times)
+        if (PLAIN && two) {
+            const double si = wo_r[0][PLAIN ? tid : 0], ui = wo_r[1][PLAIN ? tid : 0];
+            const v2d sjo = wo_c[0][PLAIN ? tid : 0], ujo = wo_c[1][PLAIN ? tid : 0];
+            if (BFGS || SR1) {
+                hn.x = hn.x + o_su * (si * ujo.x + ui * sjo.x);
+                hn.y = hn.y + o_su * (si * ujo.y + ui * sjo.y);
+            }
+            hn.x = hn.x + o_ss * (si * sjo.x);
+            hn.y = hn.y + o_ss * (si * sjo.y);
+            if (!BFGS || SR1) {
+                hn.x = hn.x + o_uu * (ui * ujo.x);
+                hn.y = hn.y + o_uu * (ui * ujo.y);
+            }
+        }
         const double si = pend ? v0.s_r : 0.0, ui = pend ? v0.u_r : 0.0;
         v2d sj = {0.0, 0.0}, uj = {0.0, 0.0};
         if (pend) { sj = v0.s_c; uj = v0.u_c; }
@@ -1773,7 +1843,7 @@ __global__ __launch_bounds__(QN_S2_TPB, 2) void s2_hpass_kernel(const QnS2Args a
             hn.x = hn.x + c_uu * (ui * uj.x);
             hn.y = hn.y + c_uu * (ui * uj.y);
         }
-        qn_sym_st<NT>(sliver_ptr(), hn);
+        if (!nost) qn_sym_st<NT>(sliver_ptr(), hn);
         double t0 = hn.x * v0.a0.x;
         t0 = __builtin_fma(hn.y, v0.a0.y, t0);
         double t1 = hn.x * v0.a1.x;
@@ -1891,6 +1961,7 @@ __global__ __launch_bounds__(QN_S2_TPB) void s2_hreduce_kernel(const QnS2Args a)
     QnS2Slots S0;
     QN_S2_STAMP(0);
     double gp = 0.0, yv = 0.0, s0e = 0.0, s1e = 0.0;
+    constexpr bool PLAIN = !SHARD && !SR1; // (the instances behind s2_hpass_kernel's read pass: QnCtl.hskip)
     auto entries = [&]() {
         if (half != 1 && tid < QN_TB) {
             gp = a.F.GT[R * QN_TB + tid]; yv = a.F.Y[R * QN_TB + tid];
@@ -1908,6 +1979,14 @@ __global__ __launch_bounds__(QN_S2_TPB) void s2_hreduce_kernel(const QnS2Args a)
     double tot0 = 0.0, tot1 = 0.0;
     if (!SHARD) {
         if (half == 1 && nrhs != 2) return; // (uniform) a direction pass has one right-hand side
+        // The pass did not store (s2_hpass_kernel's read pass): its update stays pending as the OLDER of two, and its vectors move out of the way -- u before
+        // the new u below overwrites it (the same thread), s before the next accept-reduce stages the next step in its half.  One block-row's u by the
+        // workgroup of the first right-hand side, its s by the other's.
+        if (PLAIN && L.c.hskip && L.c.pending == 1 && nrhs == 2 && tid < QN_TB) {
+            const int gi = R * QN_TB + tid; // (requested here, not at entry: held across the prologue the two words went to scratch memory)
+            if (half == 0) a.uo[gi] = a.F.UN[gi];
+            else a.so[gi] = a.F.S0[(size_t)(L.c.sc ? a.np : 0) + gi];
+        }
         const double t = qn_s2_slot_sum(a.part, a.nb, R, half, S0, qbuf);
         if (half == 0) tot0 = t; else tot1 = t;
     } else if (tid < QN_TB) { // xg: [rank][rhs][np]

@@ -65,6 +65,7 @@ OPTIONS = {
     "pnorm_rows_per_wave": 25,
     "lbfgs_unit_scaling": 26,
     "machine_fast_steps": 27,
+    "hpass_store_skip": 28,
 }
 OPT_GENERIC_KERNELS = 1
 OPT_DEFERRED_UPDATE_STEP = 2
@@ -93,6 +94,7 @@ OPT_PNORM_NONTEMPORAL = 24
 OPT_PNORM_ROWS_PER_WAVE = 25
 OPT_LBFGS_UNIT_SCALING = 26
 OPT_MACHINE_FAST_STEPS = 27
+OPT_HPASS_STORE_SKIP = 28
 
 
 class SolverError(Exception):

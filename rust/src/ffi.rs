@@ -68,6 +68,7 @@ pub const QN_OPT_PNORM_NONTEMPORAL: c_int = 24;
 pub const QN_OPT_PNORM_ROWS_PER_WAVE: c_int = 25;
 pub const QN_OPT_LBFGS_UNIT_SCALING: c_int = 26;
 pub const QN_OPT_MACHINE_FAST_STEPS: c_int = 27;
+pub const QN_OPT_HPASS_STORE_SKIP: c_int = 28;
 
 pub const QN_UNIQUE_ID_BYTES: usize = 128;
 pub const QN_TRACE_LS_MODIFIED: i32 = 1 << 30;
@@ -177,6 +178,8 @@ pub struct qn_stats {
     pub n_newton_timed: u64,
     pub newton_lu_sync_timeouts: u64,
     pub fast_machine_steps: u64,
+    pub n_hpass_nostore: u64,
+    pub h_bytes_moved: u64,
 }
 
 extern "C" {
