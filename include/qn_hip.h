@@ -205,6 +205,25 @@ int qn_quadratic_create_synthetic(qn_context* ctx, size_t n, uint64_t seed, cons
 /* f = log sum_i exp(a_i'x + c_i) + mu/2 ||x||^2; A is m x n row-major, rows sharded. */
 int qn_logsumexp_create(qn_context* ctx, size_t m, size_t n, const double* a_rowmajor_host, const double* c_host, double mu,
                         qn_objective** out);
+/* f = 1/2 x'Qx - b'x, g = Qx - b with a SPARSE Q: n x n in CSR, both triangles of a symmetric matrix -- the device objective that exists at the
+ * sizes the O(n) solvers are for.  It runs under QN_SPG, QN_PROJECTED_GRADIENT and QN_LBFGS with every line search those take; every other method:
+ * QN_ERROR_INPUT_PARAMS ("unsupported objective"; the projected Newton pair: "Hessian not available in the oracle").  One rank (a row-sharded
+ * context: QN_ERROR_INPUT_PARAMS).  The two index arrays travel as untyped pointers: `index_bytes` = 4 (int32) or 8 (int64) holds for BOTH, as in
+ * scipy's CSR; on the device they are int32, 12 bytes per nonzero.  Validated on the host in O(nnz), each failure QN_ERROR_INPUT_PARAMS: a null
+ * pointer or n == 0, index_bytes not 4 or 8, n > 2^30, nnz > 2^31 - 1, row_ptr[0] != 0, row_ptr[n] != nnz, a decreasing row_ptr, a column outside
+ * [0, n), columns not STRICTLY increasing inside a row (unsorted or duplicate).  nnz == 0 is legal (g = -b).  A matrix that is not symmetric bit
+ * for bit (pattern and values; qn_objective_sparse_info reports it) is multiplied as given, as qn_quadratic_create's is.  One evaluation is two
+ * launches (csrc/qn_sparse.hip.h): CSR-vector with `lanes_per_row` lanes to a row and whole workgroups for rows of more than 2048 entries, f's
+ * shares added in a fixed order -- no atomics, the same bits for the same x from run to run and from object to object.
+ * qn_objective_get_rows / qn_objective_hessian on it: QN_ERROR_INPUT_PARAMS. */
+int qn_sparse_quadratic_create(qn_context* ctx, size_t n, size_t nnz, const void* row_ptr_host, const void* col_idx_host,
+                               int index_bytes, const double* values_host, const double* b_host, qn_objective** out);
+/* lanes that share one row: 1, 2, 4, 8, 16, 32 or 64; 0: chosen from the mean row length (the default).  Another value may change the bits of f and g
+ * (another summation order), never between two evaluations with the same value. */
+int qn_sparse_quadratic_set_lanes_per_row(qn_objective* obj, int lanes);
+/* a sparse quadratic's shape: its nonzeros, the lanes per row in use, the rows summed by a workgroup of their own, whether Q == Q' bit for bit.
+ * Any pointer may be NULL.  Another objective: QN_ERROR_INPUT_PARAMS. */
+int qn_objective_sparse_info(qn_objective* obj, size_t* nnz, int* lanes_per_row, size_t* n_long_rows, int* symmetric);
 void qn_objective_destroy(qn_objective* obj);
 /* one evaluation at a host point (tests, and `let eval = f_and_g(x)` after minimize as in examples/quadratic.rs:39) */
 int qn_objective_eval(qn_objective* obj, const double* x_host, double* f, double* g_host);

@@ -250,6 +250,41 @@ class LogSumExp {
     }
 };
 
+// a device-resident objective f = 1/2 x'Qx - b'x with a sparse Q in CSR (both triangles of a symmetric matrix): the large objective of the O(n)
+// solvers -- SpectralProjectedGradient, ProjectedGradientDescent, LBFGS / ProjectedLBFGS.  Index: int32_t or int64_t, for both arrays.
+class SparseQuadratic {
+    qn_objective* h_ = nullptr;
+    size_t n_;
+    template <class Index>
+    void create(const std::vector<Index>& indptr, const std::vector<Index>& indices, const DVector& data, const DVector& b, Context& ctx) {
+        static_assert(sizeof(Index) == 4 || sizeof(Index) == 8, "CSR indices are 32 or 64 bits wide");
+        if (indptr.size() != n_ + 1 || indices.size() != data.size()) throw SolverError{SolverError::ErrorInputParams, "CSR arrays do not match n / nnz"};
+        const Index none = 0; // (an empty matrix: data() of an empty vector may be null, which the library takes for a missing argument)
+        const Floating zero = 0;
+        check(qn_sparse_quadratic_create(ctx.handle(), n_, data.size(), indptr.data(), indices.empty() ? &none : indices.data(), (int)sizeof(Index),
+                                         data.empty() ? &zero : data.data(), b.data(), &h_));
+    }
+  public:
+    SparseQuadratic(const std::vector<int32_t>& indptr, const std::vector<int32_t>& indices, const DVector& data, const DVector& b,
+                    Context& ctx = Context::default_context()) : n_(b.size()) { create(indptr, indices, data, b, ctx); }
+    SparseQuadratic(const std::vector<int64_t>& indptr, const std::vector<int64_t>& indices, const DVector& data, const DVector& b,
+                    Context& ctx = Context::default_context()) : n_(b.size()) { create(indptr, indices, data, b, ctx); }
+    SparseQuadratic(const SparseQuadratic&) = delete;
+    ~SparseQuadratic() { qn_objective_destroy(h_); }
+    qn_objective* handle() const { return h_; }
+    FuncEvalMultivariate operator()(const DVector& x) const {
+        DVector g(n_);
+        Floating f = 0;
+        check(qn_objective_eval(h_, x.data(), &f, g.data()));
+        return FuncEvalMultivariate(f, std::move(g));
+    }
+    size_t nnz() const { size_t v = 0; check(qn_objective_sparse_info(h_, &v, nullptr, nullptr, nullptr)); return v; }
+    int lanes_per_row() const { int v = 0; check(qn_objective_sparse_info(h_, nullptr, &v, nullptr, nullptr)); return v; }
+    size_t n_long_rows() const { size_t v = 0; check(qn_objective_sparse_info(h_, nullptr, nullptr, &v, nullptr)); return v; }
+    bool symmetric() const { int v = 0; check(qn_objective_sparse_info(h_, nullptr, nullptr, nullptr, &v)); return v != 0; }
+    void set_lanes_per_row(int lanes) { check(qn_sparse_quadratic_set_lanes_per_row(h_, lanes)); } // 0: chosen from the mean row length
+};
+
 template <int METHOD>
 class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the path
     qn_solver* h_ = nullptr;
@@ -297,7 +332,8 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
 
     // minimize with a host closure: the reference's exact oracle-call sequence (ls_solver.rs:66-111)
     // (a device objective is callable too: without the constraint a non-const Quadratic / LogSumExp lvalue would bind here, as a host closure)
-    template <class LS, class Oracle, class = std::enable_if_t<!std::is_same_v<std::decay_t<Oracle>, Quadratic> && !std::is_same_v<std::decay_t<Oracle>, LogSumExp>>>
+    template <class LS, class Oracle, class = std::enable_if_t<!std::is_same_v<std::decay_t<Oracle>, Quadratic> && !std::is_same_v<std::decay_t<Oracle>, LogSumExp> &&
+                                                               !std::is_same_v<std::decay_t<Oracle>, SparseQuadratic>>>
     Result minimize(LS& line_search, Oracle&& oracle, size_t max_iter_solver, size_t max_iter_line_search,
                     std::optional<std::function<void(const Self&)>> callback = std::nullopt) {
         using OracleT = std::remove_reference_t<Oracle>;
@@ -342,6 +378,14 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
     }
     template <class LS>
     Result minimize(LS& line_search, const LogSumExp& objective, size_t max_iter_solver, size_t max_iter_line_search) {
+        qn_oracle o{};
+        o.kind = QN_ORACLE_OBJECTIVE;
+        o.memoize = 1;
+        o.objective = objective.handle();
+        return make_result(qn_minimize(h_, &line_search.ffi(), &o, max_iter_solver, max_iter_line_search, nullptr, nullptr));
+    }
+    template <class LS>
+    Result minimize(LS& line_search, const SparseQuadratic& objective, size_t max_iter_solver, size_t max_iter_line_search) {
         qn_oracle o{};
         o.kind = QN_ORACLE_OBJECTIVE;
         o.memoize = 1;

@@ -70,3 +70,5 @@ extern "C" const char* qn_status_string(int status) {
 // limited-memory BFGS on the first-order family's machine: the two streaming kernels of its compact form, behind every existing kernel
 #include "qn_lbfgs.hip.h"
 #include "qn_host_lbfgs.hip.h"
+// the sparse quadratic objective (CSR; the O(n) solvers' large device objective): behind every existing kernel
+#include "qn_sparse.hip.h"

@@ -1,9 +1,12 @@
-// qn_host_objective.hip.h -- host side, part 3 of 7: device-resident objectives (the synthetic quadratic, the log-sum-exp) and their evaluation launches.
+// qn_host_objective.hip.h -- host side, part 3 of 7: device-resident objectives (the synthetic quadratic, the log-sum-exp, the sparse quadratic) and their evaluation launches.
 #pragma once
 // ------------------------------------------------------------------------------------------------
 // objectives
 // ------------------------------------------------------------------------------------------------
-enum { OBJ_QUADRATIC = 1, OBJ_LOGSUMEXP = 2 };
+enum { OBJ_QUADRATIC = 1, OBJ_LOGSUMEXP = 2, OBJ_SPARSE_QUADRATIC = 3 };
+// the sparse quadratic's launch shape (qn_sparse.hip.h; the creation below cuts the rows for it)
+#define SPQ_MAXG 2048     // regular workgroups at the most: 8 per CU on 256 CUs
+#define SPQ_LONG_ROW 2048 // rows longer than this get a workgroup of their own
 static std::atomic<uint64_t> g_objective_serial{0}; // objectives are numbered at creation: an address can come back after a destroy, a serial cannot
 struct qn_objective {
     uint64_t serial = ++g_objective_serial;
@@ -26,6 +29,12 @@ struct qn_objective {
     DevBuf<double> lz, lw, lgpart, lgall, lscal;
     DevBuf<double> lwgms, lwgg, lms; // one-pass evaluation: per-workgroup (m, S), G vectors; gathered per-rank (m, S)
     int lse_G = 0, lse_kch = 0;                                 // its grid and column chunks per thread (0: two-pass evaluation)
+    // sparse quadratic (qn_sparse.hip.h): Q in CSR -- int32 row offsets (n + 1), int32 columns and f64 values (nnz) --, b in `b`
+    DevBuf<int> sp_row_ptr, sp_col, sp_wg_row_start, sp_long_rows;
+    DevBuf<double> sp_val, sp_part; // sp_part: f's shares, one per workgroup of the evaluation launch
+    size_t sp_nnz = 0, sp_n_long = 0;
+    int sp_G = 0;                    // regular workgroups; the long rows' run behind them in the same launch
+    int sp_lanes = 1, sp_lanes_auto = 1; // lanes per row in use, and the choice made at creation from the mean row length
 };
 
 static int objective_base(qn_context* ctx, size_t n, const double* b_host, qn_objective** out) {
@@ -115,6 +124,135 @@ extern "C" int qn_logsumexp_create(qn_context* ctx, size_t m, size_t n, const do
         QNCHK(o->lms.alloc_zero(2 * (size_t)ctx->world, st));
     }
     HIPCHK(hipStreamSynchronize(st));
+    return QN_OK;
+}
+
+// ---- the sparse quadratic: f = 1/2 x'Qx - b'x with Q in CSR (kernels and the evaluation's launches: qn_sparse.hip.h) ----
+static int spq_enqueue_eval(qn_objective* o, const double* x_dev, double* f_dev, double* g_dev, int which = 3);
+
+template <class I>
+static int spq_validate(size_t n, size_t nnz, const I* rp, const I* ci) {
+    if (rp[0] != 0) return fail(QN_ERROR_INPUT_PARAMS, "sparse quadratic: row_ptr[0] must be 0");
+    if (rp[n] < 0 || (uint64_t)rp[n] != (uint64_t)nnz) return fail(QN_ERROR_INPUT_PARAMS, "sparse quadratic: row_ptr[n] must be nnz");
+    for (size_t i = 0; i < n; ++i) {
+        if (rp[i + 1] < rp[i]) return fail(QN_ERROR_INPUT_PARAMS, "sparse quadratic: row_ptr decreases at row " + std::to_string(i));
+        if ((uint64_t)rp[i + 1] > (uint64_t)nnz) return fail(QN_ERROR_INPUT_PARAMS, "sparse quadratic: row_ptr exceeds nnz at row " + std::to_string(i));
+        for (size_t j = (size_t)rp[i]; j < (size_t)rp[i + 1]; ++j) {
+            if (ci[j] < 0 || (uint64_t)ci[j] >= (uint64_t)n)
+                return fail(QN_ERROR_INPUT_PARAMS, "sparse quadratic: a column of row " + std::to_string(i) + " is outside [0, n)");
+            if (j > (size_t)rp[i] && ci[j] <= ci[j - 1])
+                return fail(QN_ERROR_INPUT_PARAMS, "sparse quadratic: the columns of row " + std::to_string(i) + " are not strictly increasing (unsorted or duplicate)");
+        }
+    }
+    return QN_OK;
+}
+
+// lanes per row from the mean row length: the largest power of two that is at most half of it (1 .. 64).  Measured (tools/bench_sparse.py):
+// the five-point Laplacian (5 per row) is fastest with 2 lanes, a random pattern of 17 per row with 16 to 32 (8 lanes: 9 % behind)
+static int spq_auto_lanes(size_t n, size_t nnz) {
+    const double mean = (double)nnz / (double)n;
+    int L = 1;
+    while (L < 64 && (double)(2 * L) <= 0.5 * mean) L *= 2;
+    return L;
+}
+
+extern "C" int qn_sparse_quadratic_create(qn_context* ctx, size_t n, size_t nnz, const void* row_ptr_host, const void* col_idx_host,
+                                          int index_bytes, const double* values_host, const double* b_host, qn_objective** out) {
+    if (!ctx || !out || !row_ptr_host || !col_idx_host || !values_host || !b_host || n == 0)
+        return fail(QN_ERROR_INPUT_PARAMS, "null argument or n == 0");
+    if (index_bytes != 4 && index_bytes != 8) return fail(QN_ERROR_INPUT_PARAMS, "sparse quadratic: index_bytes must be 4 or 8");
+    if (n > (size_t)1 << 30) return fail(QN_ERROR_INPUT_PARAMS, "n too large");
+    if (nnz > (size_t)INT32_MAX) return fail(QN_ERROR_INPUT_PARAMS, "sparse quadratic: nnz must not exceed 2^31 - 1");
+    if (ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "a sparse quadratic lives on one rank (no row sharding)");
+    if (index_bytes == 4) QNCHK(spq_validate(n, nnz, (const int32_t*)row_ptr_host, (const int32_t*)col_idx_host));
+    else QNCHK(spq_validate(n, nnz, (const int64_t*)row_ptr_host, (const int64_t*)col_idx_host));
+    // the device's copy: int32 whatever came in
+    std::vector<int> rp(n + 1), ci(std::max<size_t>(nnz, 1), 0);
+    if (index_bytes == 4) {
+        memcpy(rp.data(), row_ptr_host, (n + 1) * sizeof(int));
+        if (nnz) memcpy(ci.data(), col_idx_host, nnz * sizeof(int));
+    } else {
+        const int64_t *r8 = (const int64_t*)row_ptr_host, *c8 = (const int64_t*)col_idx_host;
+        for (size_t i = 0; i <= n; ++i) rp[i] = (int)r8[i];
+        for (size_t j = 0; j < nnz; ++j) ci[j] = (int)c8[j];
+    }
+    // symmetry, bit for bit: the transpose by a counting sort (its rows come out with increasing columns), compared with what was given
+    bool symmetric = true;
+    {
+        std::vector<int> tp(n + 1, 0);
+        for (size_t j = 0; j < nnz; ++j) tp[(size_t)ci[j] + 1]++;
+        for (size_t i = 0; i < n; ++i) tp[i + 1] += tp[i];
+        symmetric = memcmp(tp.data(), rp.data(), (n + 1) * sizeof(int)) == 0;
+        if (symmetric && nnz) {
+            std::vector<int> fill(tp.begin(), tp.end() - 1), tc(nnz);
+            std::vector<double> tv(nnz);
+            for (size_t i = 0; i < n; ++i)
+                for (int j = rp[i]; j < rp[i + 1]; ++j) {
+                    const int k = fill[(size_t)ci[j]]++;
+                    tc[(size_t)k] = (int)i;
+                    tv[(size_t)k] = values_host[j];
+                }
+            symmetric = memcmp(tc.data(), ci.data(), nnz * sizeof(int)) == 0 && memcmp(tv.data(), values_host, nnz * sizeof(double)) == 0;
+        }
+    }
+    // the static cut: workgroup w takes the rows whose prefix weight (nonzeros + rows in front of them) falls into its G-th of the total
+    const size_t total = nnz + n;
+    const int G = (int)std::min<size_t>(SPQ_MAXG, std::max<size_t>(1, (total + 4095) / 4096));
+    std::vector<int> cut((size_t)G + 1), longs;
+    for (int w = 0; w <= G; ++w) {
+        const uint64_t target = (uint64_t)total * (uint64_t)w / (uint64_t)G;
+        size_t lo = 0, hi = n; // the first row i with row_ptr[i] + i >= target
+        while (lo < hi) {
+            const size_t mid = (lo + hi) / 2;
+            if ((uint64_t)rp[mid] + mid >= target) hi = mid; else lo = mid + 1;
+        }
+        cut[(size_t)w] = (int)lo;
+    }
+    cut[0] = 0; cut[(size_t)G] = (int)n;
+    for (size_t i = 0; i < n; ++i)
+        if (rp[i + 1] - rp[i] > SPQ_LONG_ROW) longs.push_back((int)i);
+
+    HIPCHK(hipSetDevice(ctx->device));
+    qn_objective* o = new qn_objective();
+    *out = o;
+    o->ctx = ctx; o->kind = OBJ_SPARSE_QUADRATIC; o->n = n;
+    o->T = make_tile(n, ctx, 1); // (the padding of the solver's vectors)
+    o->q_symmetric = symmetric;
+    o->sp_nnz = nnz; o->sp_n_long = longs.size(); o->sp_G = G;
+    o->sp_lanes = o->sp_lanes_auto = spq_auto_lanes(n, nnz);
+    hipStream_t st = ctx->stream;
+    QNCHK(o->b.alloc_zero(o->T.n_pad, st));
+    QNCHK(o->sp_row_ptr.alloc(n + 1));
+    QNCHK(o->sp_col.alloc(std::max<size_t>(nnz, 1)));
+    QNCHK(o->sp_val.alloc_zero(std::max<size_t>(nnz, 1), st));
+    QNCHK(o->sp_wg_row_start.alloc((size_t)G + 1));
+    QNCHK(o->sp_long_rows.alloc(std::max<size_t>(longs.size(), 1)));
+    QNCHK(o->sp_part.alloc_zero((size_t)G + longs.size(), st));
+    HIPCHK(hipMemcpyAsync(o->b, b_host, n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(o->sp_row_ptr, rp.data(), (n + 1) * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(o->sp_col, ci.data(), ci.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    if (nnz) HIPCHK(hipMemcpyAsync(o->sp_val, values_host, nnz * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(o->sp_wg_row_start, cut.data(), cut.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    if (!longs.empty()) HIPCHK(hipMemcpyAsync(o->sp_long_rows, longs.data(), longs.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st)); // (the staging vectors above go out of scope)
+    return QN_OK;
+}
+
+extern "C" int qn_sparse_quadratic_set_lanes_per_row(qn_objective* o, int lanes) {
+    if (!o || o->kind != OBJ_SPARSE_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "lanes_per_row belongs to a sparse quadratic");
+    if (lanes == 0) { o->sp_lanes = o->sp_lanes_auto; return QN_OK; }
+    if (lanes < 1 || lanes > 64 || (lanes & (lanes - 1)) != 0)
+        return fail(QN_ERROR_INPUT_PARAMS, "sparse quadratic: lanes_per_row must be 0 (automatic), 1, 2, 4, 8, 16, 32 or 64");
+    o->sp_lanes = lanes;
+    return QN_OK;
+}
+
+extern "C" int qn_objective_sparse_info(qn_objective* o, size_t* nnz, int* lanes_per_row, size_t* n_long_rows, int* symmetric) {
+    if (!o || o->kind != OBJ_SPARSE_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "not a sparse quadratic");
+    if (nnz) *nnz = o->sp_nnz;
+    if (lanes_per_row) *lanes_per_row = o->sp_lanes;
+    if (n_long_rows) *n_long_rows = o->sp_n_long;
+    if (symmetric) *symmetric = o->q_symmetric ? 1 : 0;
     return QN_OK;
 }
 
@@ -227,6 +365,7 @@ extern "C" void qn_objective_destroy(qn_objective* o) {
 }
 
 extern "C" int qn_objective_get_rows(qn_objective* o, size_t row0, size_t nrows, double* out_host) {
+    if (o->kind == OBJ_SPARSE_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "a sparse quadratic has no dense rows / Hessian");
     const bool lse = o->kind == OBJ_LOGSUMEXP;
     const size_t lo = lse ? (size_t)o->TA.row_off : (size_t)o->T.row_off;
     const size_t hi = lse ? std::min(o->m, lo + (size_t)o->TA.rpr) : std::min(o->n, lo + (size_t)o->T.rpr);
@@ -280,6 +419,17 @@ extern "C" int qn_objective_eval(qn_objective* o, const double* x_host, double* 
         HIPCHK(hipStreamSynchronize(c->stream));
         return QN_OK;
     }
+    if (o->kind == OBJ_SPARSE_QUADRATIC) {
+        QNCHK(o->ex.ensure(2 * np, c->stream));
+        QNCHK(o->eg.ensure(np, c->stream));
+        QNCHK(o->ef.ensure(2, c->stream));
+        HIPCHK(hipMemcpyAsync(o->ex, x_host, o->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        QNCHK(spq_enqueue_eval(o, o->ex, o->ef, o->eg));
+        HIPCHK(hipMemcpyAsync(f, o->ef, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(g_host, o->eg, o->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        return QN_OK;
+    }
     if (o->kind != OBJ_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
     QNCHK(o->ex.ensure(2 * np, c->stream)); // x and xt
     QNCHK(o->eq.ensure(np, c->stream));
@@ -304,6 +454,7 @@ extern "C" int qn_objective_eval(qn_objective* o, const double* x_host, double* 
 
 extern "C" int qn_objective_hessian(qn_objective* o, const double* x_host, double* h_colmajor_host) {
     if (!o || !x_host) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
+    if (o->kind == OBJ_SPARSE_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "a sparse quadratic has no dense rows / Hessian");
     qn_context* c = o->ctx;
     if (c->world != 1) return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hessian is single-GPU");
     HIPCHK(hipSetDevice(c->device));

@@ -121,6 +121,14 @@ static int vec_enqueue_eval(VecRun& r) {
     qn_solver* s = r.s;
     qn_context* c = s->ctx;
     hipStream_t st = c->stream;
+    if (r.obj && r.obj->kind == OBJ_SPARSE_QUADRATIC) {
+        // the CSR product with g and f's shares out of the same launch, then the shares' sum (qn_sparse.hip.h).  Profiling mode times the two apart:
+        // t_eval_ms is spq_eval_kernel alone (what tools/bench_sparse.py reports), the finish counts under t_ctl_ms
+        { ProfScope ps(s, KC_EVAL); QNCHK(spq_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt, 1)); }
+        { ProfScope ps(s, KC_CTL); QNCHK(spq_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt, 2)); }
+        s->stats.launches += 2;
+        return QN_OK;
+    }
     ProfScope ps(s, KC_EVAL);
     if (r.o->kind == QN_ORACLE_HOST) { // s->hx holds xt (vec_peek)
         double f = NAN;
@@ -215,7 +223,8 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     const bool pn = pn_method(s->method), lbfgs = s->method == QN_LBFGS;
     VecRun r{s, o, nullptr, {}};
     QNCHK(check_oracle(c, s->n, o, &r.obj));
-    if (r.obj && r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_LOGSUMEXP) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
+    if (r.obj && r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_LOGSUMEXP && r.obj->kind != OBJ_SPARSE_QUADRATIC)
+        return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
     if (ls->kind == QN_LS_MORETHUENTE || ls->kind == QN_LS_MORETHUENTE_B)
         return fail(QN_ERROR_INPUT_PARAMS, "More-Thuente with SPG / projected gradient / projected Newton / L-BFGS is out of scope: use GLLQuadratic, BackTracking or BackTrackingB");
     const bool wolfe = ls->kind == QN_LS_STRONG_WOLFE;
@@ -291,6 +300,8 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         s->stats.h_passes = 0; s->stats.h_bytes = 0; s->stats.matrix_bytes_per_pass = 0;
         s->stats.obj_bytes = 0;
         if (r.obj && r.obj->kind == OBJ_QUADRATIC) s->stats.obj_bytes = h->n_evals * (uint64_t)r.obj->T.rpr * (uint64_t)r.obj->T.n_pad * 8ull;
+        if (r.obj && r.obj->kind == OBJ_SPARSE_QUADRATIC) // values + columns, the row offsets, and x, b, g of one evaluation
+            s->stats.obj_bytes = h->n_evals * (12ull * (uint64_t)r.obj->sp_nnz + 4ull * ((uint64_t)s->n + 1) + 24ull * (uint64_t)s->n);
         stats_add_totals(s); // (no update passes, one rank: total_h_* and total_xchg_* stay)
         s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u) | (lbfgs ? QN_PATH_LBFGS : 0u);
         if (s->method == QN_PROJECTED_NEWTON) { // s_norm() / y_norm() (projected_newton.rs:10-11) through the getters every solver answers

@@ -607,6 +607,77 @@ class Quadratic(Objective):
         return self
 
 
+class SparseQuadratic(Objective):
+    """f = 1/2 x'Qx - b'x on the device with a sparse Q in CSR (both triangles of a symmetric matrix; the columns of a row strictly increasing): the
+    objective that exists at the sizes the O(n) solvers are for -- SpectralProjectedGradient, ProjectedGradientDescent, LBFGS / ProjectedLBFGS.
+    int32 or int64 index arrays are passed through as they are (one width for both: a mixed pair goes as int64), other integer types as int64."""
+
+    def __init__(self, indptr, indices, data, b, ctx=None):
+        ctx = ctx or default_context()
+        indptr, indices = np.asarray(indptr), np.asarray(indices)
+        if indptr.dtype.kind not in "iu" or (indices.size and indices.dtype.kind not in "iu"):
+            raise ErrorInputParams("indptr and indices must be integer arrays")
+        it = indptr.dtype if indptr.dtype == indices.dtype and indptr.dtype in (np.dtype(np.int32), np.dtype(np.int64)) else np.dtype(np.int64)
+        indptr, indices = np.ascontiguousarray(indptr, dtype=it), np.ascontiguousarray(indices, dtype=it)
+        data, b = _f64(data), _f64(b)
+        if indptr.ndim != 1 or indices.ndim != 1 or data.ndim != 1 or b.ndim != 1 or indptr.size != b.size + 1 or indices.size != data.size:
+            raise ErrorInputParams("CSR arrays do not match: indptr has n + 1 entries, indices and data nnz each, b has n")
+        # (an empty array's pointer may be null, which the library takes for a missing argument)
+        ci = indices if indices.size else np.zeros(1, dtype=it)
+        va = data if data.size else np.zeros(1)
+        h = C.c_void_p()
+        _check(A.lib().qn_sparse_quadratic_create(ctx.h, b.size, data.size, indptr.ctypes.data_as(C.c_void_p), ci.ctypes.data_as(C.c_void_p),
+                                                  it.itemsize, _dp(va), _dp(b), C.byref(h)))
+        super().__init__(ctx, h, b.size)
+
+    @classmethod
+    def from_scipy(cls, a, b, ctx=None):
+        """Any scipy sparse matrix: through .tocsr() with sorted indices and duplicates summed."""
+        import scipy.sparse  # noqa: F401 -- only this method needs scipy
+        a = a.tocsr().copy()
+        a.sum_duplicates()
+        a.sort_indices()
+        if a.shape[0] != a.shape[1]:
+            raise ErrorInputParams(f"Q must be square, got {a.shape}")
+        return cls(a.indptr, a.indices, a.data, b, ctx=ctx)
+
+    def __call__(self, x):
+        if not self.h:
+            raise ErrorInputParams("the objective is closed")
+        if np.size(x) != self.n:
+            raise ErrorInputParams(f"x has {np.size(x)} entries, the objective has {self.n}")
+        return super().__call__(x)
+
+    def _info(self):
+        if not self.h:
+            raise ErrorInputParams("the objective is closed")
+        nnz, lanes, nlong, sym = C.c_size_t(), C.c_int(), C.c_size_t(), C.c_int()
+        _check(A.lib().qn_objective_sparse_info(self.h, C.byref(nnz), C.byref(lanes), C.byref(nlong), C.byref(sym)))
+        return nnz.value, lanes.value, nlong.value, sym.value
+
+    @property
+    def nnz(self):
+        return self._info()[0]
+
+    @property
+    def lanes_per_row(self):
+        return self._info()[1]
+
+    @property
+    def n_long_rows(self):
+        return self._info()[2]
+
+    @property
+    def symmetric(self):
+        return self._info()[3]
+
+    def set_lanes_per_row(self, lanes):
+        """Lanes that share one row: 1, 2, 4, 8, 16, 32 or 64; 0: chosen from the mean row length.  Another value may change the bits of f and g."""
+        if not self.h:
+            raise ErrorInputParams("the objective is closed")
+        _check(A.lib().qn_sparse_quadratic_set_lanes_per_row(self.h, int(lanes)))
+
+
 class LogSumExp(Objective):
     """f = log sum_i exp(a_i'x + c_i) + mu/2 ||x||^2 on the device (A is m x n row-major, rows sharded over ranks)."""
 

@@ -428,6 +428,32 @@ impl DeviceObjective {
         status_to_result(unsafe { qn_logsumexp_create(default_context(), m, n, a_rowmajor.as_ptr(), c.as_ptr(), mu, &mut h) })?;
         Ok(DeviceObjective { h, n })
     }
+    /// f = 1/2 x'Qx - b'x with a sparse Q in CSR (both triangles of a symmetric matrix; `indptr` has n + 1 entries, the columns of a row
+    /// increase strictly): the large objective of the O(n) solvers (GpuSpectralProjectedGradient, GpuProjectedGradientDescent, GpuLBFGS).
+    pub fn sparse_quadratic(indptr: &[i64], indices: &[i64], data: &[Floating], b: &DVector<Floating>) -> Result<Self, SolverError> {
+        let n = b.len();
+        if indptr.len() != n + 1 || indices.len() != data.len() {
+            return Err(SolverError::ErrorInputParams);
+        }
+        let (no_index, no_value) = ([0i64; 1], [0.0; 1]); // an empty matrix: the library takes a dangling pointer for what it is
+        let ci = if indices.is_empty() { no_index.as_ptr() } else { indices.as_ptr() };
+        let va = if data.is_empty() { no_value.as_ptr() } else { data.as_ptr() };
+        let mut h = std::ptr::null_mut();
+        status_to_result(unsafe {
+            qn_sparse_quadratic_create(default_context(), n, data.len(), indptr.as_ptr() as *const c_void, ci as *const c_void, 8, va, b.as_ptr(), &mut h)
+        })?;
+        Ok(DeviceObjective { h, n })
+    }
+    /// A sparse quadratic's shape: (nnz, lanes per row in use, rows summed by a workgroup of their own, Q == Q' bit for bit).
+    pub fn sparse_info(&self) -> Result<(usize, i32, usize, bool), SolverError> {
+        let (mut nnz, mut lanes, mut long_rows, mut sym) = (0usize, 0 as c_int, 0usize, 0 as c_int);
+        status_to_result(unsafe { qn_objective_sparse_info(self.h, &mut nnz, &mut lanes, &mut long_rows, &mut sym) })?;
+        Ok((nnz, lanes as i32, long_rows, sym != 0))
+    }
+    /// Lanes that share one row of a sparse quadratic: 1, 2, 4, .. 64; 0: chosen from the mean row length.
+    pub fn set_lanes_per_row(&mut self, lanes: i32) -> Result<(), SolverError> {
+        status_to_result(unsafe { qn_sparse_quadratic_set_lanes_per_row(self.h, lanes as c_int) })
+    }
     /// One evaluation at a host point (`let eval = f_and_g(&x)` after `minimize`).
     pub fn eval(&self, x: &DVector<Floating>) -> Result<FuncEvalMultivariate, SolverError> {
         if x.len() != self.n {
