@@ -111,7 +111,7 @@ enum { QN_LS_MORETHUENTE = 0, QN_LS_BACKTRACKING = 1,
        QN_LS_MORETHUENTE_B = 2 /* MoreThuenteB, morethuente_b.rs */, QN_LS_BACKTRACKING_B = 3 /* BackTrackingB, backtracking_b.rs */,
        QN_LS_GLL_QUADRATIC = 4 /* GLLQuadratic, gll_quadratic.rs: the non-monotone search of Grippo, Lampariello, Lucidi; QN_SPG / QN_PROJECTED_GRADIENT only */,
        QN_LS_NO_SEARCH = 5 /* NoSearch, nosearch.rs: constant step 1.0 */,
-       QN_LS_STRONG_WOLFE = 6 /* StrongWolfe: MINPACK-2 dcsrch; the first-order family, the projected Newton pair and QN_LBFGS only */ };
+       QN_LS_STRONG_WOLFE = 6 /* StrongWolfe: MINPACK-2 dcsrch; the first-order family, the projected Newton pair, QN_LBFGS and QN_NONLINEAR_CG only */ };
 typedef struct {
     int32_t kind;
     int32_t _pad;
@@ -144,7 +144,7 @@ void qn_gll_quadratic_new(qn_linesearch* ls, double c1, size_t m);              
 void qn_gll_quadratic_with_sigmas(qn_linesearch* ls, double sigma1, double sigma2);     /* :24-28 */
 /* StrongWolfe (QN_LS_STRONG_WOLFE; no counterpart among the reference's line searches): the strong-Wolfe search as published -- MINPACK-2 `dcsrch` / `dcstep`
  * (More' and Thuente, ACM TOMS 20, 1994; the search the Fortran L-BFGS-B runs) -- for QN_SPG, QN_PROJECTED_GRADIENT, QN_PROJECTED_NEWTON,
- * QN_SPECTRAL_PROJECTED_NEWTON and QN_LBFGS; every other method: QN_ERROR_INPUT_PARAMS.  ONE oracle call per trial: the bracket keeps (f, f') of its
+ * QN_SPECTRAL_PROJECTED_NEWTON, QN_LBFGS and QN_NONLINEAR_CG; every other method: QN_ERROR_INPUT_PARAMS.  ONE oracle call per trial: the bracket keeps (f, f') of its
  * end points (the reference's More-Thuente transcription evaluates two or three points per inner iteration, morethuente.rs:181-294).  It travels in
  * the fields above: kind = QN_LS_STRONG_WOLFE, c1 = ftol (1e-4), c2 = gtol (0.9), delta = xtol (0.1), t_min = stpmin (0), t_max = stpmax (1e10);
  * qn_morethuente_with_t_min / _with_t_max set the last two.  qn_minimize checks 0 < c1 < c2 < 1, xtol >= 0 and 0 <= t_min <= t_max
@@ -298,8 +298,27 @@ enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton
         * THIS IS NOT THE REFERENCE'S `Lbfgsb` (an optional binding to the Fortran L-BFGS-B library): there is no generalised Cauchy point and no
         * subspace minimisation.  The bounded variant follows this library's own BFGSB convention, d = P(x - H g) - x (bfgs_b.rs:72-75); with an active
         * box that direction is no more guaranteed to descend than BFGSB's is.  qn_solver_compute_direction: QN_ERROR_INPUT_PARAMS (use qn_minimize). */
-       QN_LBFGS = 12 /* limited-memory BFGS; no counterpart in the reference's default feature set */ };
+       QN_LBFGS = 12 /* limited-memory BFGS; no counterpart in the reference's default feature set */,
+       /* Nonlinear conjugate gradient: the O(n) method whose state is ONE extra vector -- the direction last searched -- where L-BFGS(m) keeps 2 (m + 1).
+        * d+ = beta d - g+ (beta d rounds first, then the difference); beta by the variant of qn_solver_set_cg (QN_CG_PR_PLUS after qn_solver_create),
+        * with y = g+ - g: FR g+.g+ / g.g; PR+ max(0, g+.y / g.g); HS+ max(0, g+.y / d.y); DY g+.g+ / d.y; HZ (Hager and Zhang 2005) max(betaN, eta_k),
+        * betaN = (g+.y - 2 (y.y)(g+.d) / d.y) / d.y, eta_k = -1 / (||d|| min(0.01, ||g||)).  The rules, in this order: (1) the first direction after
+        * qn_solver_create / qn_solver_reset / qn_solver_set_cg is -g (not a restart); (2) restart_every > 0 and that many iterations since the last -g
+        * direction: beta = 0; (3) the formula, plain IEEE divisions; (4) beta not finite: 0; (5) Powell's test, |g+.g| >= powell_nu g+.g+ : 0 (0.2 by
+        * default, +inf: off); (6) unless -g+.g+ + beta (g+.d) < 0 -- descent, from the sums alone -- 0.  Every beta that ends as exactly 0 counts as a
+        * restart (qn_solver_cg_state); the trace's `updated` is beta != 0, s_norm = ||s||, gnorm = ||g||_inf.  It runs on the first-order family's
+        * machine (QN_PATH_VECTOR | QN_PATH_CG, csrc/qn_cg.hip.h): the accept pass leaves every inner product beta needs, so the direction costs one
+        * stream (16 n bytes read, 16 n written) and no reduction launch of its own.  UNBOUNDED ONLY: qn_solver_set_bounds gives QN_ERROR_INPUT_PARAMS,
+        * as does qn_solver_compute_direction (use qn_minimize).  Line searches: QN_LS_STRONG_WOLFE (what FR, DY and HS+ assume) and QN_LS_BACKTRACKING;
+        * QN_LS_GLL_QUADRATIC, QN_LS_BACKTRACKING_B and both More-Thuente kinds: QN_ERROR_INPUT_PARAMS.  Every oracle kind of the family, memoize 0 / 1,
+        * trace, callbacks, warm restarts (the direction and beta survive calls: two calls of k iterations give the bits of one call of 2 k), one rank.
+        * The first trial step of every search is 1, as everywhere in this family.  Profiling mode: t_hpass_ms = cg_dir_kernel, t_hreduce_ms =
+        * cg_accept_kernel.  Not built: a box, preconditioning, an initial-step rule, the exact step on quadratics, qn_compute_step_len. */
+       QN_NONLINEAR_CG = 13 /* nonlinear conjugate gradient; no counterpart in the reference */ };
 #define QN_LBFGS_MAX_M 32
+/* QN_NONLINEAR_CG's variants (qn_solver_set_cg) */
+enum { QN_CG_FR = 0 /* Fletcher-Reeves */, QN_CG_PR_PLUS = 1 /* Polak-Ribiere+ */, QN_CG_HS_PLUS = 2 /* Hestenes-Stiefel+ */, QN_CG_DY = 3 /* Dai-Yuan */,
+       QN_CG_HZ = 4 /* Hager-Zhang */ };
 typedef struct qn_solver qn_solver;
 
 /* BFGS::new(tol, x0) / DFP::new / GradientDescent::new(grad_tol, x0): H = I (no identity copy is kept) */
@@ -326,6 +345,13 @@ int qn_solver_set_lbfgs_memory(qn_solver* s, size_t m);
 /* QN_LBFGS: m, the pairs stored now, the scaling gamma of the last direction (1 before the first pair), and how often the safeguard g.z > 0 has
  * cleared the memory since qn_solver_create / qn_solver_reset.  Any pointer may be NULL.  Other methods: QN_ERROR_INPUT_PARAMS. */
 int qn_solver_lbfgs_state(qn_solver* s, size_t* m, size_t* stored, double* gamma, size_t* resets);
+/* QN_NONLINEAR_CG: the variant (QN_CG_*; QN_CG_PR_PLUS after qn_solver_create), Powell's nu (0.2; +inf disables the test; NaN or <= 0:
+ * QN_ERROR_INPUT_PARAMS) and restart_every (0: never).  An unknown variant, or another method: QN_ERROR_INPUT_PARAMS.  The stored direction is
+ * dropped: the next direction is -g. */
+int qn_solver_set_cg(qn_solver* s, int variant, double powell_nu, size_t restart_every);
+/* QN_NONLINEAR_CG: the variant, the beta of the last accepted iteration (0 before the first), the betas that ended as exactly 0 and the iterations
+ * since the last -g direction, since qn_solver_create / qn_solver_reset.  Any pointer may be NULL.  Other methods: QN_ERROR_INPUT_PARAMS. */
+int qn_solver_cg_state(qn_solver* s, int* variant, double* beta, size_t* restarts, size_t* since_restart);
 /* QN_PNORM_DESCENT: inverse_p of PnormDescent::new(grad_tol, x0, inverse_p) (pnorm_descent.rs:20-27) and its getter; column-major n x n, like DMatrix
  * and like qn_solver_set_inv_hessian.  ANY matrix is accepted: the reference tests neither symmetry nor definiteness.  It is a constructor argument,
  * not state: qn_solver_reset keeps it.  Other methods: QN_ERROR_INPUT_PARAMS. */
@@ -443,6 +469,7 @@ typedef struct {
 #define QN_PATH_RANK1 256u     /* QN_BROYDEN's H passes: the square-tile kernel of csrc/qn_rank1.hip.h (non-symmetric rank-1 update, row AND column sums in one stream of H) */
 #define QN_PATH_PNORM 512u     /* QN_PNORM_DESCENT's directions: pnorm_dir_kernel of csrc/qn_pnorm.hip.h (one read-only stream of inverse_p, with g.d and ||g||_inf in the same launch) */
 #define QN_PATH_LBFGS 1024u    /* QN_LBFGS: the direction from the compact form of L-BFGS, two streams of the memory per iteration (csrc/qn_lbfgs.hip.h); set beside QN_PATH_VECTOR */
+#define QN_PATH_CG 2048u       /* QN_NONLINEAR_CG: the direction d = beta p - g written by cg_dir_kernel, beta from the accept pass's sums (csrc/qn_cg.hip.h); set beside QN_PATH_VECTOR */
 int qn_solver_get_stats(qn_solver* s, qn_stats* out);
 /* profiling != 0: bracket every launch with HIP events on the solver's stream (slower; for roofline reports) */
 int qn_solver_set_profiling(qn_solver* s, int on);

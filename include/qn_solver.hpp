@@ -163,7 +163,7 @@ class GLLQuadratic {
     qn_linesearch& ffi() { return s_; }
 };
 
-// StrongWolfe (QN_LS_STRONG_WOLFE): MINPACK-2 dcsrch for the O(n) solvers (SPG, projected gradient, the projected Newton pair, LBFGS / ProjectedLBFGS),
+// StrongWolfe (QN_LS_STRONG_WOLFE): MINPACK-2 dcsrch for the O(n) solvers (SPG, projected gradient, the projected Newton pair, LBFGS / ProjectedLBFGS, NonlinearCG),
 // one oracle call per trial; with a box of its own every search's stpmax is clipped to it (t_max itself is never modified).  0 < c1 < c2 < 1 is
 // checked by minimize.  Keeps its own copies of the bounds.
 class StrongWolfe {
@@ -319,7 +319,7 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
             const std::optional<Floating> d = decrement_squared();
             return d ? *d * 0.5 < tol() : false;
         }
-        if (METHOD == QN_GRADIENT_DESCENT || METHOD == QN_COORDINATE_DESCENT || METHOD == QN_PNORM_DESCENT) { // (pnorm_descent.rs:52-59, coordinate_descent.rs:61-68)
+        if (METHOD == QN_GRADIENT_DESCENT || METHOD == QN_COORDINATE_DESCENT || METHOD == QN_PNORM_DESCENT || METHOD == QN_NONLINEAR_CG) { // (pnorm_descent.rs:52-59, coordinate_descent.rs:61-68)
             Floating acc = -INFINITY;
             for (Floating v : eval.g()) acc = std::fmax(std::fabs(v), acc);
             return acc < tol();
@@ -552,6 +552,24 @@ class LBFGS : public ProjectedLBFGS {
         : ProjectedLBFGS(tol, x0, DVector(x0.size(), -INFINITY), DVector(x0.size(), INFINITY), ctx) {}
     static LBFGS new_(Floating tol, const DVector& x0) { return LBFGS(tol, x0); }
     LBFGS with_memory(size_t m) && { check(qn_solver_set_lbfgs_memory(this->handle(), m)); return std::move(*this); }
+};
+
+// Nonlinear conjugate gradient: new(tol, x0).with_variant(NonlinearCG::Variant::HZ, powell_nu, restart_every); d+ = beta d - g+, one extra vector of
+// state on the GPU.  Restarts d = -g by Powell's test |g+.g| >= powell_nu g+.g+ (INFINITY: off), every restart_every iterations (0: never) and whenever
+// beta d - g+ would not descend.  UNBOUNDED ONLY; StrongWolfe (what FR, DY and HS+ assume) or BackTracking.  has_converged: ||g||_inf < tol.
+class NonlinearCG : public LineSearchSolver<QN_NONLINEAR_CG> {
+  public:
+    enum class Variant : int { FR = QN_CG_FR, PR_PLUS = QN_CG_PR_PLUS, HS_PLUS = QN_CG_HS_PLUS, DY = QN_CG_DY, HZ = QN_CG_HZ };
+    using LineSearchSolver<QN_NONLINEAR_CG>::LineSearchSolver;
+    static NonlinearCG new_(Floating tol, const DVector& x0) { return NonlinearCG(tol, x0); }
+    NonlinearCG with_variant(Variant v, Floating powell_nu = 0.2, size_t restart_every = 0) && {
+        check(qn_solver_set_cg(this->handle(), static_cast<int>(v), powell_nu, restart_every)); // (the stored direction is dropped)
+        return std::move(*this);
+    }
+    Variant variant() const { int v = 0; check(qn_solver_cg_state(this->handle(), &v, nullptr, nullptr, nullptr)); return static_cast<Variant>(v); }
+    Floating beta() const { Floating v = 0; check(qn_solver_cg_state(this->handle(), nullptr, &v, nullptr, nullptr)); return v; }
+    size_t restarts() const { size_t v = 0; check(qn_solver_cg_state(this->handle(), nullptr, nullptr, &v, nullptr)); return v; }
+    size_t since_restart() const { size_t v = 0; check(qn_solver_cg_state(this->handle(), nullptr, nullptr, nullptr, &v)); return v; }
 };
 
 } // namespace optimization_solvers

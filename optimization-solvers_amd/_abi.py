@@ -16,6 +16,8 @@ BROYDEN = 9  # quasi_newton/broyden.rs (BroydenB once bounds are set)
 COORDINATE_DESCENT, PNORM_DESCENT = 10, 11  # steepest_descent/coordinate_descent.rs, pnorm_descent.rs
 LBFGS = 12  # limited-memory BFGS (ProjectedLBFGS once bounds are set); not the reference's Fortran-backed Lbfgsb
 LBFGS_MAX_M = 32
+NONLINEAR_CG = 13  # nonlinear conjugate gradient (unbounded only); no counterpart in the reference
+CG_FR, CG_PR_PLUS, CG_HS_PLUS, CG_DY, CG_HZ = 0, 1, 2, 3, 4  # qn_solver_set_cg's variants
 UNIQUE_ID_BYTES = 128
 
 dp = C.POINTER(C.c_double)
@@ -68,6 +70,7 @@ PATH_FUSED, PATH_SYM, PATH_SYM_GENERIC, PATH_PIPELINED, PATH_SYM2, PATH_TILES1, 
 PATH_RANK1 = 256
 PATH_PNORM = 512
 PATH_LBFGS = 1024
+PATH_CG = 2048
 
 
 # every symbol include/qn_hip.h declares: (name, restype, argtypes)
@@ -130,6 +133,8 @@ SYMBOLS = [
     ("qn_solver_newton_factorisations", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
     ("qn_solver_set_lbfgs_memory", C.c_int, [C.c_void_p, C.c_size_t]),
     ("qn_solver_lbfgs_state", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), dp, C.POINTER(C.c_size_t)]),
+    ("qn_solver_set_cg", C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_size_t]),
+    ("qn_solver_cg_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int), dp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     ("qn_minimize", C.c_int, [C.c_void_p, C.POINTER(LineSearchStruct), C.POINTER(OracleStruct), C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("qn_compute_step_len", C.c_int, [C.c_void_p, C.POINTER(LineSearchStruct), dp, C.c_double, dp, dp, C.c_size_t, C.POINTER(OracleStruct), C.c_size_t,
                              C.POINTER(C.c_double)]),

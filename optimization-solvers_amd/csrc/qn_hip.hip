@@ -72,3 +72,6 @@ extern "C" const char* qn_status_string(int status) {
 #include "qn_host_lbfgs.hip.h"
 // the sparse quadratic objective (CSR; the O(n) solvers' large device objective): behind every existing kernel
 #include "qn_sparse.hip.h"
+// nonlinear conjugate gradient on the first-order family's machine: its direction and accept kernels, behind every existing kernel
+#include "qn_cg.hip.h"
+#include "qn_host_cg.hip.h"

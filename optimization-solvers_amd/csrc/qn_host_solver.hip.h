@@ -112,6 +112,7 @@ struct qn_solver {
     int pn_reuse = 1;
     uint64_t pn_factorisations = 0;
     DevBuf<double> lb_ring, lb_part, lb_small; // QN_LBFGS (qn_lbfgs.hip.h): S and Y, [2][lb_m + 1][n_pad]; the Gram kernel's shares; Gram matrices and coefficients
+    DevBuf<double> cg_p, cg_part; // QN_NONLINEAR_CG (qn_cg.hip.h): the direction last searched, [n_pad]; the accept kernel's shares, [QN_CG_NQ][QN_VEC_MAXG]
     DevBuf<double> bounds_block; // lb, ub (solver), llb, lub (bounded line search): 4 n_pad vectors
     int bounded = 0;
     DevBuf<double> fused_block; // X0[2], S0[2], G, GT, Y, UN, UP, VV (10 n_pad vectors), then the older of two pending updates' s and u (fused_so, fused_uo)
@@ -390,7 +391,7 @@ extern "C" int qn_solver_create(qn_context* ctx, int method, double tol, const d
         return fail(QN_ERROR_INPUT_PARAMS, "unknown method");
     if (steep_method(method) && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "CoordinateDescent / PnormDescent run on one rank");
     if (method == QN_BROYDEN && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "Broyden runs on one rank: its non-symmetric H needs column sums, which a row-sharded context (world > 1) does not have");
-    if (vec_method(method) && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient / projected Newton / L-BFGS run on one rank");
+    if (vec_method(method) && ctx->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient / projected Newton / L-BFGS / nonlinear CG run on one rank");
     if (n > (size_t)1 << 30) return fail(QN_ERROR_INPUT_PARAMS, "n too large");
     HIPCHK(hipSetDevice(ctx->device));
     qn_solver* s = new qn_solver();
@@ -648,6 +649,7 @@ extern "C" int qn_solver_set_bounds(qn_solver* s, const double* lb_host, const d
     if (!s || !lb_host || !ub_host) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
     if (s->method != QN_BFGS && s->method != QN_DFP && s->method != QN_SR1 && s->method != QN_BROYDEN && !vec_method(s->method))
         return fail(QN_ERROR_INPUT_PARAMS, "bounds need a BFGS / DFP / SR1 / Broyden / SPG / projected-gradient / L-BFGS solver");
+    if (s->method == QN_NONLINEAR_CG) return fail(QN_ERROR_INPUT_PARAMS, "NonlinearCG is unbounded only: its direction beta d - g is not projected (a box is out of scope)");
     HIPCHK(hipSetDevice(s->ctx->device));
     QNCHK(bounds_alloc(s));
     QNCHK(bounds_upload(s, s->bounds_block, lb_host, -INFINITY));

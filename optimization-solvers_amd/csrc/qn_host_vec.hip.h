@@ -31,11 +31,14 @@ extern "C" int qn_strong_wolfe_with_xtol(qn_linesearch* ls, double xtol) {
 
 static bool pn_method(int method) { return method == QN_PROJECTED_NEWTON || method == QN_SPECTRAL_PROJECTED_NEWTON; }
 static bool spectral_method(int method) { return method == QN_SPG || method == QN_SPECTRAL_PROJECTED_NEWTON; }
-static bool vec_method(int method) { return method == QN_SPG || method == QN_PROJECTED_GRADIENT || pn_method(method) || method == QN_LBFGS; }
+static bool vec_method(int method) { return method == QN_SPG || method == QN_PROJECTED_GRADIENT || pn_method(method) || method == QN_LBFGS || method == QN_NONLINEAR_CG; }
 struct VecRun;
 static int lbfgs_state_alloc(qn_solver* s); // QN_LBFGS: qn_host_lbfgs.hip.h
 static int lbfgs_enqueue_direction(VecRun& r, bool wolfe_clip);
 static int lbfgs_enqueue_accept(VecRun& r);
+static int cg_state_alloc(qn_solver* s); // QN_NONLINEAR_CG: qn_host_cg.hip.h
+static int cg_enqueue_direction(VecRun& r);
+static int cg_enqueue_accept(VecRun& r);
 static int vec_grid(size_t np) { // a function of n alone: four 16-byte accesses per thread until 4 workgroups per CU are out
     const size_t per = (size_t)QN_VEC_TPB * 2 * 4;
     return (int)std::min<size_t>(QN_VEC_MAXG, std::max<size_t>(1, (np + per - 1) / per));
@@ -51,6 +54,7 @@ static int vec_state_alloc(qn_solver* s) {
     QNCHK(s->vpart.alloc_zero((size_t)QN_VEC_NPART * QN_VEC_MAXG, st));
     QNCHK(bounds_alloc(s)); // the box is (-inf, +inf) until qn_solver_set_bounds
     if (s->method == QN_LBFGS) QNCHK(lbfgs_state_alloc(s));
+    if (s->method == QN_NONLINEAR_CG) QNCHK(cg_state_alloc(s));
     return QN_OK;
 }
 static void vec_state_reset(qn_solver* s) { // back to the state right after ::new: no lambda, an empty f_previous, no memo
@@ -58,6 +62,7 @@ static void vec_state_reset(qn_solver* s) { // back to the state right after ::n
     QnVecCtl* h = s->hvctl;
     h->has_lambda = 0; h->lambda = 0.0; h->have_eval = 0; h->ring_len = 0; h->k = 0; h->n_iter = 0;
     h->lb_kmem = 0; h->lb_head = 0; h->lb_gamma = 1.0; h->lb_resets = 0; // QN_LBFGS: an empty memory (lb_m and the scaling switch are settings: kept)
+    h->cg_has_p = 0; h->cg_beta = 0.0; h->cg_since = 0; h->cg_restarts = 0; // QN_NONLINEAR_CG: no direction yet (the variant, nu and restart_every are settings: kept)
     h->has_sy = 0; h->s_norm = 0.0; h->y_norm = 0.0; // (the Cholesky factor of a device quadratic's Hessian is kept: it is keyed on the objective)
 }
 
@@ -85,6 +90,7 @@ static int vec_compute_direction(qn_solver* s, const double* g_host, double* d_h
     const size_t n = s->n, np = s->T.n_pad;
     if (pn_method(s->method)) return fail(QN_ERROR_INPUT_PARAMS, "the projected Newton direction needs the oracle's Hessian: use qn_minimize");
     if (s->method == QN_LBFGS) return fail(QN_ERROR_INPUT_PARAMS, "the L-BFGS direction is formed from the device-resident memory: use qn_minimize");
+    if (s->method == QN_NONLINEAR_CG) return fail(QN_ERROR_INPUT_PARAMS, "the NonlinearCG direction is formed from the device-resident previous direction: use qn_minimize");
     if (s->method == QN_SPG && !s->hvctl->has_lambda) return fail(QN_ERROR_INPUT_PARAMS, "lambda0 needs the oracle: the first qn_minimize evaluates it");
     std::vector<double> x(n), lb(n), ub(n);
     QNCHK(qn_solver_get_x(s, x.data()));
@@ -219,12 +225,19 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
                         qn_callback_fn callback, void* callback_user, int ls_only, double ls_f0) {
     qn_context* c = s->ctx;
     HIPCHK(hipSetDevice(c->device));
-    if (c->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient / projected Newton / L-BFGS run on one rank");
-    const bool pn = pn_method(s->method), lbfgs = s->method == QN_LBFGS;
+    if (c->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient / projected Newton / L-BFGS / nonlinear CG run on one rank");
+    const bool pn = pn_method(s->method), lbfgs = s->method == QN_LBFGS, cg = s->method == QN_NONLINEAR_CG;
     VecRun r{s, o, nullptr, {}};
     QNCHK(check_oracle(c, s->n, o, &r.obj));
     if (r.obj && r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_LOGSUMEXP && r.obj->kind != OBJ_SPARSE_QUADRATIC)
         return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
+    if (cg) { // unbounded only: the searches that hold or imply a box, and the non-monotone one, are not this method's
+        if (ls_only) return fail(QN_ERROR_INPUT_PARAMS, "compute_step_len runs on a first-order solver");
+        if (ls->kind != QN_LS_STRONG_WOLFE && ls->kind != QN_LS_BACKTRACKING)
+            return fail(QN_ERROR_INPUT_PARAMS, "NonlinearCG takes StrongWolfe or BackTracking (GLLQuadratic, BackTrackingB and More-Thuente: out of scope)");
+        if (ls->lower_bound_host || ls->upper_bound_host) return fail(QN_ERROR_INPUT_PARAMS, "NonlinearCG is unbounded only: StrongWolfe's box is out of scope");
+        if (s->bounded) return fail(QN_ERROR_INPUT_PARAMS, "NonlinearCG is unbounded only");
+    }
     if (ls->kind == QN_LS_MORETHUENTE || ls->kind == QN_LS_MORETHUENTE_B)
         return fail(QN_ERROR_INPUT_PARAMS, "More-Thuente with SPG / projected gradient / projected Newton / L-BFGS is out of scope: use GLLQuadratic, BackTracking or BackTrackingB");
     const bool wolfe = ls->kind == QN_LS_STRONG_WOLFE;
@@ -282,6 +295,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     a.lb = s->V.lb; a.ub = s->V.ub; a.llb = s->V.llb; a.lub = s->V.lub;
     a.z = s->V.y; a.part = s->vpart; a.ctl = s->vctl; a.f_dev = s->f_dev; a.trace = s->V.trace; a.xtrace = s->V.xtrace;
     a.n = (int)s->n; a.np = (int)np; a.G = vec_grid(np);
+    a.cp = s->cg_p; a.cpart = s->cg_part;
     a.zw = s->V.y; a.lsmall = s->lb_small; // (the ring and the share buffer: lbfgs_enqueue_direction, on first use)
     const int G = a.G;
     const bool host_oracle = o->kind == QN_ORACLE_HOST;
@@ -303,7 +317,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         if (r.obj && r.obj->kind == OBJ_SPARSE_QUADRATIC) // values + columns, the row offsets, and x, b, g of one evaluation
             s->stats.obj_bytes = h->n_evals * (12ull * (uint64_t)r.obj->sp_nnz + 4ull * ((uint64_t)s->n + 1) + 24ull * (uint64_t)s->n);
         stats_add_totals(s); // (no update passes, one rank: total_h_* and total_xchg_* stay)
-        s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u) | (lbfgs ? QN_PATH_LBFGS : 0u);
+        s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u) | (lbfgs ? QN_PATH_LBFGS : 0u) | (cg ? QN_PATH_CG : 0u);
         if (s->method == QN_PROJECTED_NEWTON) { // s_norm() / y_norm() (projected_newton.rs:10-11) through the getters every solver answers
             s->hctl->has_s_norm = h->has_sy; s->hctl->has_y_norm = h->has_sy; s->hctl->s_norm = h->s_norm; s->hctl->y_norm = h->y_norm;
         }
@@ -335,6 +349,8 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
             }
             // QN_LBFGS: gram, mid, apply, then the direction and the loop top's second half -- all predicated on QN_VP_NSOLVE, no peek in between
             if (lbfgs) QNCHK(lbfgs_enqueue_direction(r, wolfe_boxed));
+            // QN_NONLINEAR_CG: the direction written directly, then the loop top's second half -- the same: one peek per batch
+            if (cg) QNCHK(cg_enqueue_direction(r));
         } else if (ph == QN_VP_NSOLVE && pn) { // (QN_LBFGS never starts a batch here: no peek falls between its loop top and its direction)
             // the one n x n work matrix (Newton's), for the first iteration that wants a direction: a converged start, a cap of 0 and the
             // constructor's lambda0 batch never come here
@@ -366,6 +382,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
             VEC_LAUNCH(vec_decide_kernel, 1);
         }
         if (lbfgs) QNCHK(lbfgs_enqueue_accept(r));
+        else if (cg) QNCHK(cg_enqueue_accept(r));
         else VEC_LAUNCH(vec_accept_kernel, G);
         VEC_LAUNCH(vec_post_kernel, 1);
         QNCHK(vec_peek(r, false));

@@ -11,7 +11,7 @@
 //   vec_accept_kernel  predicated on the accept: x_next = x + t d, s, y, partials s.y, s.s; x <- x_next, g <- gt
 //   vec_post_kernel    (1 workgroup) the Barzilai-Borwein scalar, the trace record, k += 1, the iteration cap
 // (QN_LS_STRONG_WOLFE: wolfe_clip_kernel behind vec_dir_kernel, wolfe_phi_kernel behind the oracle, wolfe_decide_kernel in vec_decide_kernel's place:
-// qn_vec_wolfe.hip.h)
+// qn_vec_wolfe.hip.h.  QN_NONLINEAR_CG: cg_dir_kernel in phase QN_VP_NSOLVE, cg_accept_kernel in vec_accept_kernel's place: qn_cg.hip.h)
 //
 // REDUCTIONS are two-stage and fixed: workgroup b leaves its share in part[q * QN_VEC_MAXG + b]; the one-workgroup kernels add the G
 // shares in index order (thread j takes b = j, j + 256, ..., then the block sum in wave order).  The grid is a function of n alone, no
@@ -37,16 +37,16 @@ enum QnVecPhase : int32_t {
     QN_VP_LS_ONLY = 6, // qn_compute_step_len: g.d for the caller's direction, then the line search alone
     QN_VP_DONE = 7,
     QN_VP_NSOLVE = 8 // ProjectedNewton / SpectralProjectedNewton: the loop top let the iteration through; the host enqueues z = H^-1 g, then the direction
-                     // (QN_LBFGS: z = H_k g from the last pairs (s, y), qn_lbfgs.hip.h)
+                     // (QN_LBFGS: z = H_k g from the last pairs (s, y), qn_lbfgs.hip.h; QN_NONLINEAR_CG: d = beta p - g written directly, qn_cg.hip.h)
 };
 
 // the second-order variants (newton/projected_newton.rs, newton/spn.rs): the same machine, with z = H^-1 g where the first-order family has g
 __device__ __forceinline__ bool vec_newton(int method) { return method == QN_PROJECTED_NEWTON || method == QN_SPECTRAL_PROJECTED_NEWTON; }
 __device__ __forceinline__ bool vec_spectral(int method) { return method == QN_SPG || method == QN_SPECTRAL_PROJECTED_NEWTON; }
 // update_next_iterate calls the oracle at the accepted point, for y (spg.rs:130, spn.rs:135, projected_newton.rs:134)
-__device__ __forceinline__ bool vec_needs_y(int method) { return vec_spectral(method) || method == QN_PROJECTED_NEWTON || method == QN_LBFGS; }
-// the direction is P(x - z) - x with a z that arrives from outside this file, in phase QN_VP_NSOLVE
-__device__ __forceinline__ bool vec_nsolve(int method) { return vec_newton(method) || method == QN_LBFGS; }
+__device__ __forceinline__ bool vec_needs_y(int method) { return vec_spectral(method) || method == QN_PROJECTED_NEWTON || method == QN_LBFGS || method == QN_NONLINEAR_CG; }
+// the direction is P(x - z) - x with a z that arrives from outside this file, in phase QN_VP_NSOLVE (QN_NONLINEAR_CG: the direction itself does)
+__device__ __forceinline__ bool vec_nsolve(int method) { return vec_newton(method) || method == QN_LBFGS || method == QN_NONLINEAR_CG; }
 
 struct QnVecCtl {
     // ---- configuration (host, per call) ----
@@ -87,6 +87,13 @@ struct QnVecCtl {
     double w_finit, w_ginit, w_gtest, w_width, w_width1, w_stx, w_fx, w_gx, w_sty, w_fy, w_gy, w_stmin, w_stmax;
     int32_t w_boxed, w_brackt, w_stage, w_err; // w_err: 1 = g.d >= 0 at the start, 2 = stpmax < stpmin
     int32_t tr_ls_cases, tr_ndigits;           // trace scratch: dcstep's cases of this iteration's search, base 8
+    // ---- QN_NONLINEAR_CG (qn_cg.hip.h): the settings, then what survives calls like lambda ----
+    int32_t cg_variant, cg_has_p; // QN_CG_*; cg_p holds the direction last searched (0: the next direction is -g, rule 1)
+    double cg_powell_nu;          // Powell's restart test (+inf: off)
+    int64_t cg_restart_every;     // 0: never
+    double cg_beta;               // of the last accepted iteration: what the next direction is made with
+    int64_t cg_since;             // iterations since the last -g direction
+    uint64_t cg_restarts;         // betas that ended as exactly 0
 };
 
 struct QnVecArgs {
@@ -101,12 +108,17 @@ struct QnVecArgs {
     int n, np, G;
     // QN_LBFGS: the ring S[lb_m + 1][np], Y[lb_m + 1][np], the Gram kernel's shares, the small block (Gram matrices, u, gamma v), z for writing
     double *lS, *lY, *lpart, *lsmall, *zw;
+    // QN_NONLINEAR_CG: the direction last searched (n_pad doubles, updated in place), the accept kernel's shares [QN_CG_NQ][QN_VEC_MAXG]
+    double *cp, *cpart;
 };
 
 __device__ __forceinline__ double vec_block_max(double v, double* lds) { return ctl_block_fmax(v, lds); }
 // QN_LS_STRONG_WOLFE's part of the loop top (qn_vec_wolfe.hip.h)
 __device__ __forceinline__ double wolfe_min_parts(const double* part, int q, int G, double* lds);
 __device__ __forceinline__ bool wolfe_start(QnVecCtl* c, double gd, double clip);
+// QN_NONLINEAR_CG's part of the post kernel (qn_cg.hip.h): the eight sums (every thread), then beta by the rules (thread 0)
+__device__ __forceinline__ void cg_post_sums(const QnVecArgs& a, double* q, double* lds);
+__device__ __forceinline__ int cg_post(QnVecCtl* c, const double* q);
 
 // d = P(x - lambda g) - x, three roundings per element in that order (spg.rs:81-83); PGD: x - g (projected_gradient_descent.rs:56-58).
 // Before SPG has its lambda the same kernel forms P(x0 - g0) - x0, whose infinity norm gives lambda0 (spg.rs:41-46).
@@ -391,8 +403,12 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_post_kernel(const QnVecArgs a)
         yy = vec_sum_parts(a.part, 5, a.G, lds);
     }
     if (lbfgs) yy = vec_sum_parts(a.part, 5, a.G, lds);
+    const bool cg = c->method == QN_NONLINEAR_CG; // (cg_accept_kernel ran in vec_accept_kernel's place)
+    double cq[8];
+    if (cg) cg_post_sums(a, cq, lds);
     if (threadIdx.x != 0) return;
     int committed = 0;
+    if (cg) committed = cg_post(c, cq); // beta for the next direction; `updated` = beta != 0
     if (lbfgs && sy > DBL_EPSILON * yy) { // the pair in the staging slot joins the memory; otherwise the memory stays as it was
         committed = 1;
         if (c->lb_kmem == c->lb_m) c->lb_head = (c->lb_head + 1) % (c->lb_m + 1); // (the oldest pair's slot is the next staging slot)
@@ -405,7 +421,7 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_post_kernel(const QnVecArgs a)
     }
     if (a.trace && (int64_t)c->n_iter < c->trace_cap) {
         QnTraceRec r;
-        r.f = c->tr_f; r.gnorm = c->tr_gnorm; r.t = c->t; r.s_norm = (vec_spectral(c->method) || c->method == QN_PROJECTED_NEWTON || lbfgs) ? sqrt(ss) : 0.0;
+        r.f = c->tr_f; r.gnorm = c->tr_gnorm; r.t = c->t; r.s_norm = (vec_spectral(c->method) || c->method == QN_PROJECTED_NEWTON || lbfgs || cg) ? sqrt(ss) : 0.0;
         r.y_norm = c->method == QN_PROJECTED_NEWTON ? sqrt(yy) : 0.0;
         r.n_evals = c->tr_n_evals; r.ls_iters = c->tr_ls_iters; r.ls_cases = c->tr_ls_cases; r.updated = committed;
         a.trace[c->n_iter] = r;

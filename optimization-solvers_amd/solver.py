@@ -1144,6 +1144,57 @@ class LBFGS(ProjectedLBFGS):
         return cls(tol, x0, m, ctx, memoize)
 
 
+class NonlinearCG(_SolverBase):
+    """Nonlinear conjugate gradient: `new(tol, x0, variant="pr+", powell_nu=0.2, restart_every=0)`; d+ = beta d - g+ with beta by the variant --
+    "fr" (Fletcher-Reeves), "pr+" (Polak-Ribiere+), "hs+" (Hestenes-Stiefel+), "dy" (Dai-Yuan), "hz" (Hager-Zhang) -- and restarts d = -g by
+    Powell's test |g+.g| >= powell_nu g+.g+ (inf: off), every `restart_every` iterations (0: never), and whenever beta d - g+ would not descend.
+    One extra vector of state.  UNBOUNDED ONLY; line searches: StrongWolfe (what "fr", "dy" and "hs+" assume) and BackTracking."""
+    METHOD = A.NONLINEAR_CG
+    VARIANTS = {"fr": A.CG_FR, "pr+": A.CG_PR_PLUS, "hs+": A.CG_HS_PLUS, "dy": A.CG_DY, "hz": A.CG_HZ}
+
+    def __init__(self, tol, x0, variant="pr+", powell_nu=0.2, restart_every=0, memoize=None, ctx=None):
+        super().__init__(tol, x0, ctx)
+        self.memoize = memoize
+        if (variant, powell_nu, restart_every) != ("pr+", 0.2, 0):
+            self.set_cg(variant, powell_nu, restart_every)
+
+    @classmethod
+    def new(cls, tol, x0, variant="pr+", powell_nu=0.2, restart_every=0, memoize=None, ctx=None):
+        return cls(tol, x0, variant, powell_nu, restart_every, memoize, ctx)
+
+    def set_cg(self, variant="pr+", powell_nu=0.2, restart_every=0):
+        """qn_solver_set_cg: the stored direction is dropped (the next direction is -g)"""
+        code = self.VARIANTS.get(variant, variant)
+        if not isinstance(code, int) or isinstance(code, bool):
+            raise ErrorInputParams('NonlinearCG: unknown variant (one of "fr", "pr+", "hs+", "dy", "hz")')
+        if not 0 <= int(restart_every) < 2 ** 63:
+            raise ErrorInputParams("NonlinearCG: restart_every must not be negative")
+        _check(A.lib().qn_solver_set_cg(self.h, code, float(powell_nu), int(restart_every)))
+
+    def _cg_state(self):
+        variant, beta, restarts, since = C.c_int(), C.c_double(), C.c_size_t(), C.c_size_t()
+        _check(A.lib().qn_solver_cg_state(self.h, C.byref(variant), C.byref(beta), C.byref(restarts), C.byref(since)))
+        return variant.value, beta.value, restarts.value, since.value
+
+    @property
+    def variant(self):
+        code = self._cg_state()[0]
+        return next(k for k, v in self.VARIANTS.items() if v == code)
+
+    def beta(self):
+        """of the last accepted iteration: what the next direction is made with (0 before the first, and after a restart)"""
+        return self._cg_state()[1]
+
+    def restarts(self):
+        return self._cg_state()[2]
+
+    def since_restart(self):
+        return self._cg_state()[3]
+
+    def grad_tol(self):
+        return self.tol()
+
+
 class Newton(_SolverBase):
     """newton/mod.rs: direction from a dense factorisation of the Hessian on the GPU."""
     METHOD = A.NEWTON

@@ -39,6 +39,12 @@ pub const QN_COORDINATE_DESCENT: c_int = 10;
 pub const QN_PNORM_DESCENT: c_int = 11;
 pub const QN_LBFGS: c_int = 12;
 pub const QN_LBFGS_MAX_M: usize = 32;
+pub const QN_NONLINEAR_CG: c_int = 13;
+pub const QN_CG_FR: c_int = 0;
+pub const QN_CG_PR_PLUS: c_int = 1;
+pub const QN_CG_HS_PLUS: c_int = 2;
+pub const QN_CG_DY: c_int = 3;
+pub const QN_CG_HZ: c_int = 4;
 
 // qn_option (ABI 5): what rounds 1-5 selected through negative codes of qn_solver_set_tiling; value != 0 on, 0 off
 pub const QN_OPT_GENERIC_KERNELS: c_int = 1;
@@ -83,6 +89,7 @@ pub const QN_PATH_PNEWTON: u32 = 128;
 pub const QN_PATH_RANK1: u32 = 256;
 pub const QN_PATH_PNORM: u32 = 512;
 pub const QN_PATH_LBFGS: u32 = 1024;
+pub const QN_PATH_CG: u32 = 2048;
 
 #[repr(C)] pub struct qn_context { _p: [u8; 0] }
 #[repr(C)] pub struct qn_solver { _p: [u8; 0] }
@@ -248,6 +255,8 @@ extern "C" {
     pub fn qn_solver_newton_factorisations(s: *mut qn_solver, out: *mut usize) -> c_int;
     pub fn qn_solver_set_lbfgs_memory(s: *mut qn_solver, m: usize) -> c_int;
     pub fn qn_solver_lbfgs_state(s: *mut qn_solver, m: *mut usize, stored: *mut usize, gamma: *mut f64, resets: *mut usize) -> c_int;
+    pub fn qn_solver_set_cg(s: *mut qn_solver, variant: c_int, powell_nu: f64, restart_every: usize) -> c_int;
+    pub fn qn_solver_cg_state(s: *mut qn_solver, variant: *mut c_int, beta: *mut f64, restarts: *mut usize, since_restart: *mut usize) -> c_int;
     pub fn qn_solver_reset(s: *mut qn_solver, x0_host: *const f64) -> c_int;
     pub fn qn_minimize(s: *mut qn_solver, ls: *mut qn_linesearch, oracle: *const qn_oracle, max_iter_solver: usize, max_iter_line_search: usize, callback: qn_callback_fn, callback_user: *mut c_void) -> c_int;
     pub fn qn_compute_step_len(ctx: *mut qn_context, ls: *mut qn_linesearch, x_k_host: *const f64, f_k: f64, g_k_host: *const f64, direction_host: *const f64, n: usize, oracle: *const qn_oracle, max_iter: usize, step_out: *mut f64) -> c_int;

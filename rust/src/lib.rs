@@ -865,6 +865,60 @@ macro_rules! lbfgs_memory {
 lbfgs_memory!(GpuLbfgs);
 lbfgs_memory!(GpuProjectedLbfgs);
 
+gpu_solver!(
+    /// Nonlinear conjugate gradient: `new(tol, x0).with_variant(CgVariant::HagerZhang, 0.2, 0)`; d+ = beta d - g+ with one extra vector of state on
+    /// the GPU (QN_PATH_CG): the accept pass leaves every inner product beta needs, so the direction costs one stream and no reduction launch of
+    /// its own.  Restarts d = -g by Powell's test |g+.g| >= powell_nu g+.g+ (`f64::INFINITY`: off), every `restart_every` iterations (0: never) and
+    /// whenever beta d - g+ would not descend.  UNBOUNDED ONLY; `GpuStrongWolfe` (what FR, DY and HS+ assume) or `GpuBackTracking`.  Drive it
+    /// with `minimize_on_device` / `minimize_objective`: the direction lives on the device.
+    GpuNonlinearCg, QN_NONLINEAR_CG, false
+);
+
+/// `qn_solver_set_cg`'s variants
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum CgVariant {
+    FletcherReeves,
+    PolakRibierePlus,
+    HestenesStiefelPlus,
+    DaiYuan,
+    HagerZhang,
+}
+
+impl CgVariant {
+    fn code(self) -> c_int {
+        match self {
+            CgVariant::FletcherReeves => QN_CG_FR,
+            CgVariant::PolakRibierePlus => QN_CG_PR_PLUS,
+            CgVariant::HestenesStiefelPlus => QN_CG_HS_PLUS,
+            CgVariant::DaiYuan => QN_CG_DY,
+            CgVariant::HagerZhang => QN_CG_HZ,
+        }
+    }
+    fn from_code(code: c_int) -> Self {
+        match code {
+            QN_CG_FR => CgVariant::FletcherReeves,
+            QN_CG_HS_PLUS => CgVariant::HestenesStiefelPlus,
+            QN_CG_DY => CgVariant::DaiYuan,
+            QN_CG_HZ => CgVariant::HagerZhang,
+            _ => CgVariant::PolakRibierePlus,
+        }
+    }
+}
+
+impl GpuNonlinearCg {
+    /// the variant (Polak-Ribiere+ by default), Powell's nu (0.2) and restart_every (0: never); the stored direction is dropped
+    pub fn with_variant(self, variant: CgVariant, powell_nu: Floating, restart_every: usize) -> Self {
+        assert_eq!(unsafe { qn_solver_set_cg(self.core.h, variant.code(), powell_nu, restart_every) }, QN_OK, "{}", last_error());
+        self
+    }
+    /// (variant, beta of the last accepted iteration, betas that ended as exactly 0, iterations since the last -g direction)
+    pub fn cg_state(&self) -> (CgVariant, Floating, usize, usize) {
+        let (mut variant, mut beta, mut restarts, mut since) = (0 as c_int, 0.0, 0usize, 0usize);
+        assert_eq!(unsafe { qn_solver_cg_state(self.core.h, &mut variant, &mut beta, &mut restarts, &mut since) }, QN_OK, "{}", last_error());
+        (CgVariant::from_code(variant), beta, restarts, since)
+    }
+}
+
 macro_rules! bounded_first_order {
     ($name:ident) => {
         impl $name {
