@@ -111,7 +111,8 @@ enum { QN_LS_MORETHUENTE = 0, QN_LS_BACKTRACKING = 1,
        QN_LS_MORETHUENTE_B = 2 /* MoreThuenteB, morethuente_b.rs */, QN_LS_BACKTRACKING_B = 3 /* BackTrackingB, backtracking_b.rs */,
        QN_LS_GLL_QUADRATIC = 4 /* GLLQuadratic, gll_quadratic.rs: the non-monotone search of Grippo, Lampariello, Lucidi; QN_SPG / QN_PROJECTED_GRADIENT only */,
        QN_LS_NO_SEARCH = 5 /* NoSearch, nosearch.rs: constant step 1.0 */,
-       QN_LS_STRONG_WOLFE = 6 /* StrongWolfe: MINPACK-2 dcsrch; the first-order family, the projected Newton pair, QN_LBFGS and QN_NONLINEAR_CG only */ };
+       QN_LS_STRONG_WOLFE = 6 /* StrongWolfe: MINPACK-2 dcsrch; the first-order family, the projected Newton pair, QN_LBFGS and QN_NONLINEAR_CG only */,
+       QN_LS_EXACT_QUADRATIC = 7 /* ExactQuadratic: the exact step -g.d / d'Qd on a device quadratic; QN_SPG, QN_PROJECTED_GRADIENT, QN_LBFGS, QN_NONLINEAR_CG only */ };
 typedef struct {
     int32_t kind;
     int32_t _pad;
@@ -161,6 +162,26 @@ void qn_gll_quadratic_with_sigmas(qn_linesearch* ls, double sigma1, double sigma
  * bit 30 when the search switched to its second stage.  qn_compute_step_len: QN_ERROR_INPUT_PARAMS for this kind. */
 void qn_strong_wolfe_new(qn_linesearch* ls, double c1, double c2);
 int qn_strong_wolfe_with_xtol(qn_linesearch* ls, double xtol);
+/* ExactQuadratic (QN_LS_EXACT_QUADRATIC; no counterpart among the reference's line searches): on f = 1/2 x'Qx - b'x the minimiser along d is
+ * t = -g.d / d'Qd.  It costs ONE product q = Q d (the curvature pass of qn_objective_hess_vec), after which g(x + t d) = g + t q and
+ * f(x + t d) = f + t (g.d + (t / 2) d'Qd) need no second pass over the matrix.  No value of f is ever compared: the step is accepted as it is.  With
+ * QN_NONLINEAR_CG this is linear conjugate gradients.
+ * Methods: QN_SPG, QN_PROJECTED_GRADIENT, QN_LBFGS (free and with a box), QN_NONLINEAR_CG; objectives: the dense and the sparse device quadratic.
+ * QN_ERROR_INPUT_PARAMS with the reason in qn_last_error_message: a host closure, a device closure or log-sum-exp ("the exact step needs a device
+ * quadratic"), every other method, qn_compute_step_len, a search with a box of its own (lower_bound_host / upper_bound_host set), refresh_every < 0.
+ * ONE SEARCH: (1) the loop top leaves g.d; unless g.d < 0 the run ends with QN_ABNORMAL_TERMINATION ("ExactQuadratic: not a descent direction"),
+ * x at x_k; (2) q = Q d and c = d.q (products and sums round separately, fixed orders); (3) unless c > 0 and finite: QN_ABNORMAL_TERMINATION
+ * ("ExactQuadratic: non-positive curvature along the direction"), x at x_k; (4) t = (-g.d) / c, one division; on a solver with a box t = min(t, 1)
+ * (a comparison): there d = P(x - z) - x, so t <= 1 keeps x + t d feasible; (5) xt = x + t d, t d rounded first; (6) (f_t, gt) at xt: on a REFRESH
+ * iteration the objective's own launches, otherwise gt_i = g_i + t q_i (t q_i rounded first) and f_t = f + t (g.d + (0.5 t) c); (7) accepted.
+ * REFRESH: refresh_every = r travels in `_pad`.  r = 1 (what every binding's default is): the objective evaluates every accepted point -- two matrix
+ * passes per iteration, every gradient a true one.  r = k > 1: every k-th accepted point (the count survives calls, qn_solver_reset clears it).
+ * r = 0: never -- except that the first evaluation at x is always the objective's, and that CONVERGENCE IS DECLARED ONLY ON A TRUE GRADIENT: when the
+ * loop top's test passes on a gradient that came from the recurrence, the run does not stop; x is evaluated by the objective (a forced refresh,
+ * counted) and the loop top runs again.  The oracle's `memoize` is not consulted: the evaluation of the accepted point is always kept.
+ * qn_stats: oracle_evals counts evaluations by the objective only; curvature passes are reported by qn_solver_exact_state and counted in obj_bytes
+ * (sparse: 12 nnz + 4 (n + 1) + 16 n each; dense: the matrix once) and in launches. */
+void qn_exact_quadratic_new(qn_linesearch* ls, int refresh_every);
 
 /* ---------------------------------------------------------------------------------------------
  * Oracle: `impl FnMut(&DVector<f64>) -> FuncEvalMultivariate` (ls_solver.rs:69, func_eval.rs:4-41).
@@ -235,6 +256,14 @@ int qn_objective_get_rows(qn_objective* obj, size_t row0, size_t nrows, double* 
  * bit for bit, the same bits for the same x.  The n_pad x n_pad device matrix is allocated by the first call.  h_colmajor_host == NULL: the
  * launches run and are waited for, nothing is downloaded.  One rank (a row-sharded context: QN_ERROR_INPUT_PARAMS). */
 int qn_objective_hessian(qn_objective* obj, const double* x_host, double* h_colmajor_host);
+/* the Hessian-vector product of a quadratic at a host vector: q = Q v into q_host (n entries; NULL: not downloaded) and the curvature v'Qv into
+ * *vqv -- what the exact step t = -g.d / d'Qd along d costs, and what a binding needs for a conjugate-gradient loop of its own.  One pass over
+ * the matrix and no evaluation of f.  A sparse quadratic: the CSR kernel's curvature form (csrc/qn_sparse.hip.h) -- the structure, the lanes per
+ * row and the summation order inside a row of an evaluation, so q has the bits an evaluation at v with b = 0 gives g; 12 nnz + 4 (n + 1) + 16 n
+ * bytes, 8 n fewer than an evaluation.  A dense quadratic: the row kernel of an evaluation with the point set to v, then one workgroup that forms
+ * v.q.  v'Qv's products and sums round separately, in a fixed order: the same bits for the same v from run to run and from object to object.
+ * Log-sum-exp: QN_ERROR_INPUT_PARAMS (not built).  One rank (a row-sharded context: QN_ERROR_INPUT_PARAMS). */
+int qn_objective_hess_vec(qn_objective* obj, const double* v_host, double* q_host, double* vqv);
 
 /* ---------------------------------------------------------------------------------------------
  * Solvers: BFGS (bfgs.rs:4-127), DFP (dfp.rs), Broyden (broyden.rs), GradientDescent (gradient_descent.rs:7-82), Newton (newton/mod.rs).
@@ -309,11 +338,12 @@ enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton
         * restart (qn_solver_cg_state); the trace's `updated` is beta != 0, s_norm = ||s||, gnorm = ||g||_inf.  It runs on the first-order family's
         * machine (QN_PATH_VECTOR | QN_PATH_CG, csrc/qn_cg.hip.h): the accept pass leaves every inner product beta needs, so the direction costs one
         * stream (16 n bytes read, 16 n written) and no reduction launch of its own.  UNBOUNDED ONLY: qn_solver_set_bounds gives QN_ERROR_INPUT_PARAMS,
-        * as does qn_solver_compute_direction (use qn_minimize).  Line searches: QN_LS_STRONG_WOLFE (what FR, DY and HS+ assume) and QN_LS_BACKTRACKING;
+        * as does qn_solver_compute_direction (use qn_minimize).  Line searches: QN_LS_STRONG_WOLFE (what FR, DY and HS+ assume), QN_LS_BACKTRACKING and,
+        * on a device quadratic, QN_LS_EXACT_QUADRATIC (the exact step: linear conjugate gradients);
         * QN_LS_GLL_QUADRATIC, QN_LS_BACKTRACKING_B and both More-Thuente kinds: QN_ERROR_INPUT_PARAMS.  Every oracle kind of the family, memoize 0 / 1,
         * trace, callbacks, warm restarts (the direction and beta survive calls: two calls of k iterations give the bits of one call of 2 k), one rank.
         * The first trial step of every search is 1, as everywhere in this family.  Profiling mode: t_hpass_ms = cg_dir_kernel, t_hreduce_ms =
-        * cg_accept_kernel.  Not built: a box, preconditioning, an initial-step rule, the exact step on quadratics, qn_compute_step_len. */
+        * cg_accept_kernel.  Not built: a box, preconditioning, an initial-step rule, qn_compute_step_len. */
        QN_NONLINEAR_CG = 13 /* nonlinear conjugate gradient; no counterpart in the reference */ };
 #define QN_LBFGS_MAX_M 32
 /* QN_NONLINEAR_CG's variants (qn_solver_set_cg) */
@@ -352,6 +382,10 @@ int qn_solver_set_cg(qn_solver* s, int variant, double powell_nu, size_t restart
 /* QN_NONLINEAR_CG: the variant, the beta of the last accepted iteration (0 before the first), the betas that ended as exactly 0 and the iterations
  * since the last -g direction, since qn_solver_create / qn_solver_reset.  Any pointer may be NULL.  Other methods: QN_ERROR_INPUT_PARAMS. */
 int qn_solver_cg_state(qn_solver* s, int* variant, double* beta, size_t* restarts, size_t* since_restart);
+/* QN_LS_EXACT_QUADRATIC, of the last qn_minimize: the curvature passes, the accepted points (and forced re-evaluations of x) that the objective
+ * evaluated -- the first evaluation at x is not counted --, and the last search's step and curvature d'Qd.  Any pointer may be NULL.  A solver
+ * outside the first-order family: QN_ERROR_INPUT_PARAMS. */
+int qn_solver_exact_state(qn_solver* s, size_t* curvature_passes, size_t* refreshes, double* last_t, double* last_curvature);
 /* QN_PNORM_DESCENT: inverse_p of PnormDescent::new(grad_tol, x0, inverse_p) (pnorm_descent.rs:20-27) and its getter; column-major n x n, like DMatrix
  * and like qn_solver_set_inv_hessian.  ANY matrix is accepted: the reference tests neither symmetry nor definiteness.  It is a constructor argument,
  * not state: qn_solver_reset keeps it.  Other methods: QN_ERROR_INPUT_PARAMS. */
@@ -470,6 +504,7 @@ typedef struct {
 #define QN_PATH_PNORM 512u     /* QN_PNORM_DESCENT's directions: pnorm_dir_kernel of csrc/qn_pnorm.hip.h (one read-only stream of inverse_p, with g.d and ||g||_inf in the same launch) */
 #define QN_PATH_LBFGS 1024u    /* QN_LBFGS: the direction from the compact form of L-BFGS, two streams of the memory per iteration (csrc/qn_lbfgs.hip.h); set beside QN_PATH_VECTOR */
 #define QN_PATH_CG 2048u       /* QN_NONLINEAR_CG: the direction d = beta p - g written by cg_dir_kernel, beta from the accept pass's sums (csrc/qn_cg.hip.h); set beside QN_PATH_VECTOR */
+#define QN_PATH_EXACT 4096u    /* QN_LS_EXACT_QUADRATIC: the step from one curvature pass, (f, g) of the accepted point by the recurrence or by the objective (csrc/qn_vec_exact.hip.h); set beside QN_PATH_VECTOR */
 int qn_solver_get_stats(qn_solver* s, qn_stats* out);
 /* profiling != 0: bracket every launch with HIP events on the solver's stream (slower; for roofline reports) */
 int qn_solver_set_profiling(qn_solver* s, int on);

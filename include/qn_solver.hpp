@@ -190,6 +190,24 @@ class StrongWolfe {
     qn_linesearch& ffi() { return s_; }
 };
 
+// ExactQuadratic (QN_LS_EXACT_QUADRATIC): the exact step -g.d / d'Qd on a device quadratic (Quadratic, SparseQuadratic) for SpectralProjectedGradient,
+// ProjectedGradientDescent, LBFGS / ProjectedLBFGS and NonlinearCG -- with the last, linear conjugate gradients.  refresh_every = 1: the objective
+// evaluates every accepted point; k > 1: every k-th; 0: never, except that convergence is only declared on a gradient the objective evaluated.
+class ExactQuadratic {
+    qn_linesearch s_;
+  public:
+    explicit ExactQuadratic(int refresh_every = 1) { qn_exact_quadratic_new(&s_, refresh_every); }
+    static ExactQuadratic new_(int refresh_every = 1) { return ExactQuadratic(refresh_every); }
+    int refresh_every() const { return s_._pad; }
+    qn_linesearch& ffi() { return s_; }
+};
+
+// what ExactQuadratic did in the last minimize (qn_solver_exact_state)
+struct ExactState {
+    size_t curvature_passes = 0, refreshes = 0;
+    Floating last_t = 0, last_curvature = 0;
+};
+
 // backtracking_b.rs: projected trial points; keeps its own copies of the box
 class BackTrackingB {
     qn_linesearch s_;
@@ -223,6 +241,13 @@ class Quadratic {
         DVector h(n_ * n_);
         check(qn_objective_hessian(h_, x.data(), h.data()));
         return h;
+    }
+    std::pair<DVector, Floating> hess_vec(const DVector& v) const { // (Q v, v'Qv): one pass over Q, no evaluation of f
+        if (v.size() != n_) throw SolverError{SolverError::ErrorInputParams, "v does not have the objective's n entries"};
+        DVector q(n_);
+        Floating c = 0;
+        check(qn_objective_hess_vec(h_, v.data(), q.data(), &c));
+        return {std::move(q), c};
     }
 };
 
@@ -278,6 +303,13 @@ class SparseQuadratic {
         check(qn_objective_eval(h_, x.data(), &f, g.data()));
         return FuncEvalMultivariate(f, std::move(g));
     }
+    std::pair<DVector, Floating> hess_vec(const DVector& v) const { // (Q v, v'Qv): the CSR kernel's curvature form, one pass over Q
+        if (v.size() != n_) throw SolverError{SolverError::ErrorInputParams, "v does not have the objective's n entries"};
+        DVector q(n_);
+        Floating c = 0;
+        check(qn_objective_hess_vec(h_, v.data(), q.data(), &c));
+        return {std::move(q), c};
+    }
     size_t nnz() const { size_t v = 0; check(qn_objective_sparse_info(h_, &v, nullptr, nullptr, nullptr)); return v; }
     int lanes_per_row() const { int v = 0; check(qn_objective_sparse_info(h_, nullptr, &v, nullptr, nullptr)); return v; }
     size_t n_long_rows() const { size_t v = 0; check(qn_objective_sparse_info(h_, nullptr, nullptr, &v, nullptr)); return v; }
@@ -298,6 +330,11 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
         check(qn_solver_create(ctx.handle(), METHOD, tol, x0.data(), x0.size(), &h_));
     }
     qn_solver* handle() const { return h_; }
+    ExactState exact_state() const { // ExactQuadratic, of the last minimize (the first-order family's solvers)
+        ExactState e;
+        check(qn_solver_exact_state(h_, &e.curvature_passes, &e.refreshes, &e.last_t, &e.last_curvature));
+        return e;
+    }
     static Self new_(Floating tol, const DVector& x0) { return Self(tol, x0); }
     LineSearchSolver(const Self&) = delete;
     LineSearchSolver(Self&& o) noexcept : h_(o.h_), n_(o.n_) { o.h_ = nullptr; }

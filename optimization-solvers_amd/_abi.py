@@ -10,6 +10,7 @@ OK, MAX_ITER_REACHED, OUT_OF_DOMAIN, ERROR_INPUT_PARAMS, ABNORMAL_TERMINATION = 
 LS_MORETHUENTE, LS_BACKTRACKING, LS_MORETHUENTE_B, LS_BACKTRACKING_B, LS_GLL_QUADRATIC = 0, 1, 2, 3, 4
 LS_NO_SEARCH = 5  # line_search/nosearch.rs
 LS_STRONG_WOLFE = 6  # MINPACK-2 dcsrch on the vector machine (no counterpart among the reference's searches)
+LS_EXACT_QUADRATIC = 7  # the exact step -g.d / d'Qd on a device quadratic (no counterpart among the reference's searches)
 ORACLE_HOST, ORACLE_DEVICE_FN, ORACLE_OBJECTIVE = 0, 1, 2
 BFGS, DFP, GRADIENT_DESCENT, NEWTON, SR1, SPG, PROJECTED_GRADIENT, PROJECTED_NEWTON, SPECTRAL_PROJECTED_NEWTON = 0, 1, 2, 3, 4, 5, 6, 7, 8
 BROYDEN = 9  # quasi_newton/broyden.rs (BroydenB once bounds are set)
@@ -71,6 +72,7 @@ PATH_RANK1 = 256
 PATH_PNORM = 512
 PATH_LBFGS = 1024
 PATH_CG = 2048
+PATH_EXACT = 4096
 
 
 # every symbol include/qn_hip.h declares: (name, restype, argtypes)
@@ -112,6 +114,7 @@ SYMBOLS = [
     ("qn_gll_quadratic_with_sigmas", None, [C.POINTER(LineSearchStruct), C.c_double, C.c_double]),
     ("qn_strong_wolfe_new", None, [C.POINTER(LineSearchStruct), C.c_double, C.c_double]),
     ("qn_strong_wolfe_with_xtol", C.c_int, [C.POINTER(LineSearchStruct), C.c_double]),
+    ("qn_exact_quadratic_new", None, [C.POINTER(LineSearchStruct), C.c_int]),
     ("qn_quadratic_create", C.c_int, [C.c_void_p, C.c_size_t, dp, dp, C.POINTER(C.c_void_p)]),
     ("qn_quadratic_create_synthetic", C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, dp, dp, C.POINTER(C.c_void_p)]),
     ("qn_logsumexp_create", C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, dp, dp, C.c_double, C.POINTER(C.c_void_p)]),
@@ -122,6 +125,7 @@ SYMBOLS = [
     ("qn_objective_eval", C.c_int, [C.c_void_p, dp, dp, dp]),
     ("qn_objective_get_rows", C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, dp]),
     ("qn_objective_hessian", C.c_int, [C.c_void_p, dp, dp]),
+    ("qn_objective_hess_vec", C.c_int, [C.c_void_p, dp, dp, dp]),
     ("qn_solver_create", C.c_int, [C.c_void_p, C.c_int, C.c_double, dp, C.c_size_t, C.POINTER(C.c_void_p)]),
     ("qn_solver_destroy", None, [C.c_void_p]),
     ("qn_solver_reset", C.c_int, [C.c_void_p, dp]),
@@ -135,6 +139,7 @@ SYMBOLS = [
     ("qn_solver_lbfgs_state", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), dp, C.POINTER(C.c_size_t)]),
     ("qn_solver_set_cg", C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_size_t]),
     ("qn_solver_cg_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int), dp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("qn_solver_exact_state", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), dp, dp]),
     ("qn_minimize", C.c_int, [C.c_void_p, C.POINTER(LineSearchStruct), C.POINTER(OracleStruct), C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("qn_compute_step_len", C.c_int, [C.c_void_p, C.POINTER(LineSearchStruct), dp, C.c_double, dp, dp, C.c_size_t, C.POINTER(OracleStruct), C.c_size_t,
                              C.POINTER(C.c_double)]),

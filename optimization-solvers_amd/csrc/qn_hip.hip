@@ -75,3 +75,5 @@ extern "C" const char* qn_status_string(int status) {
 // nonlinear conjugate gradient on the first-order family's machine: its direction and accept kernels, behind every existing kernel
 #include "qn_cg.hip.h"
 #include "qn_host_cg.hip.h"
+// the curvature pass of the device quadratics (q = Q v, v'Qv) and qn_objective_hess_vec: behind every existing kernel
+#include "qn_vec_exact.hip.h"

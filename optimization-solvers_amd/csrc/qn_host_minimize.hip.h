@@ -518,6 +518,7 @@ static int minimize_impl(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, si
     if (!s || !ls || !o) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
     if (vec_method(s->method)) return vec_minimize(s, ls, o, max_iter_solver, max_iter_line_search, callback, callback_user, ls_only, ls_f0);
     if (ls->kind == QN_LS_GLL_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "GLLQuadratic pairs with SPG / projected gradient only");
+    if (ls->kind == QN_LS_EXACT_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "ExactQuadratic pairs with SPG / projected gradient / L-BFGS / NonlinearCG only");
     qn_context* c = s->ctx;
     HIPCHK(hipSetDevice(c->device));
     Run r{s, o, nullptr, QN_ORACLE_GENERIC, false};
@@ -548,6 +549,7 @@ extern "C" int qn_compute_step_len(qn_context* ctx, qn_linesearch* ls, const dou
                                    const double* direction_host, size_t n, const qn_oracle* oracle, size_t max_iter, double* step_out) {
     if (!ctx || !ls || !x_k_host || !g_k_host || !direction_host || !oracle || !step_out || n == 0)
         return fail(QN_ERROR_INPUT_PARAMS, "null argument");
+    if (ls->kind == QN_LS_EXACT_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "ExactQuadratic: compute_step_len on its own is not built: use qn_minimize");
     if (ls->kind == QN_LS_GLL_QUADRATIC) return vec_compute_step_len(ctx, ls, x_k_host, f_k, g_k_host, direction_host, n, oracle, max_iter, step_out);
     qn_solver* s = nullptr;
     QNCHK(qn_solver_create(ctx, QN_GRADIENT_DESCENT, 0.0, x_k_host, n, &s)); // owns x and the work vectors; no inverse Hessian

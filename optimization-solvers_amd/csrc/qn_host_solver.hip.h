@@ -113,8 +113,10 @@ struct qn_solver {
     uint64_t pn_factorisations = 0;
     DevBuf<double> lb_ring, lb_part, lb_small; // QN_LBFGS (qn_lbfgs.hip.h): S and Y, [2][lb_m + 1][n_pad]; the Gram kernel's shares; Gram matrices and coefficients
     DevBuf<double> cg_p, cg_part; // QN_NONLINEAR_CG (qn_cg.hip.h): the direction last searched, [n_pad]; the accept kernel's shares, [QN_CG_NQ][QN_VEC_MAXG]
+    DevBuf<double> ex_q, ex_c; // QN_LS_EXACT_QUADRATIC (qn_vec_exact.hip.h): q = Q d of the last curvature pass, [n_pad]; d'Qd of a dense quadratic, [2]
     DevBuf<double> bounds_block; // lb, ub (solver), llb, lub (bounded line search): 4 n_pad vectors
     int bounded = 0;
+    int box_finite = 0; // qn_solver_set_bounds gave at least one finite bound (ExactQuadratic caps its step at 1 only then: with (-inf, +inf) d = P(x - z) - x is -z)
     DevBuf<double> fused_block; // X0[2], S0[2], G, GT, Y, UN, UP, VV (10 n_pad vectors), then the older of two pending updates' s and u (fused_so, fused_uo)
     DevBuf<double> fused_evp, fused_hpp;
     int fused_nblk = 0;
@@ -658,6 +660,9 @@ extern "C" int qn_solver_set_bounds(qn_solver* s, const double* lb_host, const d
     QNCHK(qn_solver_get_x(s, x.data()));
     for (size_t i = 0; i < s->n; ++i) x[i] = std::fmin(std::fmax(x[i], lb_host[i]), ub_host[i]); // x0.box_projection(&lower, &upper), :49
     s->bounded = 1;
+    s->box_finite = 0;
+    for (size_t i = 0; i < s->n; ++i)
+        if (std::isfinite(lb_host[i]) || std::isfinite(ub_host[i])) s->box_finite = 1;
     return qn_solver_set_x(s, x.data());
 }
 

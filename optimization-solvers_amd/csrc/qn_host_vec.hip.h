@@ -39,6 +39,9 @@ static int lbfgs_enqueue_accept(VecRun& r);
 static int cg_state_alloc(qn_solver* s); // QN_NONLINEAR_CG: qn_host_cg.hip.h
 static int cg_enqueue_direction(VecRun& r);
 static int cg_enqueue_accept(VecRun& r);
+static int exact_state_alloc(qn_solver* s); // QN_LS_EXACT_QUADRATIC: qn_vec_exact.hip.h
+static int exact_enqueue_step(VecRun& r);
+static int exact_enqueue_advance(VecRun& r);
 static int vec_grid(size_t np) { // a function of n alone: four 16-byte accesses per thread until 4 workgroups per CU are out
     const size_t per = (size_t)QN_VEC_TPB * 2 * 4;
     return (int)std::min<size_t>(QN_VEC_MAXG, std::max<size_t>(1, (np + per - 1) / per));
@@ -63,6 +66,7 @@ static void vec_state_reset(qn_solver* s) { // back to the state right after ::n
     h->has_lambda = 0; h->lambda = 0.0; h->have_eval = 0; h->ring_len = 0; h->k = 0; h->n_iter = 0;
     h->lb_kmem = 0; h->lb_head = 0; h->lb_gamma = 1.0; h->lb_resets = 0; // QN_LBFGS: an empty memory (lb_m and the scaling switch are settings: kept)
     h->cg_has_p = 0; h->cg_beta = 0.0; h->cg_since = 0; h->cg_restarts = 0; // QN_NONLINEAR_CG: no direction yet (the variant, nu and restart_every are settings: kept)
+    h->ex_since = 0; h->ex_g_true = 0; // QN_LS_EXACT_QUADRATIC: no accepted point yet (the next evaluation at x is the objective's: have_eval is 0)
     h->has_sy = 0; h->s_norm = 0.0; h->y_norm = 0.0; // (the Cholesky factor of a device quadratic's Hessian is kept: it is keyed on the objective)
 }
 
@@ -231,17 +235,27 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     QNCHK(check_oracle(c, s->n, o, &r.obj));
     if (r.obj && r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_LOGSUMEXP && r.obj->kind != OBJ_SPARSE_QUADRATIC)
         return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
+    const bool exact = ls->kind == QN_LS_EXACT_QUADRATIC;
+    if (exact) { // the exact step -g.d / d'Qd: a device quadratic under the four O(n) methods (qn_vec_exact.hip.h)
+        if (pn) return fail(QN_ERROR_INPUT_PARAMS, "ExactQuadratic is not built for the projected Newton pair: it runs under SPG, projected gradient, L-BFGS and NonlinearCG");
+        if (ls_only) return fail(QN_ERROR_INPUT_PARAMS, "ExactQuadratic: compute_step_len on its own is not built: use qn_minimize");
+        if (!r.obj || (r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_SPARSE_QUADRATIC))
+            return fail(QN_ERROR_INPUT_PARAMS, "ExactQuadratic: the exact step needs a device quadratic (Quadratic or SparseQuadratic), not a closure or log-sum-exp");
+        if (ls->lower_bound_host || ls->upper_bound_host)
+            return fail(QN_ERROR_INPUT_PARAMS, "ExactQuadratic holds no box of its own: lower_bound_host / upper_bound_host must not be set (the solver's box caps the step at 1)");
+        if (ls->_pad < 0) return fail(QN_ERROR_INPUT_PARAMS, "ExactQuadratic: refresh_every must not be negative");
+    }
     if (cg) { // unbounded only: the searches that hold or imply a box, and the non-monotone one, are not this method's
         if (ls_only) return fail(QN_ERROR_INPUT_PARAMS, "compute_step_len runs on a first-order solver");
-        if (ls->kind != QN_LS_STRONG_WOLFE && ls->kind != QN_LS_BACKTRACKING)
-            return fail(QN_ERROR_INPUT_PARAMS, "NonlinearCG takes StrongWolfe or BackTracking (GLLQuadratic, BackTrackingB and More-Thuente: out of scope)");
+        if (ls->kind != QN_LS_STRONG_WOLFE && ls->kind != QN_LS_BACKTRACKING && !exact)
+            return fail(QN_ERROR_INPUT_PARAMS, "NonlinearCG takes StrongWolfe or BackTracking, or ExactQuadratic on a device quadratic (GLLQuadratic, BackTrackingB and More-Thuente: out of scope)");
         if (ls->lower_bound_host || ls->upper_bound_host) return fail(QN_ERROR_INPUT_PARAMS, "NonlinearCG is unbounded only: StrongWolfe's box is out of scope");
         if (s->bounded) return fail(QN_ERROR_INPUT_PARAMS, "NonlinearCG is unbounded only");
     }
     if (ls->kind == QN_LS_MORETHUENTE || ls->kind == QN_LS_MORETHUENTE_B)
         return fail(QN_ERROR_INPUT_PARAMS, "More-Thuente with SPG / projected gradient / projected Newton / L-BFGS is out of scope: use GLLQuadratic, BackTracking or BackTrackingB");
     const bool wolfe = ls->kind == QN_LS_STRONG_WOLFE;
-    if (ls->kind != QN_LS_GLL_QUADRATIC && ls->kind != QN_LS_BACKTRACKING && ls->kind != QN_LS_BACKTRACKING_B && !wolfe)
+    if (ls->kind != QN_LS_GLL_QUADRATIC && ls->kind != QN_LS_BACKTRACKING && ls->kind != QN_LS_BACKTRACKING_B && !wolfe && !exact)
         return fail(QN_ERROR_INPUT_PARAMS, "unknown line search");
     if (wolfe) {
         if (ls_only) return fail(QN_ERROR_INPUT_PARAMS, "StrongWolfe: compute_step_len on its own is not built: use qn_minimize");
@@ -259,6 +273,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
             return fail(QN_ERROR_INPUT_PARAMS, "Hessian not available in the oracle"); // projected_newton.rs:73, spn.rs:85 .expect(...)
     }
     QNCHK(vec_state_alloc(s));
+    if (exact) QNCHK(exact_state_alloc(s));
     hipStream_t st = c->stream;
     const size_t np = s->T.n_pad;
     if (ls->kind == QN_LS_BACKTRACKING_B || wolfe_boxed) {
@@ -274,6 +289,9 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     if (ls->kind == QN_LS_GLL_QUADRATIC) { h->c1 = ls->c1; h->m = ls->_pad; h->sigma1 = ls->delta_min; h->sigma2 = ls->delta_max; h->beta = 0.0; }
     else if (wolfe) { h->c1 = ls->c1; h->w_c2 = ls->c2; h->w_xtol = ls->delta; h->w_tmin = ls->t_min; h->w_tmax = ls->t_max; h->beta = 0.0; h->m = 0; }
     else { h->c1 = ls->bt_c1; h->beta = ls->bt_beta; h->m = 0; }
+    if (exact) { h->c1 = 0.0; h->beta = 0.0; h->m = 0; h->memoize = 1; } // (the accepted point's evaluation is always kept: memoize 0 and 1 run the same launches)
+    h->ex_refresh_every = exact ? ls->_pad : 0; h->ex_err = 0; h->ex_adv = 0; h->ex_passes = 0; h->ex_refreshes = 0; h->ex_forced = 0;
+    if (!exact) h->ex_g_true = 1; // (every other search's accepted gradient is the oracle's own: a memo it leaves behind is a true one)
     h->w_boxed = wolfe_boxed ? 1 : 0; h->w_err = 0; h->tr_ls_cases = 0; h->tr_ndigits = 0;
     h->trace_cap = (int64_t)s->trace_cap; h->trace_x = s->trace_x;
     h->k = 0; h->ls_i = 0; h->status = -1; // ls_solver.rs:74
@@ -316,8 +334,11 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         if (r.obj && r.obj->kind == OBJ_QUADRATIC) s->stats.obj_bytes = h->n_evals * (uint64_t)r.obj->T.rpr * (uint64_t)r.obj->T.n_pad * 8ull;
         if (r.obj && r.obj->kind == OBJ_SPARSE_QUADRATIC) // values + columns, the row offsets, and x, b, g of one evaluation
             s->stats.obj_bytes = h->n_evals * (12ull * (uint64_t)r.obj->sp_nnz + 4ull * ((uint64_t)s->n + 1) + 24ull * (uint64_t)s->n);
+        if (exact && r.obj->kind == OBJ_QUADRATIC) s->stats.obj_bytes += h->ex_passes * (uint64_t)r.obj->T.rpr * (uint64_t)r.obj->T.n_pad * 8ull;
+        if (exact && r.obj->kind == OBJ_SPARSE_QUADRATIC) // a curvature pass: values + columns, the row offsets, d and q -- no b
+            s->stats.obj_bytes += h->ex_passes * (12ull * (uint64_t)r.obj->sp_nnz + 4ull * ((uint64_t)s->n + 1) + 16ull * (uint64_t)s->n);
         stats_add_totals(s); // (no update passes, one rank: total_h_* and total_xchg_* stay)
-        s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u) | (lbfgs ? QN_PATH_LBFGS : 0u) | (cg ? QN_PATH_CG : 0u);
+        s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u) | (lbfgs ? QN_PATH_LBFGS : 0u) | (cg ? QN_PATH_CG : 0u) | (exact ? QN_PATH_EXACT : 0u);
         if (s->method == QN_PROJECTED_NEWTON) { // s_norm() / y_norm() (projected_newton.rs:10-11) through the getters every solver answers
             s->hctl->has_s_norm = h->has_sy; s->hctl->has_y_norm = h->has_sy; s->hctl->s_norm = h->s_norm; s->hctl->y_norm = h->y_norm;
         }
@@ -325,6 +346,14 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
 
     while (!done) {
         int ph = h->phase;
+        if (ph == QN_VP_EXACT_REFRESH) { // ExactQuadratic: the convergence test passed on a recurrence gradient; the objective evaluates x and the loop top runs again
+            h->phase = ph = QN_VP_EVAL_X;
+            HIPCHK(hipMemcpyAsync(s->vctl, h, sizeof(QnVecCtl), hipMemcpyHostToDevice, st));
+        }
+        // ExactQuadratic: does the objective evaluate the point this batch accepts?  exact_step_kernel applies the same rule to the same numbers (an
+        // evaluation at x in this batch clears the count before it does)
+        const int64_t ex_since = ph == QN_VP_EVAL_X ? 0 : h->ex_since;
+        const bool ex_refresh = exact && (h->ex_refresh_every == 1 || (h->ex_refresh_every > 1 && ex_since + 1 >= (int64_t)h->ex_refresh_every));
         if (ph == QN_VP_EVAL_X) { // the oracle at x itself: through xt / gt like every evaluation
             HIPCHK(hipMemcpyAsync(s->V.xt, s->V.x, vb, hipMemcpyDeviceToDevice, st));
             if (host_oracle) {
@@ -367,6 +396,28 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         } else if (ph != QN_VP_TRIAL && ph != QN_VP_REEVAL) {
             return fail(QN_ABNORMAL_TERMINATION, "vector pump: control block in an unexpected phase");
         }
+        if (exact) { // the curvature pass and the step, then the accepted point's (f, g): the objective's launches or the recurrence, never both
+            if (ph != QN_VP_TRIAL && ph != QN_VP_REEVAL) QNCHK(exact_enqueue_step(r));
+            if (ex_refresh || ph == QN_VP_REEVAL) {
+                VEC_LAUNCH(vec_trial_kernel, G);
+                QNCHK(vec_enqueue_eval(r));
+                VEC_LAUNCH(vec_decide_kernel, 1);
+            } else {
+                QNCHK(exact_enqueue_advance(r));
+            }
+            if (lbfgs) QNCHK(lbfgs_enqueue_accept(r));
+            else if (cg) QNCHK(cg_enqueue_accept(r));
+            else VEC_LAUNCH(vec_accept_kernel, G);
+            VEC_LAUNCH(vec_post_kernel, 1);
+            QNCHK(vec_peek(r, false));
+            if (callback && h->k != k_seen) {
+                k_seen = h->k;
+                s->hctl->k = h->k; s->hctl->n_iterations = h->n_iter;
+                callback(callback_user, s);
+            }
+            done = h->phase == QN_VP_DONE;
+            continue;
+        }
         VEC_LAUNCH(vec_trial_kernel, G);
         if (host_oracle) { // a host closure is called only for a point the machine asked for
             QNCHK(vec_peek(r, true));
@@ -398,6 +449,9 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     if (status == QN_ABNORMAL_TERMINATION && h->w_err) // dcsrch's START errors; the loop top ran, x is x_k
         return fail(QN_ABNORMAL_TERMINATION, h->w_err == 1 ? "StrongWolfe: not a descent direction (g.d >= 0 at the start of the search); x is left at x_k"
                                                            : "StrongWolfe: not a descent direction the search can follow (the box leaves stpmax < stpmin); x is left at x_k");
+    if (status == QN_ABNORMAL_TERMINATION && h->ex_err) // the loop top ran, x is x_k
+        return fail(QN_ABNORMAL_TERMINATION, h->ex_err == 1 ? "ExactQuadratic: not a descent direction (g.d >= 0 at the start of the search); x is left at x_k"
+                                                            : "ExactQuadratic: non-positive curvature along the direction (d'Qd is not positive and finite); x is left at x_k");
     if (status < 0 || status == QN_ABNORMAL_TERMINATION) return fail(QN_ABNORMAL_TERMINATION, "vector pump: the machine stopped without a status");
     return status;
 }

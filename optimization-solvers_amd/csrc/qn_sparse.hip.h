@@ -123,3 +123,78 @@ static int spq_enqueue_eval(qn_objective* o, const double* x_dev, double* f_dev,
     a.n = (int)o->n; a.G = o->sp_G; a.n_long = (int)o->sp_n_long;
     return spq_launch(o->ctx->stream, a, o->sp_lanes, f_dev, which);
 }
+
+// ---- the curvature pass: q = Q d and the shares of c = d'Qd (qn_objective_hess_vec; QN_LS_EXACT_QUADRATIC's search, qn_vec_exact.hip.h) ----
+// spq_eval_kernel's sibling with the same structure -- L lanes to a row, the same static cut, whole workgroups for the long rows behind the regular
+// ones in the same launch, the same order of additions inside a row -- and so the same bits for q_i as an evaluation at d with b = 0 gives g_i.
+// It reads d (in QnSpqArgs.x) where the evaluation reads x and reads no b; lane 0 stores q_i (in QnSpqArgs.g) and adds d_i * q_i, two roundings,
+// to the workgroup's share; spq_finish_kernel adds the shares in index order.  Bytes: 12 nnz + 4 (n + 1) + 16 n, 8 n fewer than an evaluation.
+// The evaluation kernel above is not touched: it keeps its code and its operation order.  `ctl` != NULL (the search): predicated on phase
+// QN_VP_EXACT, like every launch of the vector machine; NULL (qn_objective_hess_vec): unconditional.
+template <int L>
+__global__ __launch_bounds__(SPQ_TPB) void spq_curv_kernel(const QnSpqArgs a, const QnVecCtl* ctl) {
+    __shared__ double lds[16];
+    if (ctl && ctl->phase != QN_VP_EXACT) return;
+    double cs[1] = {0.0};
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= a.G) { // one long row, the whole workgroup
+        const int i = a.long_rows[blockIdx.x - a.G];
+        const int j1 = a.row_ptr[i + 1];
+        double acc[1] = {0.0};
+        for (int j = a.row_ptr[i] + tid; j < j1; j += SPQ_TPB) acc[0] = acc[0] + spq_product(a, j);
+        ctl_block_sum<1>(acc, lds);
+        if (tid == 0) {
+            a.g[i] = acc[0];
+            a.part[blockIdx.x] = a.x[i] * acc[0];
+        }
+        return;
+    }
+    constexpr int RPT = SPQ_TPB / L; // rows per trip
+    const int r0 = a.wg_row_start[blockIdx.x], r1 = a.wg_row_start[blockIdx.x + 1];
+    const int sub = tid / L, l = tid % L;
+    for (int base = r0; base < r1; base += RPT) {
+        const int i = base + sub;
+        int j0 = 0, j1 = 0;
+        if (i < r1) { j0 = a.row_ptr[i]; j1 = a.row_ptr[i + 1]; }
+        const bool regular = j1 - j0 <= SPQ_LONG_ROW;
+        double acc = 0.0;
+        if (regular)
+            for (int j = j0 + l; j < j1; j += L) acc = acc + spq_product(a, j);
+#pragma unroll
+        for (int off = L / 2; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
+        if (l == 0 && i < r1 && regular) {
+            a.g[i] = acc;
+            cs[0] = cs[0] + a.x[i] * acc;
+        }
+    }
+    ctl_block_sum<1>(cs, lds);
+    if (tid == 0) a.part[blockIdx.x] = cs[0];
+}
+
+template <int L>
+static void spq_launch_curv_L(hipStream_t st, const QnSpqArgs& a, const QnVecCtl* ctl) {
+    hipLaunchKernelGGL(spq_curv_kernel<L>, dim3(a.G + a.n_long), dim3(SPQ_TPB), 0, st, a, ctl);
+}
+
+// enqueue one curvature pass of a sparse quadratic, with the lanes per row of the evaluation: q = Q d -> q_dev[0 .. n) and the shares (which & 1), then
+// d'Qd -> c_dev by spq_finish_kernel (which & 2; the search adds the shares in exact_step_kernel instead, in the same order)
+static int spq_enqueue_curvature(qn_objective* o, const double* d_dev, double* c_dev, double* q_dev, const QnVecCtl* ctl, int which) {
+    QnSpqArgs a{};
+    a.row_ptr = o->sp_row_ptr; a.col = o->sp_col; a.val = o->sp_val; a.b = nullptr; a.wg_row_start = o->sp_wg_row_start; a.long_rows = o->sp_long_rows;
+    a.x = d_dev; a.g = q_dev; a.part = o->sp_part;
+    a.n = (int)o->n; a.G = o->sp_G; a.n_long = (int)o->sp_n_long;
+    hipStream_t st = o->ctx->stream;
+    if (which & 1) switch (o->sp_lanes) {
+    case 1: spq_launch_curv_L<1>(st, a, ctl); break;
+    case 2: spq_launch_curv_L<2>(st, a, ctl); break;
+    case 4: spq_launch_curv_L<4>(st, a, ctl); break;
+    case 8: spq_launch_curv_L<8>(st, a, ctl); break;
+    case 16: spq_launch_curv_L<16>(st, a, ctl); break;
+    case 32: spq_launch_curv_L<32>(st, a, ctl); break;
+    case 64: spq_launch_curv_L<64>(st, a, ctl); break;
+    default: return fail(QN_ERROR_INPUT_PARAMS, "sparse quadratic: lanes_per_row must be 1, 2, 4, 8, 16, 32 or 64");
+    }
+    if (which & 2) hipLaunchKernelGGL(spq_finish_kernel, dim3(1), dim3(SPQ_TPB), 0, st, a.part, a.G + a.n_long, c_dev);
+    HIPCHK(hipGetLastError());
+    return QN_OK;
+}

@@ -36,8 +36,11 @@ enum QnVecPhase : int32_t {
     QN_VP_ACCEPT = 5, // the step is decided: accept and post kernels
     QN_VP_LS_ONLY = 6, // qn_compute_step_len: g.d for the caller's direction, then the line search alone
     QN_VP_DONE = 7,
-    QN_VP_NSOLVE = 8 // ProjectedNewton / SpectralProjectedNewton: the loop top let the iteration through; the host enqueues z = H^-1 g, then the direction
-                     // (QN_LBFGS: z = H_k g from the last pairs (s, y), qn_lbfgs.hip.h; QN_NONLINEAR_CG: d = beta p - g written directly, qn_cg.hip.h)
+    QN_VP_NSOLVE = 8, // ProjectedNewton / SpectralProjectedNewton: the loop top let the iteration through; the host enqueues z = H^-1 g, then the direction
+                      // (QN_LBFGS: z = H_k g from the last pairs (s, y), qn_lbfgs.hip.h; QN_NONLINEAR_CG: d = beta p - g written directly, qn_cg.hip.h)
+    QN_VP_EXACT = 9,  // QN_LS_EXACT_QUADRATIC: the loop top left g.d < 0; the curvature pass and exact_step_kernel act (qn_vec_exact.hip.h)
+    QN_VP_EXACT_REFRESH = 10 // ... the loop top's test passed on a recurrence gradient: NO kernel acts on this phase (the L-BFGS and CG batches launch
+                             // vec_top_kernel a second time); the host turns it into QN_VP_EVAL_X in front of the next batch
 };
 
 // the second-order variants (newton/projected_newton.rs, newton/spn.rs): the same machine, with z = H^-1 g where the first-order family has g
@@ -94,6 +97,13 @@ struct QnVecCtl {
     double cg_beta;               // of the last accepted iteration: what the next direction is made with
     int64_t cg_since;             // iterations since the last -g direction
     uint64_t cg_restarts;         // betas that ended as exactly 0
+    // ---- QN_LS_EXACT_QUADRATIC (qn_vec_exact.hip.h): the setting; what survives calls like lambda; this search's results; counters of this call ----
+    int32_t ex_refresh_every;     // r: 1 every accepted point is evaluated by the objective, k > 1 every k-th, 0 never (but see ex_g_true)
+    int32_t ex_g_true;            // g is the objective's own gradient at x, not the recurrence's: only then may the loop top declare convergence
+    int64_t ex_since;             // accepted points since the objective last evaluated one
+    int32_t ex_err, ex_adv;       // ex_err: 1 = g.d >= 0, 2 = curvature not positive and finite; ex_adv: this iteration's (f_t, gt) come from exact_advance_kernel
+    double ex_c, ex_t;            // d'Qd and the step of the last search
+    uint64_t ex_passes, ex_refreshes, ex_forced; // curvature passes; accepted points (and forced x) the objective evaluated; the forced ones among them
 };
 
 struct QnVecArgs {
@@ -206,6 +216,10 @@ __device__ __forceinline__ bool vec_loop_top(QnVecCtl* c, double pg) {
         if (c->s_norm < c->tol) { c->status = QN_OK; c->phase = QN_VP_DONE; return true; }
         if (c->y_norm < c->tol) { c->status = QN_OK; c->phase = QN_VP_DONE; return true; }
     }
+    if (pg < c->tol && c->ls_kind == QN_LS_EXACT_QUADRATIC && !c->ex_g_true) { // the test passed on a recurrence gradient: the objective evaluates x, then the loop top again
+        c->have_eval = 0; c->ex_refreshes++; c->ex_forced++; c->phase = QN_VP_EXACT_REFRESH;
+        return true;
+    }
     if (pg < c->tol) { c->status = QN_OK; c->phase = QN_VP_DONE; return true; } // spg.rs:89-92
     c->tr_f = c->f_cur; c->tr_gnorm = pg;
     return false;
@@ -222,7 +236,7 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_top_kernel(const QnVecArgs a) 
     double clip = INFINITY; // StrongWolfe's boxed form: the largest step that stays inside the search's box (wolfe_clip_kernel's shares)
     if (c->ls_kind == QN_LS_STRONG_WOLFE && c->w_boxed && ph != QN_VP_LS_ONLY) clip = wolfe_min_parts(a.part, 6, a.G, lds);
     if (threadIdx.x != 0) return;
-    if (ph == QN_VP_EVAL_X) { c->f_cur = *a.f_dev; c->have_eval = 1; c->n_evals++; }
+    if (ph == QN_VP_EVAL_X) { c->f_cur = *a.f_dev; c->have_eval = 1; c->n_evals++; c->ex_g_true = 1; c->ex_since = 0; } // (ex_*: QN_LS_EXACT_QUADRATIC's, read by no other kind)
     if (ph != QN_VP_LS_ONLY && ph != QN_VP_NSOLVE) {
         c->n_calls++;
         if (vec_spectral(c->method) && !c->has_lambda) { // spg.rs:40-46: the constructor's call; d was formed with lambda = 1
@@ -236,6 +250,12 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_top_kernel(const QnVecArgs a) 
         if (vec_nsolve(c->method)) { c->phase = QN_VP_NSOLVE; return; } // the direction needs the factorisation (QN_LBFGS: the two streams of its memory): enqueued for this phase only
     }
     c->gd = gd;
+    if (c->ls_kind == QN_LS_EXACT_QUADRATIC) { // no first trial of 1: the curvature pass and exact_step_kernel make the step (qn_vec_exact.hip.h)
+        c->ls_i = 0;
+        if (!(gd < 0.0)) { c->ex_err = 1; c->status = QN_ABNORMAL_TERMINATION; c->phase = QN_VP_DONE; return; }
+        c->phase = QN_VP_EXACT;
+        return;
+    }
     if (c->ls_kind == QN_LS_GLL_QUADRATIC) { // gll_quadratic.rs:62-64: append_new_f, then f_max once
         if (c->ring_len == c->m) {
             for (int i = 1; i < c->ring_len; ++i) c->ring[i - 1] = c->ring[i];

@@ -473,6 +473,25 @@ class GLLQuadratic(_LineSearch):
         return self.s._pad
 
 
+class ExactQuadratic(_LineSearch):
+    """The exact step t = -g.d / d'Qd on a device quadratic (Quadratic, SparseQuadratic) for SpectralProjectedGradient, ProjectedGradientDescent,
+    LBFGS / ProjectedLBFGS and NonlinearCG -- with NonlinearCG, linear conjugate gradients.  One product Q d per iteration; no value of f is compared.
+    refresh_every = 1: the objective evaluates every accepted point (two matrix passes per iteration); k > 1: every k-th; 0: never -- (f, g) of the
+    accepted point come from g + t Q d and f + t (g.d + t/2 d'Qd) -- except that convergence is only declared on a gradient the objective evaluated.
+    With a box on the solver the step is capped at 1.  Closures, LogSumExp, other solvers, compute_step_len: ErrorInputParams."""
+
+    def __init__(self, refresh_every=1):
+        self.s = A.LineSearchStruct()
+        A.lib().qn_exact_quadratic_new(C.byref(self.s), int(refresh_every))
+
+    @classmethod
+    def new(cls, refresh_every=1):
+        return cls(refresh_every)
+
+    def refresh_every(self):
+        return self.s._pad
+
+
 class StrongWolfe(_LineSearch, _WolfeConditions):
     """The strong-Wolfe line search of the O(n) solvers (SpectralProjectedGradient, ProjectedGradientDescent, ProjectedNewton, SpectralProjectedNewton,
     LBFGS / ProjectedLBFGS): MINPACK-2 `dcsrch` / `dcstep` (More' and Thuente 1994), one oracle call per trial.  c1 = ftol, c2 = gtol; xtol 0.1,
@@ -550,6 +569,19 @@ class Objective:
         out = np.empty((self.n, self.n), order="F")
         _check(A.lib().qn_objective_hessian(self.h, _dp(x), out.ctypes.data_as(C.POINTER(C.c_double))))
         return out
+
+    def hess_vec(self, v, download=True):
+        """(Q v, v'Qv) of a Quadratic or a SparseQuadratic: one pass over the matrix, no evaluation of f -- the cost of the exact step
+        -g.d / d'Qd along d.  download=False: (None, v'Qv).  LogSumExp: ErrorInputParams (not built)."""
+        if not self.h:
+            raise ErrorInputParams("the objective is closed")
+        v = _f64(v)
+        if v.size != self.n:
+            raise ErrorInputParams(f"v has {v.size} entries, the objective has {self.n}")
+        q = np.empty(self.n) if download else None
+        c = C.c_double()
+        _check(A.lib().qn_objective_hess_vec(self.h, _dp(v), _dp(q) if download else None, C.byref(c)))
+        return q, c.value
 
     def rows(self, row0, nrows):
         out = np.empty((nrows, self.n))
@@ -723,6 +755,13 @@ class _SolverBase:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+    def exact_state(self):
+        """ExactQuadratic, of the last minimize: dict(curvature_passes, refreshes, last_t, last_curvature) -- refreshes: the accepted points (and
+        forced re-evaluations of x) the objective itself evaluated, the first evaluation at x not counted."""
+        passes, refreshes, t, c = C.c_size_t(), C.c_size_t(), C.c_double(), C.c_double()
+        _check(A.lib().qn_solver_exact_state(self.h, C.byref(passes), C.byref(refreshes), C.byref(t), C.byref(c)))
+        return dict(curvature_passes=passes.value, refreshes=refreshes.value, last_t=t.value, last_curvature=c.value)
 
     # ---- LineSearchSolver::minimize (ls_solver.rs:66-111) ----
     def minimize(self, line_search, oracle, max_iter_solver, max_iter_line_search, callback=None):

@@ -20,6 +20,7 @@ pub const QN_LS_BACKTRACKING_B: i32 = 3;
 pub const QN_LS_GLL_QUADRATIC: i32 = 4;
 pub const QN_LS_NO_SEARCH: i32 = 5;
 pub const QN_LS_STRONG_WOLFE: i32 = 6;
+pub const QN_LS_EXACT_QUADRATIC: i32 = 7;
 
 pub const QN_ORACLE_HOST: i32 = 0;
 pub const QN_ORACLE_DEVICE_FN: i32 = 1;
@@ -90,6 +91,7 @@ pub const QN_PATH_RANK1: u32 = 256;
 pub const QN_PATH_PNORM: u32 = 512;
 pub const QN_PATH_LBFGS: u32 = 1024;
 pub const QN_PATH_CG: u32 = 2048;
+pub const QN_PATH_EXACT: u32 = 4096;
 
 #[repr(C)] pub struct qn_context { _p: [u8; 0] }
 #[repr(C)] pub struct qn_solver { _p: [u8; 0] }
@@ -231,6 +233,7 @@ extern "C" {
     pub fn qn_gll_quadratic_with_sigmas(ls: *mut qn_linesearch, sigma1: f64, sigma2: f64);
     pub fn qn_strong_wolfe_new(ls: *mut qn_linesearch, c1: f64, c2: f64);
     pub fn qn_strong_wolfe_with_xtol(ls: *mut qn_linesearch, xtol: f64) -> c_int;
+    pub fn qn_exact_quadratic_new(ls: *mut qn_linesearch, refresh_every: c_int);
 
     // ---- device-resident objectives ----
     pub fn qn_quadratic_create(ctx: *mut qn_context, n: usize, q_rowmajor_host: *const f64, b_host: *const f64, out: *mut *mut qn_objective) -> c_int;
@@ -243,6 +246,7 @@ extern "C" {
     pub fn qn_objective_eval(obj: *mut qn_objective, x_host: *const f64, f: *mut f64, g_host: *mut f64) -> c_int;
     pub fn qn_objective_get_rows(obj: *mut qn_objective, row0: usize, nrows: usize, out_host: *mut f64) -> c_int;
     pub fn qn_objective_hessian(obj: *mut qn_objective, x_host: *const f64, h_colmajor_host: *mut f64) -> c_int;
+    pub fn qn_objective_hess_vec(obj: *mut qn_objective, v_host: *const f64, q_host: *mut f64, vqv: *mut f64) -> c_int;
 
     // ---- solvers ----
     pub fn qn_solver_create(ctx: *mut qn_context, method: c_int, tol: f64, x0_host: *const f64, n: usize, out: *mut *mut qn_solver) -> c_int;
@@ -257,6 +261,7 @@ extern "C" {
     pub fn qn_solver_lbfgs_state(s: *mut qn_solver, m: *mut usize, stored: *mut usize, gamma: *mut f64, resets: *mut usize) -> c_int;
     pub fn qn_solver_set_cg(s: *mut qn_solver, variant: c_int, powell_nu: f64, restart_every: usize) -> c_int;
     pub fn qn_solver_cg_state(s: *mut qn_solver, variant: *mut c_int, beta: *mut f64, restarts: *mut usize, since_restart: *mut usize) -> c_int;
+    pub fn qn_solver_exact_state(s: *mut qn_solver, curvature_passes: *mut usize, refreshes: *mut usize, last_t: *mut f64, last_curvature: *mut f64) -> c_int;
     pub fn qn_solver_reset(s: *mut qn_solver, x0_host: *const f64) -> c_int;
     pub fn qn_minimize(s: *mut qn_solver, ls: *mut qn_linesearch, oracle: *const qn_oracle, max_iter_solver: usize, max_iter_line_search: usize, callback: qn_callback_fn, callback_user: *mut c_void) -> c_int;
     pub fn qn_compute_step_len(ctx: *mut qn_context, ls: *mut qn_linesearch, x_k_host: *const f64, f_k: f64, g_k_host: *const f64, direction_host: *const f64, n: usize, oracle: *const qn_oracle, max_iter: usize, step_out: *mut f64) -> c_int;

@@ -354,6 +354,33 @@ impl CurvatureCondition for GpuStrongWolfe {
     }
 }
 
+/// The exact step `t = -g.d / d'Qd` on a device quadratic (QN_LS_EXACT_QUADRATIC; `DeviceObjective::quadratic` / `sparse_quadratic`, driven by
+/// `minimize_objective`) for `GpuSpectralProjectedGradient`, `GpuProjectedGradientDescent`, `GpuLBFGS` and `GpuNonlinearCG` -- with the last, linear
+/// conjugate gradients.  One product `Q d` per iteration; no value of f is compared.  `refresh_every` = 1: the objective evaluates every accepted
+/// point; k > 1: every k-th; 0: never (the gradient follows `g + t Q d`), except that convergence is only declared on a gradient the objective
+/// evaluated.  A closure has no `Q`: the trait's `compute_step_len` and `minimize` with a closure fail with the library's message.
+#[derive(Clone, Debug)]
+pub struct GpuExactQuadratic {
+    ls: qn_linesearch,
+}
+
+impl GpuExactQuadratic {
+    pub fn new(refresh_every: usize) -> Self {
+        let mut ls = unsafe { std::mem::zeroed::<qn_linesearch>() };
+        unsafe { qn_exact_quadratic_new(&mut ls, refresh_every.min(i32::MAX as usize) as c_int) };
+        GpuExactQuadratic { ls }
+    }
+    pub fn refresh_every(&self) -> usize {
+        self.ls._pad as usize
+    }
+}
+impl Default for GpuExactQuadratic {
+    fn default() -> Self {
+        Self::new(1)
+    }
+}
+impl_line_search!(GpuExactQuadratic);
+
 /// `NoSearch` (nosearch.rs): `compute_step_len` returns 1.0 and never calls the oracle.  On the device it pairs with
 /// `GpuGradientDescent`, `GpuCoordinateDescent`, `GpuPnormDescent` (and Newton): the solvers on the trait's default update hook.
 #[derive(Clone, Debug)]
@@ -473,6 +500,17 @@ impl DeviceObjective {
         let mut m = DMatrix::<Floating>::zeros(self.n, self.n);
         status_to_result(unsafe { qn_objective_hessian(self.h, x.as_ptr(), m.as_mut_ptr()) })?; // column-major, like DMatrix
         Ok(m)
+    }
+    /// (Q v, v'Qv) of a dense or a sparse quadratic: one pass over the matrix and no evaluation of f -- what the exact step
+    /// `-g.d / d'Qd` along d costs, and what a conjugate-gradient loop of the caller's own needs.  Log-sum-exp: `ErrorInputParams`.
+    pub fn hess_vec(&self, v: &DVector<Floating>) -> Result<(DVector<Floating>, Floating), SolverError> {
+        if v.len() != self.n {
+            return Err(SolverError::ErrorInputParams);
+        }
+        let mut c = 0.0;
+        let mut q = DVector::zeros(self.n);
+        status_to_result(unsafe { qn_objective_hess_vec(self.h, v.as_ptr(), q.as_mut_ptr(), &mut c) })?;
+        Ok((q, c))
     }
 }
 
