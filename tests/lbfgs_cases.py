@@ -1,7 +1,8 @@
 """The problems the L-BFGS tests share (tests/test_ref_lbfgs.py licenses the windows, tests/test_gpu_lbfgs.py uses them).  Sizes from the
 vector kernels' grid (G = ceil(n_pad / 2048), at most 1024): n = 2 (the reference's test size), 7 (odd, padding, m > n), 2050 (two workgroups,
 the last one ragged), 2^21 + 2 (the grid-stride loop wraps; m = 3, a separable function).  kappa = 1e2, tol 1e-10, at most 30 iterations, as
-pnewton_cases.  Every restatement run is made once and kept."""
+pnewton_cases.  Every restatement run is made once and kept.  At the end: REPLAY_CASES, the runs tests/lbfgs_replay.py replays direction by
+direction (m up to 32 with the ring wrapping twice, m = 5 at n = 2^21 + 2)."""
 import functools
 
 import numpy as np
@@ -188,3 +189,55 @@ def concave_mixed_fn(x):
 
 
 CONCAVE_X0, CONCAVE_WINDOW = (0.1, 1.0), 5
+
+
+# ---- the replay's cases (tests/lbfgs_replay.py; licensed by tests/test_ref_lbfgs_replay.py, run on the GPU by tests/test_gpu_lbfgs_replay.py) ----
+def _replay_case(name, prob, n, m, ls, iters, **kw):
+    """prob: "quad" / "lse" / "sep" (the problems above), "reject", "concave", "zero" (f = x.x / 2 from (3, 4): g = 0 exactly after one step).
+    box: S.bounds(n, BOX); calls: minimize calls of `iters` iterations each, replayed as one run; wraps: the case exists to wrap the ring
+    (2 (m + 1) committed pairs at least; 66 at m = 32); cpu_n: the size the float64 stand-in runs at where n is too large for it."""
+    c = dict(name=name, prob=prob, n=n, m=m, ls=ls, iters=iters, box=False, memoize=None, unit=False, tol=TOL, calls=1, wraps=False, cpu_n=None)
+    assert set(kw) <= set(c), kw
+    c.update(kw)
+    return c
+
+
+REPLAY_SMALL_M = (1, 2, 3, 4, 5, 8)
+REPLAY_CASES = (
+    # m = 32, full and wrapping: k passes through 1 .. 32 (every count of every Gram group), then the head goes round more than once
+    [_replay_case(f"m32-{p}-{ls}-n{n}", p, n, 32, ls, 72, wraps=True) for p, ls, n in (("quad", "bt", 64), ("quad", "gll", 64), ("sep", "bt", 2050), ("sep", "gll", 2050))]
+    # small memories: a Gram group exactly full (m = 4, 8), the first element of the next (m = 5), m > n (n = 7, m = 8)
+    + [_replay_case(f"wrap-m{m}-n{n}", "sep", n, m, "bt", 2 * (m + 1) + 4, wraps=True) for m in REPLAY_SMALL_M for n in (7, 2050)]
+    # the line searches, each with the loop's own evaluations (memoize = 0) and with the search's last trial reused (memoize = 1)
+    + [_replay_case(f"{ls}-memo{memo}", "lse", 2050, 5, ls, 25, memoize=memo) for ls in ("bt", "gll", "sw") for memo in (0, 1)]
+    # the box: to the iteration cap at n = 2050; at n = 7 for 6 iterations (from the seventh on the projected direction stops descending, both searches
+    # run to their cap of 50 halvings and a step of 1e-13 |d| is below what any bound can tell apart: more than a fifth of 30 iterations would prove
+    # nothing, and which of them do differs between summation orders)
+    + [_replay_case(f"box-{ls}-n{n}", p, n, 5, ls, it, box=True) for ls in ("bt", "btb") for p, n, it in (("quad", 7, 6), ("lse", 2050, WINDOW))]
+    # rejected pairs and the reset
+    + [_replay_case(f"reject-m{m}", "reject", 3, m, "bt", it) for m, it in zip(REJECT_MEMORIES, (6, 7, 9))]  # (to convergence)
+    + [_replay_case("concave-m2", "concave", 2, 2, "bt", CONCAVE_WINDOW), _replay_case("zero-gradient-reset", "zero", 2, 5, "bt", 3, tol=0.0)]
+    + [_replay_case("unit-scaling", "quad", UNIT_N, UNIT_M, "bt", 24, unit=True)]
+    # the grid-stride loop wraps while two Gram groups run (k = 5: groups of 4 + 1)
+    + [_replay_case("grid-wraps-m5", "sep", BIG_N, 5, "bt", 7, cpu_n=4098)]
+    # k and head survive the call boundary
+    + [_replay_case("warm-restart", "sep", 2050, 5, "gll", 20, calls=2)]
+)
+
+
+def replay_problem(case, n=None):
+    """(fn, x0, lb, ub) of a replay case"""
+    n = case["n"] if n is None else n
+    prob = case["prob"]
+    if prob == "sep":
+        fn, x0 = separable_problem(n)
+    elif prob == "reject":
+        fn, x0 = reject_fn, np.array(REJECT_X0)
+    elif prob == "concave":
+        fn, x0 = concave_mixed_fn, np.array(CONCAVE_X0)
+    elif prob == "zero":
+        fn, x0 = (lambda x: (0.5 * float(x @ x), x.copy())), np.array([3.0, 4.0])
+    else:
+        fn, x0 = oracle_fn("lse" if prob == "lse" else "host", n)
+    lb, ub = S.bounds(n, BOX) if case["box"] else free_box(n)
+    return fn, np.asarray(x0, dtype=np.float64), lb, ub

@@ -1,6 +1,6 @@
 """GPU tests of limited-memory BFGS (QN_LBFGS: LBFGS / ProjectedLBFGS; kernels csrc/qn_lbfgs.hip.h) against the restatement tests/ref_lbfgs.py,
 whose direction is the two-loop recursion where the GPU runs the compact form.  Windows and the tolerance (1e-9 max(1, ||x||), the family's)
-are licensed case by case by tests/test_ref_lbfgs.py.
+are licensed case by case by tests/test_ref_lbfgs.py.  Every direction on its own, through whole runs with a full and wrapping memory: tests/test_gpu_lbfgs_replay.py.
 
 The safeguard case.  Every stored pair has s.y > DBL_EPSILON y.y > 0, so H_k is positive definite in exact arithmetic: a concave slice cannot
 make g.z <= 0 -- its pair is simply not stored (checked below: no reset, the iterates follow the restatement).  g.z <= 0 needs rounding,
