@@ -884,7 +884,11 @@ __global__ __launch_bounds__(512) void lse_onepass_kernel(const QnLseArgs a, dou
         for (int w = 1; w < 8; ++w) z = z + red[r & 1][w];
         z = z + a.c[a.rank * a.mrpr + r];
         const double m_new = fmax(m_run, z);
-        const double scale = exp(m_run - m_new), e = exp(z - m_new); // (first row: exp(-inf) = 0)
+        // (first row: exp(-inf) = 0.  A row with c_i = -inf -- masked -- contributes nothing wherever it falls: while the workgroup has no
+        // finite maximum yet m_new is -inf, and exp(-inf - (-inf)) would be NaN; against a finite stand-in both factors are exp(-inf) = 0.
+        // A select, not a branch: for finite data every bit stays what it was)
+        const double m_ref = m_new == -INFINITY ? 0.0 : m_new;
+        const double scale = exp(m_run - m_ref), e = exp(z - m_ref);
         s_run = __builtin_fma(s_run, scale, e);
 #pragma unroll
         for (int k = 0; k < KCH; ++k) {

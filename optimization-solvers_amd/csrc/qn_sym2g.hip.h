@@ -103,7 +103,10 @@ __global__ __launch_bounds__(512) void s2g_onepass_kernel(const QnS2GArgs g) {
         for (int w = 1; w < 8; ++w) z = z + red[r & 1][w];
         z = z + a.c[a.rank * a.mrpr + r];
         const double m_new = fmax(m_run, z);
-        const double scale = exp(m_run - m_new), e = exp(z - m_new); // (first row: exp(-inf) = 0)
+        // (first row: exp(-inf) = 0.  No finite maximum yet -- the workgroup's leading rows masked, c_i = -inf -- and m_new is -inf: against a
+        // finite stand-in both factors are exp(-inf) = 0, where exp(-inf - (-inf)) would be NaN.  A select: finite data keeps every bit)
+        const double m_ref = m_new == -INFINITY ? 0.0 : m_new;
+        const double scale = exp(m_run - m_ref), e = exp(z - m_ref);
         s_run = __builtin_fma(s_run, scale, e);
 #pragma unroll
         for (int k = 0; k < KCH; ++k) {

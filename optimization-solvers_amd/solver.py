@@ -711,7 +711,11 @@ class SparseQuadratic(Objective):
 
 
 class LogSumExp(Objective):
-    """f = log sum_i exp(a_i'x + c_i) + mu/2 ||x||^2 on the device (A is m x n row-major, rows sharded over ranks)."""
+    """f = log sum_i exp(a_i'x + c_i) + mu/2 ||x||^2 on the device (A is m x n row-major, rows sharded over ranks).
+
+    A row with c_i = -inf is masked: it contributes nothing to f and g, wherever it falls in the partition of the rows over ranks and workgroups (the
+    value is that of the problem with the row deleted).  With every row masked f = -inf + mu/2 ||x||^2, which the line searches treat as non-finite.
+    +inf and NaN entries of c and non-finite entries of A are not supported: the result is unspecified."""
 
     def __init__(self, a, c, mu, ctx=None):
         ctx = ctx or default_context()
