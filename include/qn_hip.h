@@ -262,8 +262,17 @@ int qn_objective_hessian(qn_objective* obj, const double* x_host, double* h_colm
  * row and the summation order inside a row of an evaluation, so q has the bits an evaluation at v with b = 0 gives g; 12 nnz + 4 (n + 1) + 16 n
  * bytes, 8 n fewer than an evaluation.  A dense quadratic: the row kernel of an evaluation with the point set to v, then one workgroup that forms
  * v.q.  v'Qv's products and sums round separately, in a fixed order: the same bits for the same v from run to run and from object to object.
- * Log-sum-exp: QN_ERROR_INPUT_PARAMS (not built).  One rank (a row-sharded context: QN_ERROR_INPUT_PARAMS). */
+ * Log-sum-exp: QN_ERROR_INPUT_PARAMS (not built: its Hessian depends on a point, see qn_objective_hess_vec_at).  One rank (a row-sharded
+ * context: QN_ERROR_INPUT_PARAMS). */
 int qn_objective_hess_vec(qn_objective* obj, const double* v_host, double* q_host, double* vqv);
+/* the Hessian-vector product AT A POINT: q = H(x) v into q_host (n entries; NULL: not downloaded) and v'H(x)v into *vhv, without the matrix.
+ * Log-sum-exp: H v = A'(p o (A v)) - gbar (p . (A v)) + mu v with p = softmax(A x + c), gbar = A'p -- the weights at x (two passes of A, the launches
+ * qn_objective_hessian starts with), then ONE stream of A (8 m n bytes, what an evaluation moves; csrc/qn_lse_hv.hip.h) where the dense Hessian costs
+ * O(m n^2) flops and 8 n^2 bytes.  Rows with p_k = 0 (c_k = -inf) add nothing.  Fixed summation orders, no atomics: the same bits for the same
+ * (x, v) from run to run and from object to object.  Built where the one-pass evaluation exists, n_pad <= 16384, and on one rank; otherwise
+ * QN_ERROR_INPUT_PARAMS ("not built").  A dense or a sparse quadratic: x is not read (it may be NULL) and the call IS qn_objective_hess_vec -- the
+ * same launches, the same bits.  (qn_objective_hess_vec itself still answers "not built" on log-sum-exp: it has no point to form p at.) */
+int qn_objective_hess_vec_at(qn_objective* obj, const double* x_host, const double* v_host, double* q_host, double* vhv);
 
 /* ---------------------------------------------------------------------------------------------
  * Solvers: BFGS (bfgs.rs:4-127), DFP (dfp.rs), Broyden (broyden.rs), GradientDescent (gradient_descent.rs:7-82), Newton (newton/mod.rs).
@@ -344,7 +353,32 @@ enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton
         * trace, callbacks, warm restarts (the direction and beta survive calls: two calls of k iterations give the bits of one call of 2 k), one rank.
         * The first trial step of every search is 1, as everywhere in this family.  Profiling mode: t_hpass_ms = cg_dir_kernel, t_hreduce_ms =
         * cg_accept_kernel.  Not built: a box, preconditioning, an initial-step rule, qn_compute_step_len. */
-       QN_NONLINEAR_CG = 13 /* nonlinear conjugate gradient; no counterpart in the reference */ };
+       QN_NONLINEAR_CG = 13 /* nonlinear conjugate gradient; no counterpart in the reference */,
+       /* Truncated Newton: Newton's direction from a few conjugate-gradient steps on H z = g, each costing ONE Hessian-vector product and never a
+        * matrix -- the method between dense Newton (O(m n^2) flops and 8 n^2 bytes per iteration) and the O(n) solvers that keep no curvature.  The
+        * only objective is the device log-sum-exp (qn_logsumexp_create, n_pad <= 16384, one rank), whose product is one stream of A
+        * (csrc/qn_lse_hv.hip.h, qn_objective_hess_vec_at); a closure or a quadratic: QN_ERROR_INPUT_PARAMS (on a quadratic the method is linear
+        * conjugate gradients, which QN_NONLINEAR_CG with QN_LS_EXACT_QUADRATIC already is).  UNBOUNDED ONLY (qn_solver_set_bounds:
+        * QN_ERROR_INPUT_PARAMS).  Line searches: QN_LS_BACKTRACKING and QN_LS_STRONG_WOLFE without a box of its own, first trial t = 1 (the Newton
+        * direction is scaled); every other search: QN_ERROR_INPUT_PARAMS.  It runs on the first-order family's machine (QN_PATH_VECTOR |
+        * QN_PATH_NEWTON_CG, csrc/qn_newton_cg.hip.h): memoize 0 / 1, trace (gnorm = ||g||_inf), callbacks and warm restarts as for QN_LBFGS; the
+        * convergence test is the machine's, ||g||_inf < tol at the loop top.  THE RULES of one direction, in this order:
+        *   1. p = softmax(A x_k + c), gbar = A'p: two passes of A (the loop top's one-pass evaluation keeps no normalised p);
+        *   2. z = 0, r = g, p = g, gg = g.g, rr = gg, j = 0, eta = min(eta_max, sqrt(sqrt(gg)));
+        *   3. q = H p = A'(p o (A p)) - gbar (p . (A p)) + mu p, kappa = p.q;
+        *   4. unless kappa > 0 and finite: neg_curv += 1; if j == 0 then z = g; the loop ends;
+        *   5. alpha = rr / kappa; z += alpha p, r -= alpha q (alpha p and alpha q round first, no FMA); j += 1; rr' = r.r;
+        *   6. sqrt(rr') <= eta sqrt(gg): the loop ends (tolerance); else j == max_inner: it ends (cap);
+        *   7. beta = rr' / rr; p = r + beta p (beta p rounds first); rr = rr'; back to 3;
+        *   8. behind the loop: g.z > 0 and finite, or else z = g and fallbacks += 1 (QN_LBFGS's safeguard; after rule 4 at j = 0 z is g and the
+        *      test is not made); d = -z, written directly (not through P(x - z) - x).
+        * Inner products: product and sum round separately, fixed orders, no atomics: the same bits from run to run.  The host enqueues the inner
+        * steps `chunk` at a time with the rest of the iteration behind them, all predicated on the device's control block, and reads that block
+        * once per batch: host_syncs <= sum_k max(1, ceil(j_k / chunk)) + extra trials + 2; the chunk never changes a bit.  qn_stats: obj_bytes
+        * counts 8 m n_pad per product and 16 m n_pad per weights pass; profiling mode: t_newton_ms = the product launches, t_hpass_ms = the
+        * method's O(n) streams.  Not built: n_pad > 16384, a box, preconditioning, a trust region, row sharding, qn_compute_step_len,
+        * qn_solver_compute_direction (QN_ERROR_INPUT_PARAMS). */
+       QN_NEWTON_CG = 14 /* truncated Newton (Newton-CG) on the log-sum-exp Hessian-vector product; no counterpart in the reference */ };
 #define QN_LBFGS_MAX_M 32
 /* QN_NONLINEAR_CG's variants (qn_solver_set_cg) */
 enum { QN_CG_FR = 0 /* Fletcher-Reeves */, QN_CG_PR_PLUS = 1 /* Polak-Ribiere+ */, QN_CG_HS_PLUS = 2 /* Hestenes-Stiefel+ */, QN_CG_DY = 3 /* Dai-Yuan */,
@@ -382,6 +416,14 @@ int qn_solver_set_cg(qn_solver* s, int variant, double powell_nu, size_t restart
 /* QN_NONLINEAR_CG: the variant, the beta of the last accepted iteration (0 before the first), the betas that ended as exactly 0 and the iterations
  * since the last -g direction, since qn_solver_create / qn_solver_reset.  Any pointer may be NULL.  Other methods: QN_ERROR_INPUT_PARAMS. */
 int qn_solver_cg_state(qn_solver* s, int* variant, double* beta, size_t* restarts, size_t* since_restart);
+/* QN_NEWTON_CG: the forcing term's cap eta_max (0.5 after qn_solver_create; outside (0, 1): QN_ERROR_INPUT_PARAMS), the inner steps of one
+ * direction at the most (0, the default: min(n, 100)) and the inner steps enqueued per batch (8; 0: QN_ERROR_INPUT_PARAMS).  Another method:
+ * QN_ERROR_INPUT_PARAMS. */
+int qn_solver_set_newton_cg(qn_solver* s, double eta_max, size_t max_inner, size_t chunk);
+/* QN_NEWTON_CG, of the last qn_minimize: the inner steps of the last direction, of all directions, the Hessian-vector products (one per inner
+ * step started), the times rule 4 met curvature that was not positive, and the times rule 8 replaced z by g.  Any pointer may be NULL.
+ * Another method: QN_ERROR_INPUT_PARAMS. */
+int qn_solver_newton_cg_state(qn_solver* s, size_t* inner_last, size_t* inner_total, size_t* hv_passes, size_t* neg_curv, size_t* fallbacks);
 /* QN_LS_EXACT_QUADRATIC, of the last qn_minimize: the curvature passes, the accepted points (and forced re-evaluations of x) that the objective
  * evaluated -- the first evaluation at x is not counted --, and the last search's step and curvature d'Qd.  Any pointer may be NULL.  A solver
  * outside the first-order family: QN_ERROR_INPUT_PARAMS. */
@@ -505,6 +547,7 @@ typedef struct {
 #define QN_PATH_LBFGS 1024u    /* QN_LBFGS: the direction from the compact form of L-BFGS, two streams of the memory per iteration (csrc/qn_lbfgs.hip.h); set beside QN_PATH_VECTOR */
 #define QN_PATH_CG 2048u       /* QN_NONLINEAR_CG: the direction d = beta p - g written by cg_dir_kernel, beta from the accept pass's sums (csrc/qn_cg.hip.h); set beside QN_PATH_VECTOR */
 #define QN_PATH_EXACT 4096u    /* QN_LS_EXACT_QUADRATIC: the step from one curvature pass, (f, g) of the accepted point by the recurrence or by the objective (csrc/qn_vec_exact.hip.h); set beside QN_PATH_VECTOR */
+#define QN_PATH_NEWTON_CG 8192u /* QN_NEWTON_CG: the direction from conjugate gradients on H z = g, one log-sum-exp Hessian-vector product per inner step (csrc/qn_newton_cg.hip.h, qn_lse_hv.hip.h); set beside QN_PATH_VECTOR */
 int qn_solver_get_stats(qn_solver* s, qn_stats* out);
 /* profiling != 0: bracket every launch with HIP events on the solver's stream (slower; for roofline reports) */
 int qn_solver_set_profiling(qn_solver* s, int on);

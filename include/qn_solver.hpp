@@ -249,6 +249,7 @@ class Quadratic {
         check(qn_objective_hess_vec(h_, v.data(), q.data(), &c));
         return {std::move(q), c};
     }
+    std::pair<DVector, Floating> hess_vec_at(const DVector&, const DVector& v) const { return hess_vec(v); } // the Hessian is Q wherever x is
 };
 
 // a device-resident objective f = log sum_i exp(a_i'x + c_i) + mu/2 ||x||^2 (A is m x n row-major).  Newton forms its Hessian on the device.
@@ -272,6 +273,13 @@ class LogSumExp {
         DVector h(n_ * n_);
         check(qn_objective_hessian(h_, x.data(), h.data()));
         return h;
+    }
+    std::pair<DVector, Floating> hess_vec_at(const DVector& x, const DVector& v) const { // (H(x) v, v'H(x)v): the weights at x, then one stream of A; no matrix
+        if (x.size() != n_ || v.size() != n_) throw SolverError{SolverError::ErrorInputParams, "x or v does not have the objective's n entries"};
+        DVector q(n_);
+        Floating c = 0;
+        check(qn_objective_hess_vec_at(h_, x.data(), v.data(), q.data(), &c));
+        return {std::move(q), c};
     }
 };
 
@@ -310,6 +318,7 @@ class SparseQuadratic {
         check(qn_objective_hess_vec(h_, v.data(), q.data(), &c));
         return {std::move(q), c};
     }
+    std::pair<DVector, Floating> hess_vec_at(const DVector&, const DVector& v) const { return hess_vec(v); } // the Hessian is Q wherever x is
     size_t nnz() const { size_t v = 0; check(qn_objective_sparse_info(h_, &v, nullptr, nullptr, nullptr)); return v; }
     int lanes_per_row() const { int v = 0; check(qn_objective_sparse_info(h_, nullptr, &v, nullptr, nullptr)); return v; }
     size_t n_long_rows() const { size_t v = 0; check(qn_objective_sparse_info(h_, nullptr, nullptr, &v, nullptr)); return v; }
@@ -356,7 +365,7 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
             const std::optional<Floating> d = decrement_squared();
             return d ? *d * 0.5 < tol() : false;
         }
-        if (METHOD == QN_GRADIENT_DESCENT || METHOD == QN_COORDINATE_DESCENT || METHOD == QN_PNORM_DESCENT || METHOD == QN_NONLINEAR_CG) { // (pnorm_descent.rs:52-59, coordinate_descent.rs:61-68)
+        if (METHOD == QN_GRADIENT_DESCENT || METHOD == QN_COORDINATE_DESCENT || METHOD == QN_PNORM_DESCENT || METHOD == QN_NONLINEAR_CG || METHOD == QN_NEWTON_CG) { // (pnorm_descent.rs:52-59, coordinate_descent.rs:61-68)
             Floating acc = -INFINITY;
             for (Floating v : eval.g()) acc = std::fmax(std::fabs(v), acc);
             return acc < tol();
@@ -607,6 +616,24 @@ class NonlinearCG : public LineSearchSolver<QN_NONLINEAR_CG> {
     Floating beta() const { Floating v = 0; check(qn_solver_cg_state(this->handle(), nullptr, &v, nullptr, nullptr)); return v; }
     size_t restarts() const { size_t v = 0; check(qn_solver_cg_state(this->handle(), nullptr, nullptr, &v, nullptr)); return v; }
     size_t since_restart() const { size_t v = 0; check(qn_solver_cg_state(this->handle(), nullptr, nullptr, nullptr, &v)); return v; }
+};
+
+// Truncated Newton: new(tol, x0).with_inner(eta_max, max_inner, chunk); Newton's direction from a few conjugate-gradient steps on H z = g, each
+// costing one Hessian-vector product of the device LogSumExp objective (one stream of A, never a matrix).  UNBOUNDED ONLY; LogSumExp only
+// (n_pad <= 16384); BackTracking or StrongWolfe, first trial t = 1.  has_converged: ||g||_inf < tol.
+class NewtonCG : public LineSearchSolver<QN_NEWTON_CG> {
+  public:
+    using LineSearchSolver<QN_NEWTON_CG>::LineSearchSolver;
+    static NewtonCG new_(Floating tol, const DVector& x0) { return NewtonCG(tol, x0); }
+    NewtonCG with_inner(Floating eta_max = 0.5, size_t max_inner = 0, size_t chunk = 8) && {
+        check(qn_solver_set_newton_cg(this->handle(), eta_max, max_inner, chunk));
+        return std::move(*this);
+    }
+    size_t inner_last() const { size_t v = 0; check(qn_solver_newton_cg_state(this->handle(), &v, nullptr, nullptr, nullptr, nullptr)); return v; }
+    size_t inner_total() const { size_t v = 0; check(qn_solver_newton_cg_state(this->handle(), nullptr, &v, nullptr, nullptr, nullptr)); return v; }
+    size_t hv_passes() const { size_t v = 0; check(qn_solver_newton_cg_state(this->handle(), nullptr, nullptr, &v, nullptr, nullptr)); return v; }
+    size_t negative_curvature() const { size_t v = 0; check(qn_solver_newton_cg_state(this->handle(), nullptr, nullptr, nullptr, &v, nullptr)); return v; }
+    size_t fallbacks() const { size_t v = 0; check(qn_solver_newton_cg_state(this->handle(), nullptr, nullptr, nullptr, nullptr, &v)); return v; }
 };
 
 } // namespace optimization_solvers

@@ -18,6 +18,7 @@ COORDINATE_DESCENT, PNORM_DESCENT = 10, 11  # steepest_descent/coordinate_descen
 LBFGS = 12  # limited-memory BFGS (ProjectedLBFGS once bounds are set); not the reference's Fortran-backed Lbfgsb
 LBFGS_MAX_M = 32
 NONLINEAR_CG = 13  # nonlinear conjugate gradient (unbounded only); no counterpart in the reference
+NEWTON_CG = 14  # truncated Newton on the log-sum-exp Hessian-vector product (unbounded only); no counterpart in the reference
 CG_FR, CG_PR_PLUS, CG_HS_PLUS, CG_DY, CG_HZ = 0, 1, 2, 3, 4  # qn_solver_set_cg's variants
 UNIQUE_ID_BYTES = 128
 
@@ -73,6 +74,7 @@ PATH_PNORM = 512
 PATH_LBFGS = 1024
 PATH_CG = 2048
 PATH_EXACT = 4096
+PATH_NEWTON_CG = 8192
 
 
 # every symbol include/qn_hip.h declares: (name, restype, argtypes)
@@ -126,6 +128,7 @@ SYMBOLS = [
     ("qn_objective_get_rows", C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, dp]),
     ("qn_objective_hessian", C.c_int, [C.c_void_p, dp, dp]),
     ("qn_objective_hess_vec", C.c_int, [C.c_void_p, dp, dp, dp]),
+    ("qn_objective_hess_vec_at", C.c_int, [C.c_void_p, dp, dp, dp, dp]),
     ("qn_solver_create", C.c_int, [C.c_void_p, C.c_int, C.c_double, dp, C.c_size_t, C.POINTER(C.c_void_p)]),
     ("qn_solver_destroy", None, [C.c_void_p]),
     ("qn_solver_reset", C.c_int, [C.c_void_p, dp]),
@@ -139,6 +142,8 @@ SYMBOLS = [
     ("qn_solver_lbfgs_state", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), dp, C.POINTER(C.c_size_t)]),
     ("qn_solver_set_cg", C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_size_t]),
     ("qn_solver_cg_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int), dp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("qn_solver_set_newton_cg", C.c_int, [C.c_void_p, C.c_double, C.c_size_t, C.c_size_t]),
+    ("qn_solver_newton_cg_state", C.c_int, [C.c_void_p] + [C.POINTER(C.c_size_t)] * 5),
     ("qn_solver_exact_state", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), dp, dp]),
     ("qn_minimize", C.c_int, [C.c_void_p, C.POINTER(LineSearchStruct), C.POINTER(OracleStruct), C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("qn_compute_step_len", C.c_int, [C.c_void_p, C.POINTER(LineSearchStruct), dp, C.c_double, dp, dp, C.c_size_t, C.POINTER(OracleStruct), C.c_size_t,

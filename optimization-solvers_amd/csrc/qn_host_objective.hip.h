@@ -29,6 +29,7 @@ struct qn_objective {
     DevBuf<double> lz, lw, lgpart, lgall, lscal;
     DevBuf<double> lwgms, lwgg, lms; // one-pass evaluation: per-workgroup (m, S), G vectors; gathered per-rank (m, S)
     int lse_G = 0, lse_kch = 0;                                 // its grid and column chunks per thread (0: two-pass evaluation)
+    DevBuf<double> lhv_shares; // qn_lse_hv.hip.h: the combine kernel's shares of v'Hv (256 at the most) and their sum; allocated by the first product
     // sparse quadratic (qn_sparse.hip.h): Q in CSR -- int32 row offsets (n + 1), int32 columns and f64 values (nnz) --, b in `b`
     DevBuf<int> sp_row_ptr, sp_col, sp_wg_row_start, sp_long_rows;
     DevBuf<double> sp_val, sp_part; // sp_part: f's shares, one per workgroup of the evaluation launch

@@ -31,7 +31,7 @@ extern "C" int qn_strong_wolfe_with_xtol(qn_linesearch* ls, double xtol) {
 
 static bool pn_method(int method) { return method == QN_PROJECTED_NEWTON || method == QN_SPECTRAL_PROJECTED_NEWTON; }
 static bool spectral_method(int method) { return method == QN_SPG || method == QN_SPECTRAL_PROJECTED_NEWTON; }
-static bool vec_method(int method) { return method == QN_SPG || method == QN_PROJECTED_GRADIENT || pn_method(method) || method == QN_LBFGS || method == QN_NONLINEAR_CG; }
+static bool vec_method(int method) { return method == QN_SPG || method == QN_PROJECTED_GRADIENT || pn_method(method) || method == QN_LBFGS || method == QN_NONLINEAR_CG || method == QN_NEWTON_CG; }
 struct VecRun;
 static int lbfgs_state_alloc(qn_solver* s); // QN_LBFGS: qn_host_lbfgs.hip.h
 static int lbfgs_enqueue_direction(VecRun& r, bool wolfe_clip);
@@ -40,6 +40,9 @@ static int cg_state_alloc(qn_solver* s); // QN_NONLINEAR_CG: qn_host_cg.hip.h
 static int cg_enqueue_direction(VecRun& r);
 static int cg_enqueue_accept(VecRun& r);
 static int exact_state_alloc(qn_solver* s); // QN_LS_EXACT_QUADRATIC: qn_vec_exact.hip.h
+static int tn_state_alloc(qn_solver* s); // QN_NEWTON_CG: qn_host_newton_cg.hip.h
+static int tn_check(const qn_solver* s, const qn_linesearch* ls, const qn_objective* obj, int ls_only);
+static int tn_enqueue_direction(VecRun& r, bool fresh, uint64_t* weights_passes);
 static int exact_enqueue_step(VecRun& r);
 static int exact_enqueue_advance(VecRun& r);
 static int vec_grid(size_t np) { // a function of n alone: four 16-byte accesses per thread until 4 workgroups per CU are out
@@ -58,6 +61,7 @@ static int vec_state_alloc(qn_solver* s) {
     QNCHK(bounds_alloc(s)); // the box is (-inf, +inf) until qn_solver_set_bounds
     if (s->method == QN_LBFGS) QNCHK(lbfgs_state_alloc(s));
     if (s->method == QN_NONLINEAR_CG) QNCHK(cg_state_alloc(s));
+    if (s->method == QN_NEWTON_CG) QNCHK(tn_state_alloc(s));
     return QN_OK;
 }
 static void vec_state_reset(qn_solver* s) { // back to the state right after ::new: no lambda, an empty f_previous, no memo
@@ -66,6 +70,7 @@ static void vec_state_reset(qn_solver* s) { // back to the state right after ::n
     h->has_lambda = 0; h->lambda = 0.0; h->have_eval = 0; h->ring_len = 0; h->k = 0; h->n_iter = 0;
     h->lb_kmem = 0; h->lb_head = 0; h->lb_gamma = 1.0; h->lb_resets = 0; // QN_LBFGS: an empty memory (lb_m and the scaling switch are settings: kept)
     h->cg_has_p = 0; h->cg_beta = 0.0; h->cg_since = 0; h->cg_restarts = 0; // QN_NONLINEAR_CG: no direction yet (the variant, nu and restart_every are settings: kept)
+    h->tn_state = 0; h->tn_inner_last = 0; h->tn_inner_total = 0; h->tn_hv_passes = 0; h->tn_neg_curv = 0; h->tn_fallbacks = 0; // QN_NEWTON_CG: no inner loop has run (eta_max, max_inner and chunk are settings: kept)
     h->ex_since = 0; h->ex_g_true = 0; // QN_LS_EXACT_QUADRATIC: no accepted point yet (the next evaluation at x is the objective's: have_eval is 0)
     h->has_sy = 0; h->s_norm = 0.0; h->y_norm = 0.0; // (the Cholesky factor of a device quadratic's Hessian is kept: it is keyed on the objective)
 }
@@ -95,6 +100,7 @@ static int vec_compute_direction(qn_solver* s, const double* g_host, double* d_h
     if (pn_method(s->method)) return fail(QN_ERROR_INPUT_PARAMS, "the projected Newton direction needs the oracle's Hessian: use qn_minimize");
     if (s->method == QN_LBFGS) return fail(QN_ERROR_INPUT_PARAMS, "the L-BFGS direction is formed from the device-resident memory: use qn_minimize");
     if (s->method == QN_NONLINEAR_CG) return fail(QN_ERROR_INPUT_PARAMS, "the NonlinearCG direction is formed from the device-resident previous direction: use qn_minimize");
+    if (s->method == QN_NEWTON_CG) return fail(QN_ERROR_INPUT_PARAMS, "the NewtonCG direction is formed by an inner loop on the device objective: use qn_minimize");
     if (s->method == QN_SPG && !s->hvctl->has_lambda) return fail(QN_ERROR_INPUT_PARAMS, "lambda0 needs the oracle: the first qn_minimize evaluates it");
     std::vector<double> x(n), lb(n), ub(n);
     QNCHK(qn_solver_get_x(s, x.data()));
@@ -230,11 +236,12 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     qn_context* c = s->ctx;
     HIPCHK(hipSetDevice(c->device));
     if (c->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient / projected Newton / L-BFGS / nonlinear CG run on one rank");
-    const bool pn = pn_method(s->method), lbfgs = s->method == QN_LBFGS, cg = s->method == QN_NONLINEAR_CG;
+    const bool pn = pn_method(s->method), lbfgs = s->method == QN_LBFGS, cg = s->method == QN_NONLINEAR_CG, tn = s->method == QN_NEWTON_CG;
     VecRun r{s, o, nullptr, {}};
     QNCHK(check_oracle(c, s->n, o, &r.obj));
     if (r.obj && r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_LOGSUMEXP && r.obj->kind != OBJ_SPARSE_QUADRATIC)
         return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
+    if (tn) QNCHK(tn_check(s, ls, r.obj, ls_only)); // unbounded, log-sum-exp, BackTracking or StrongWolfe without a box
     const bool exact = ls->kind == QN_LS_EXACT_QUADRATIC;
     if (exact) { // the exact step -g.d / d'Qd: a device quadratic under the four O(n) methods (qn_vec_exact.hip.h)
         if (pn) return fail(QN_ERROR_INPUT_PARAMS, "ExactQuadratic is not built for the projected Newton pair: it runs under SPG, projected gradient, L-BFGS and NonlinearCG");
@@ -292,6 +299,11 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     if (exact) { h->c1 = 0.0; h->beta = 0.0; h->m = 0; h->memoize = 1; } // (the accepted point's evaluation is always kept: memoize 0 and 1 run the same launches)
     h->ex_refresh_every = exact ? ls->_pad : 0; h->ex_err = 0; h->ex_adv = 0; h->ex_passes = 0; h->ex_refreshes = 0; h->ex_forced = 0;
     if (!exact) h->ex_g_true = 1; // (every other search's accepted gradient is the oracle's own: a memo it leaves behind is a true one)
+    if (tn) { // the inner loop's cap for this call; the counters speak of this call
+        h->tn_cap = h->tn_max_inner > 0 ? h->tn_max_inner : (int32_t)std::min<size_t>(s->n, 100);
+        h->tn_state = 0; h->tn_inner_last = 0; h->tn_inner_total = 0; h->tn_hv_passes = 0; h->tn_neg_curv = 0; h->tn_fallbacks = 0;
+    }
+    uint64_t tn_weights = 0;
     h->w_boxed = wolfe_boxed ? 1 : 0; h->w_err = 0; h->tr_ls_cases = 0; h->tr_ndigits = 0;
     h->trace_cap = (int64_t)s->trace_cap; h->trace_x = s->trace_x;
     h->k = 0; h->ls_i = 0; h->status = -1; // ls_solver.rs:74
@@ -337,8 +349,10 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         if (exact && r.obj->kind == OBJ_QUADRATIC) s->stats.obj_bytes += h->ex_passes * (uint64_t)r.obj->T.rpr * (uint64_t)r.obj->T.n_pad * 8ull;
         if (exact && r.obj->kind == OBJ_SPARSE_QUADRATIC) // a curvature pass: values + columns, the row offsets, d and q -- no b
             s->stats.obj_bytes += h->ex_passes * (12ull * (uint64_t)r.obj->sp_nnz + 4ull * ((uint64_t)s->n + 1) + 16ull * (uint64_t)s->n);
+        if (tn) // a product streams A once (8 m n_pad), the weights at x_k twice (16 m n_pad)
+            s->stats.obj_bytes += ((uint64_t)h->tn_hv_passes + 2ull * tn_weights) * (uint64_t)r.obj->m * (uint64_t)r.obj->T.n_pad * 8ull;
         stats_add_totals(s); // (no update passes, one rank: total_h_* and total_xchg_* stay)
-        s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u) | (lbfgs ? QN_PATH_LBFGS : 0u) | (cg ? QN_PATH_CG : 0u) | (exact ? QN_PATH_EXACT : 0u);
+        s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u) | (lbfgs ? QN_PATH_LBFGS : 0u) | (cg ? QN_PATH_CG : 0u) | (exact ? QN_PATH_EXACT : 0u) | (tn ? QN_PATH_NEWTON_CG : 0u);
         if (s->method == QN_PROJECTED_NEWTON) { // s_norm() / y_norm() (projected_newton.rs:10-11) through the getters every solver answers
             s->hctl->has_s_norm = h->has_sy; s->hctl->has_y_norm = h->has_sy; s->hctl->s_norm = h->s_norm; s->hctl->y_norm = h->y_norm;
         }
@@ -380,6 +394,9 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
             if (lbfgs) QNCHK(lbfgs_enqueue_direction(r, wolfe_boxed));
             // QN_NONLINEAR_CG: the direction written directly, then the loop top's second half -- the same: one peek per batch
             if (cg) QNCHK(cg_enqueue_direction(r));
+            // QN_NEWTON_CG: the weights at x, then a chunk of inner steps, the direction and the loop top's second half -- every one predicated: a
+            // loop that outlasts the chunk leaves the phase at QN_VP_NSOLVE and the rest of this batch returns at once
+            if (tn) QNCHK(tn_enqueue_direction(r, true, &tn_weights));
         } else if (ph == QN_VP_NSOLVE && pn) { // (QN_LBFGS never starts a batch here: no peek falls between its loop top and its direction)
             // the one n x n work matrix (Newton's), for the first iteration that wants a direction: a converged start, a cap of 0 and the
             // constructor's lambda0 batch never come here
@@ -393,6 +410,8 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
             VEC_LAUNCH(vec_dir_kernel, G);
             if (wolfe_boxed) VEC_LAUNCH(wolfe_clip_kernel, G);
             VEC_LAUNCH(vec_top_kernel, 1);
+        } else if (ph == QN_VP_NSOLVE && tn) { // the inner loop was still running when the last batch's chunk was used up: another chunk
+            QNCHK(tn_enqueue_direction(r, false, &tn_weights));
         } else if (ph != QN_VP_TRIAL && ph != QN_VP_REEVAL) {
             return fail(QN_ABNORMAL_TERMINATION, "vector pump: control block in an unexpected phase");
         }

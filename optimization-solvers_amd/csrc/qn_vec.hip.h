@@ -49,7 +49,7 @@ __device__ __forceinline__ bool vec_spectral(int method) { return method == QN_S
 // update_next_iterate calls the oracle at the accepted point, for y (spg.rs:130, spn.rs:135, projected_newton.rs:134)
 __device__ __forceinline__ bool vec_needs_y(int method) { return vec_spectral(method) || method == QN_PROJECTED_NEWTON || method == QN_LBFGS || method == QN_NONLINEAR_CG; }
 // the direction is P(x - z) - x with a z that arrives from outside this file, in phase QN_VP_NSOLVE (QN_NONLINEAR_CG: the direction itself does)
-__device__ __forceinline__ bool vec_nsolve(int method) { return vec_newton(method) || method == QN_LBFGS || method == QN_NONLINEAR_CG; }
+__device__ __forceinline__ bool vec_nsolve(int method) { return vec_newton(method) || method == QN_LBFGS || method == QN_NONLINEAR_CG || method == QN_NEWTON_CG; }
 
 struct QnVecCtl {
     // ---- configuration (host, per call) ----
@@ -104,7 +104,21 @@ struct QnVecCtl {
     int32_t ex_err, ex_adv;       // ex_err: 1 = g.d >= 0, 2 = curvature not positive and finite; ex_adv: this iteration's (f_t, gt) come from exact_advance_kernel
     double ex_c, ex_t;            // d'Qd and the step of the last search
     uint64_t ex_passes, ex_refreshes, ex_forced; // curvature passes; accepted points (and forced x) the objective evaluated; the forced ones among them
+    // ---- QN_NEWTON_CG (qn_newton_cg.hip.h): the settings; the inner loop's scalars; counters of this call ----
+    double tn_eta_max;                // the forcing term's cap, in (0, 1)
+    int32_t tn_max_inner, tn_chunk;   // settings: inner steps at the most (0: min(n, 100)); inner steps enqueued per batch
+    int32_t tn_cap, tn_state;         // max_inner resolved for this call; QN_TN_IDLE / QN_TN_RUNNING / QN_TN_ENDED
+    int32_t tn_j, tn_exit;            // inner steps taken in this outer iteration; why the loop ended (QN_TN_EXIT_*)
+    int32_t tn_zg, tn_use_g;          // rule 4 at j = 0: z = g; the direction is -g (rule 4 at j = 0, or rule 8's safeguard)
+    double tn_gg, tn_sqgg, tn_rr, tn_eta, tn_kappa, tn_alpha, tn_beta, tn_gz;
+    uint64_t tn_inner_last, tn_inner_total, tn_hv_passes, tn_neg_curv, tn_fallbacks;
 };
+#define QN_TN_IDLE 0
+#define QN_TN_RUNNING 1
+#define QN_TN_ENDED 2
+#define QN_TN_EXIT_TOL 1
+#define QN_TN_EXIT_CAP 2
+#define QN_TN_EXIT_NEGCURV 3
 
 struct QnVecArgs {
     double *x, *g, *d, *xt, *gt;

@@ -583,6 +583,22 @@ class Objective:
         _check(A.lib().qn_objective_hess_vec(self.h, _dp(v), _dp(q) if download else None, C.byref(c)))
         return q, c.value
 
+    def hess_vec_at(self, x, v, download=True):
+        """(H(x) v, v'H(x)v) without the matrix.  LogSumExp: the softmax weights at x (two passes of A), then ONE stream of A for
+        A'(p o (A v)) - gbar (p . (A v)) + mu v -- the bytes of one evaluation; n_pad <= 16384, one rank (otherwise ErrorInputParams, "not built").
+        Quadratic / SparseQuadratic: x is not read and the call is `hess_vec(v)`, bit for bit.  download=False: (None, v'Hv)."""
+        if not self.h:
+            raise ErrorInputParams("the objective is closed")
+        x, v = _f64(x), _f64(v)
+        if x.size != self.n:
+            raise ErrorInputParams(f"x has {x.size} entries, the objective has {self.n}")
+        if v.size != self.n:
+            raise ErrorInputParams(f"v has {v.size} entries, the objective has {self.n}")
+        q = np.empty(self.n) if download else None
+        c = C.c_double()
+        _check(A.lib().qn_objective_hess_vec_at(self.h, _dp(x), _dp(v), _dp(q) if download else None, C.byref(c)))
+        return q, c.value
+
     def rows(self, row0, nrows):
         out = np.empty((nrows, self.n))
         _check(A.lib().qn_objective_get_rows(self.h, row0, nrows, _dp(out)))
@@ -1233,6 +1249,52 @@ class NonlinearCG(_SolverBase):
 
     def since_restart(self):
         return self._cg_state()[3]
+
+    def grad_tol(self):
+        return self.tol()
+
+
+class NewtonCG(_SolverBase):
+    """Truncated Newton: `new(tol, x0, eta_max=0.5, max_inner=0, chunk=8)`; Newton's direction from a few conjugate-gradient steps on H z = g,
+    each costing one Hessian-vector product of the device LogSumExp objective (one stream of A, never a matrix).  The inner loop ends once
+    ||r|| <= min(eta_max, sqrt(||g||)) ||g||, after max_inner steps (0: min(n, 100)) or on curvature that is not positive; `chunk` inner steps
+    are enqueued per batch (it never changes a bit).  UNBOUNDED ONLY; objective: LogSumExp with n_pad <= 16384; line searches: BackTracking and
+    StrongWolfe, first trial t = 1.  Closures, quadratics, other searches: ErrorInputParams."""
+    METHOD = A.NEWTON_CG
+
+    def __init__(self, tol, x0, eta_max=0.5, max_inner=0, chunk=8, memoize=None, ctx=None):
+        super().__init__(tol, x0, ctx)
+        self.memoize = memoize
+        if (eta_max, max_inner, chunk) != (0.5, 0, 8):
+            self.set_newton_cg(eta_max, max_inner, chunk)
+
+    @classmethod
+    def new(cls, tol, x0, eta_max=0.5, max_inner=0, chunk=8, memoize=None, ctx=None):
+        return cls(tol, x0, eta_max, max_inner, chunk, memoize, ctx)
+
+    def set_newton_cg(self, eta_max=0.5, max_inner=0, chunk=8):
+        if not 0 <= int(max_inner) < 2 ** 63 or not 0 <= int(chunk) < 2 ** 63:
+            raise ErrorInputParams("NewtonCG: max_inner and chunk must not be negative")
+        _check(A.lib().qn_solver_set_newton_cg(self.h, float(eta_max), int(max_inner), int(chunk)))
+
+    def _tn_state(self):
+        v = [C.c_size_t() for _ in range(5)]
+        _check(A.lib().qn_solver_newton_cg_state(self.h, *[C.byref(x) for x in v]))
+        return [x.value for x in v]
+
+    def inner_iterations(self):
+        """(inner steps of the last direction, of all directions of the last minimize)"""
+        s = self._tn_state()
+        return s[0], s[1]
+
+    def hv_passes(self):
+        return self._tn_state()[2]
+
+    def negative_curvature(self):
+        return self._tn_state()[3]
+
+    def fallbacks(self):
+        return self._tn_state()[4]
 
     def grad_tol(self):
         return self.tol()

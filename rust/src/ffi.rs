@@ -41,6 +41,7 @@ pub const QN_PNORM_DESCENT: c_int = 11;
 pub const QN_LBFGS: c_int = 12;
 pub const QN_LBFGS_MAX_M: usize = 32;
 pub const QN_NONLINEAR_CG: c_int = 13;
+pub const QN_NEWTON_CG: c_int = 14;
 pub const QN_CG_FR: c_int = 0;
 pub const QN_CG_PR_PLUS: c_int = 1;
 pub const QN_CG_HS_PLUS: c_int = 2;
@@ -92,6 +93,7 @@ pub const QN_PATH_PNORM: u32 = 512;
 pub const QN_PATH_LBFGS: u32 = 1024;
 pub const QN_PATH_CG: u32 = 2048;
 pub const QN_PATH_EXACT: u32 = 4096;
+pub const QN_PATH_NEWTON_CG: u32 = 8192;
 
 #[repr(C)] pub struct qn_context { _p: [u8; 0] }
 #[repr(C)] pub struct qn_solver { _p: [u8; 0] }
@@ -247,6 +249,7 @@ extern "C" {
     pub fn qn_objective_get_rows(obj: *mut qn_objective, row0: usize, nrows: usize, out_host: *mut f64) -> c_int;
     pub fn qn_objective_hessian(obj: *mut qn_objective, x_host: *const f64, h_colmajor_host: *mut f64) -> c_int;
     pub fn qn_objective_hess_vec(obj: *mut qn_objective, v_host: *const f64, q_host: *mut f64, vqv: *mut f64) -> c_int;
+    pub fn qn_objective_hess_vec_at(obj: *mut qn_objective, x_host: *const f64, v_host: *const f64, q_host: *mut f64, vhv: *mut f64) -> c_int;
 
     // ---- solvers ----
     pub fn qn_solver_create(ctx: *mut qn_context, method: c_int, tol: f64, x0_host: *const f64, n: usize, out: *mut *mut qn_solver) -> c_int;
@@ -261,6 +264,8 @@ extern "C" {
     pub fn qn_solver_lbfgs_state(s: *mut qn_solver, m: *mut usize, stored: *mut usize, gamma: *mut f64, resets: *mut usize) -> c_int;
     pub fn qn_solver_set_cg(s: *mut qn_solver, variant: c_int, powell_nu: f64, restart_every: usize) -> c_int;
     pub fn qn_solver_cg_state(s: *mut qn_solver, variant: *mut c_int, beta: *mut f64, restarts: *mut usize, since_restart: *mut usize) -> c_int;
+    pub fn qn_solver_set_newton_cg(s: *mut qn_solver, eta_max: f64, max_inner: usize, chunk: usize) -> c_int;
+    pub fn qn_solver_newton_cg_state(s: *mut qn_solver, inner_last: *mut usize, inner_total: *mut usize, hv_passes: *mut usize, neg_curv: *mut usize, fallbacks: *mut usize) -> c_int;
     pub fn qn_solver_exact_state(s: *mut qn_solver, curvature_passes: *mut usize, refreshes: *mut usize, last_t: *mut f64, last_curvature: *mut f64) -> c_int;
     pub fn qn_solver_reset(s: *mut qn_solver, x0_host: *const f64) -> c_int;
     pub fn qn_minimize(s: *mut qn_solver, ls: *mut qn_linesearch, oracle: *const qn_oracle, max_iter_solver: usize, max_iter_line_search: usize, callback: qn_callback_fn, callback_user: *mut c_void) -> c_int;

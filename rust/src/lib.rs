@@ -512,6 +512,18 @@ impl DeviceObjective {
         status_to_result(unsafe { qn_objective_hess_vec(self.h, v.as_ptr(), q.as_mut_ptr(), &mut c) })?;
         Ok((q, c))
     }
+    /// (H(x) v, v'H(x)v) without the matrix.  Log-sum-exp: the softmax weights at x, then one stream of A for
+    /// A'(p o (A v)) - gbar (p . (A v)) + mu v (n_pad <= 16384, one rank; otherwise `ErrorInputParams`).  A quadratic: x is not read,
+    /// the call is `hess_vec(v)` bit for bit.
+    pub fn hess_vec_at(&self, x: &DVector<Floating>, v: &DVector<Floating>) -> Result<(DVector<Floating>, Floating), SolverError> {
+        if x.len() != self.n || v.len() != self.n {
+            return Err(SolverError::ErrorInputParams);
+        }
+        let mut c = 0.0;
+        let mut q = DVector::zeros(self.n);
+        status_to_result(unsafe { qn_objective_hess_vec_at(self.h, x.as_ptr(), v.as_ptr(), q.as_mut_ptr(), &mut c) })?;
+        Ok((q, c))
+    }
 }
 
 impl Drop for DeviceObjective {
@@ -911,6 +923,28 @@ gpu_solver!(
     /// with `minimize_on_device` / `minimize_objective`: the direction lives on the device.
     GpuNonlinearCg, QN_NONLINEAR_CG, false
 );
+
+gpu_solver!(
+    /// Truncated Newton: `new(tol, x0).with_inner(0.5, 0, 8)`; Newton's direction from a few conjugate-gradient steps on H z = g, each costing one
+    /// Hessian-vector product of the device log-sum-exp objective (QN_PATH_NEWTON_CG: one stream of A, never a matrix).  UNBOUNDED ONLY;
+    /// `DeviceObjective::log_sum_exp` only (n_pad <= 16384); `GpuBackTracking` or `GpuStrongWolfe`, first trial t = 1.  Drive it with
+    /// `minimize_objective`: the inner loop lives on the device.
+    GpuNewtonCg, QN_NEWTON_CG, false
+);
+
+impl GpuNewtonCg {
+    /// the forcing term's cap eta_max in (0, 1) (0.5), the inner steps of one direction at the most (0: min(n, 100)), inner steps per batch (8)
+    pub fn with_inner(self, eta_max: Floating, max_inner: usize, chunk: usize) -> Self {
+        assert_eq!(unsafe { qn_solver_set_newton_cg(self.core.h, eta_max, max_inner, chunk) }, QN_OK, "{}", last_error());
+        self
+    }
+    /// (inner steps of the last direction, of all directions, Hessian-vector products, non-positive curvature met, rule-8 fallbacks)
+    pub fn newton_cg_state(&self) -> (usize, usize, usize, usize, usize) {
+        let (mut last, mut total, mut hv, mut neg, mut fb) = (0usize, 0usize, 0usize, 0usize, 0usize);
+        assert_eq!(unsafe { qn_solver_newton_cg_state(self.core.h, &mut last, &mut total, &mut hv, &mut neg, &mut fb) }, QN_OK, "{}", last_error());
+        (last, total, hv, neg, fb)
+    }
+}
 
 /// `qn_solver_set_cg`'s variants
 #[derive(Clone, Copy, Debug, PartialEq, Eq)]
