@@ -226,6 +226,17 @@ int qn_quadratic_create_synthetic(qn_context* ctx, size_t n, uint64_t seed, cons
 /* f = log sum_i exp(a_i'x + c_i) + mu/2 ||x||^2; A is m x n row-major, rows sharded. */
 int qn_logsumexp_create(qn_context* ctx, size_t m, size_t n, const double* a_rowmajor_host, const double* c_host, double mu,
                         qn_objective** out);
+/* Regularised logistic regression: f = sum_i w_i log(1 + exp(-y_i a_i'x)) + mu/2 ||x||^2, g = -A'(y o w o s) + mu x with s_i = 1 / (1 + exp(y_i a_i'x)),
+ * H = A' diag(d) A + mu I with d_i = w_i s_i (1 - s_i).  A is m x n row-major and dense; y_i is EXACTLY -1 or +1 (0 / 1 labels: pass 2 y - 1; any other
+ * value: QN_ERROR_INPUT_PARAMS -- a 0 never masks a row silently); w_host holds m sample weights >= 0, finite (a negative or non-finite one:
+ * QN_ERROR_INPUT_PARAMS), NULL: all ones.  A row with w_i = 0 is masked: it adds nothing to f, g or H, the value is that of the problem with the row
+ * deleted.  mu: any finite value.  n_pad <= 16384 and one rank (otherwise QN_ERROR_INPUT_PARAMS, "not built").  One evaluation is TWO launches
+ * (csrc/qn_logistic.hip.h): one stream of A, 8 m n_pad bytes, stable for every finite margin; no atomics, the same bits for the same x from run to run
+ * and from object to object.  It runs under QN_SPG, QN_PROJECTED_GRADIENT, QN_LBFGS, QN_NONLINEAR_CG and QN_NEWTON_CG with every line search those take
+ * but ExactQuadratic; every other method: QN_ERROR_INPUT_PARAMS.  qn_objective_hess_vec_at gives H(x) v (one weights pass of A at x, one product pass);
+ * qn_objective_hess_vec, qn_objective_hessian and qn_objective_sparse_info on it: QN_ERROR_INPUT_PARAMS; qn_objective_get_rows returns rows of A. */
+int qn_logistic_create(qn_context* ctx, size_t m, size_t n, const double* a_rowmajor_host, const double* y_host, const double* w_host, double mu,
+                       qn_objective** out);
 /* f = 1/2 x'Qx - b'x, g = Qx - b with a SPARSE Q: n x n in CSR, both triangles of a symmetric matrix -- the device objective that exists at the
  * sizes the O(n) solvers are for.  It runs under QN_SPG, QN_PROJECTED_GRADIENT and QN_LBFGS with every line search those take; every other method:
  * QN_ERROR_INPUT_PARAMS ("unsupported objective"; the projected Newton pair: "Hessian not available in the oracle").  One rank (a row-sharded
@@ -356,7 +367,8 @@ enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton
        QN_NONLINEAR_CG = 13 /* nonlinear conjugate gradient; no counterpart in the reference */,
        /* Truncated Newton: Newton's direction from a few conjugate-gradient steps on H z = g, each costing ONE Hessian-vector product and never a
         * matrix -- the method between dense Newton (O(m n^2) flops and 8 n^2 bytes per iteration) and the O(n) solvers that keep no curvature.  The
-        * only objective is the device log-sum-exp (qn_logsumexp_create, n_pad <= 16384, one rank), whose product is one stream of A
+        * objectives are the device log-sum-exp (qn_logsumexp_create) and the device logistic regression (qn_logistic_create: H = A' diag(d) A +
+        * mu I, the same kernels with a zero gbar, ONE pass of A for the weights d at x_k), n_pad <= 16384, one rank; the product is one stream of A
         * (csrc/qn_lse_hv.hip.h, qn_objective_hess_vec_at); a closure or a quadratic: QN_ERROR_INPUT_PARAMS (on a quadratic the method is linear
         * conjugate gradients, which QN_NONLINEAR_CG with QN_LS_EXACT_QUADRATIC already is).  UNBOUNDED ONLY (qn_solver_set_bounds:
         * QN_ERROR_INPUT_PARAMS).  Line searches: QN_LS_BACKTRACKING and QN_LS_STRONG_WOLFE without a box of its own, first trial t = 1 (the Newton

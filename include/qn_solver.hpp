@@ -283,6 +283,37 @@ class LogSumExp {
     }
 };
 
+// a device-resident regularised logistic regression, f = sum_i w_i log(1 + exp(-y_i a_i'x)) + mu/2 ||x||^2 (A is m x n row-major and dense).  y_i is
+// exactly -1 or +1 (0 / 1 labels: pass 2 y - 1; anything else throws ErrorInputParams); weights are >= 0, a row with weight 0 is masked (the value is
+// that of the problem with the row deleted); an empty `weights`: all ones.  It runs under SpectralProjectedGradient, ProjectedGradientDescent, LBFGS /
+// ProjectedLBFGS, NonlinearCG and NewtonCG.
+class Logistic {
+    qn_objective* h_ = nullptr;
+    size_t n_;
+  public:
+    Logistic(const DVector& a_rowmajor, const DVector& y, size_t n, Floating mu, const DVector& weights = DVector(), Context& ctx = Context::default_context()) : n_(n) {
+        if (!weights.empty() && weights.size() != y.size()) throw SolverError{SolverError::ErrorInputParams, "weights does not have one entry per row"};
+        if (a_rowmajor.size() != y.size() * n) throw SolverError{SolverError::ErrorInputParams, "a_rowmajor is not y.size() x n"};
+        check(qn_logistic_create(ctx.handle(), y.size(), n, a_rowmajor.data(), y.data(), weights.empty() ? nullptr : weights.data(), mu, &h_));
+    }
+    Logistic(const Logistic&) = delete;
+    ~Logistic() { qn_objective_destroy(h_); }
+    qn_objective* handle() const { return h_; }
+    FuncEvalMultivariate operator()(const DVector& x) const {
+        DVector g(n_);
+        Floating f = 0;
+        check(qn_objective_eval(h_, x.data(), &f, g.data()));
+        return FuncEvalMultivariate(f, std::move(g));
+    }
+    std::pair<DVector, Floating> hess_vec_at(const DVector& x, const DVector& v) const { // (H(x) v, v'H(x)v), H = A' diag(d) A + mu I: d at x (one pass of A), then one stream of A; no matrix
+        if (x.size() != n_ || v.size() != n_) throw SolverError{SolverError::ErrorInputParams, "x or v does not have the objective's n entries"};
+        DVector q(n_);
+        Floating c = 0;
+        check(qn_objective_hess_vec_at(h_, x.data(), v.data(), q.data(), &c));
+        return {std::move(q), c};
+    }
+};
+
 // a device-resident objective f = 1/2 x'Qx - b'x with a sparse Q in CSR (both triangles of a symmetric matrix): the large objective of the O(n)
 // solvers -- SpectralProjectedGradient, ProjectedGradientDescent, LBFGS / ProjectedLBFGS.  Index: int32_t or int64_t, for both arrays.
 class SparseQuadratic {
@@ -379,7 +410,7 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
     // minimize with a host closure: the reference's exact oracle-call sequence (ls_solver.rs:66-111)
     // (a device objective is callable too: without the constraint a non-const Quadratic / LogSumExp lvalue would bind here, as a host closure)
     template <class LS, class Oracle, class = std::enable_if_t<!std::is_same_v<std::decay_t<Oracle>, Quadratic> && !std::is_same_v<std::decay_t<Oracle>, LogSumExp> &&
-                                                               !std::is_same_v<std::decay_t<Oracle>, SparseQuadratic>>>
+                                                               !std::is_same_v<std::decay_t<Oracle>, SparseQuadratic> && !std::is_same_v<std::decay_t<Oracle>, Logistic>>>
     Result minimize(LS& line_search, Oracle&& oracle, size_t max_iter_solver, size_t max_iter_line_search,
                     std::optional<std::function<void(const Self&)>> callback = std::nullopt) {
         using OracleT = std::remove_reference_t<Oracle>;
@@ -424,6 +455,14 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
     }
     template <class LS>
     Result minimize(LS& line_search, const LogSumExp& objective, size_t max_iter_solver, size_t max_iter_line_search) {
+        qn_oracle o{};
+        o.kind = QN_ORACLE_OBJECTIVE;
+        o.memoize = 1;
+        o.objective = objective.handle();
+        return make_result(qn_minimize(h_, &line_search.ffi(), &o, max_iter_solver, max_iter_line_search, nullptr, nullptr));
+    }
+    template <class LS>
+    Result minimize(LS& line_search, const Logistic& objective, size_t max_iter_solver, size_t max_iter_line_search) {
         qn_oracle o{};
         o.kind = QN_ORACLE_OBJECTIVE;
         o.memoize = 1;
@@ -619,7 +658,7 @@ class NonlinearCG : public LineSearchSolver<QN_NONLINEAR_CG> {
 };
 
 // Truncated Newton: new(tol, x0).with_inner(eta_max, max_inner, chunk); Newton's direction from a few conjugate-gradient steps on H z = g, each
-// costing one Hessian-vector product of the device LogSumExp objective (one stream of A, never a matrix).  UNBOUNDED ONLY; LogSumExp only
+// costing one Hessian-vector product of the device LogSumExp or Logistic objective (one stream of A, never a matrix).  UNBOUNDED ONLY; those two only
 // (n_pad <= 16384); BackTracking or StrongWolfe, first trial t = 1.  has_converged: ||g||_inf < tol.
 class NewtonCG : public LineSearchSolver<QN_NEWTON_CG> {
   public:

@@ -79,6 +79,9 @@ extern "C" const char* qn_status_string(int status) {
 #include "qn_vec_exact.hip.h"
 // the log-sum-exp Hessian-vector product (q = H v in one stream of A) and qn_objective_hess_vec_at: behind every existing kernel
 #include "qn_lse_hv.hip.h"
+// the logistic objective (two launches per evaluation; its Hessian-vector product is the log-sum-exp one's kernels): behind every existing kernel
+#include "qn_logistic.hip.h"
+#include "qn_host_logistic.hip.h"
 // truncated Newton (NewtonCG) on the first-order family's machine: conjugate gradients on H z = g with that product, behind every existing kernel
 #include "qn_newton_cg.hip.h"
 #include "qn_host_newton_cg.hip.h"

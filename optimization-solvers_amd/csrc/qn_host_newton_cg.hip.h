@@ -42,9 +42,9 @@ extern "C" int qn_solver_newton_cg_state(qn_solver* s, size_t* inner_last, size_
 // what qn_minimize checks before a NewtonCG run starts (the pump's other checks have passed)
 static int tn_check(const qn_solver* s, const qn_linesearch* ls, const qn_objective* obj, int ls_only) {
     if (ls_only) return fail(QN_ERROR_INPUT_PARAMS, "compute_step_len runs on a first-order solver");
-    if (!obj) return fail(QN_ERROR_INPUT_PARAMS, "NewtonCG needs a device LogSumExp objective: a closure has no Hessian-vector product");
-    if (obj->kind != OBJ_LOGSUMEXP)
-        return fail(QN_ERROR_INPUT_PARAMS, "NewtonCG runs on a LogSumExp objective only: on a quadratic the method is linear conjugate gradients, which NonlinearCG with ExactQuadratic already is");
+    if (!obj) return fail(QN_ERROR_INPUT_PARAMS, "NewtonCG needs a device LogSumExp or Logistic objective: a closure has no Hessian-vector product");
+    if (obj->kind != OBJ_LOGSUMEXP && obj->kind != OBJ_LOGISTIC)
+        return fail(QN_ERROR_INPUT_PARAMS, "NewtonCG runs on a LogSumExp or Logistic objective only: on a quadratic the method is linear conjugate gradients, which NonlinearCG with ExactQuadratic already is");
     if (ls->kind != QN_LS_BACKTRACKING && ls->kind != QN_LS_STRONG_WOLFE)
         return fail(QN_ERROR_INPUT_PARAMS, "NewtonCG takes BackTracking or StrongWolfe (GLLQuadratic, BackTrackingB, ExactQuadratic, NoSearch and More-Thuente: out of scope)");
     if (ls->lower_bound_host || ls->upper_bound_host) return fail(QN_ERROR_INPUT_PARAMS, "NewtonCG is unbounded only: StrongWolfe's box is out of scope");
@@ -61,7 +61,8 @@ static int tn_enqueue_direction(VecRun& r, bool fresh, uint64_t* weights_passes)
     const size_t np = s->T.n_pad;
     QnTnArgs t{};
     t.r = s->tn_block; t.p = s->tn_block + np; t.q = s->tn_block + 2 * np; t.gbar = s->tn_block + 3 * np; t.tpart = s->tn_block + 4 * np;
-    t.gbar_src = r.obj->lgall; t.kcount = (int)((np + 63) / 64);
+    const bool logit = r.obj->kind == OBJ_LOGISTIC; // H = A' diag(d) A + mu I: the product's kernels with pw = d and zeros where gbar goes
+    t.gbar_src = logit ? r.obj->lzero : r.obj->lgall; t.kcount = (int)((np + 63) / 64);
     QNCHK(r.obj->lhv_shares.ensure(257, st));
     t.kshares = r.obj->lhv_shares;
     const dim3 one(1), wide(r.a.G), tpb(QN_VEC_TPB);
@@ -69,8 +70,9 @@ static int tn_enqueue_direction(VecRun& r, bool fresh, uint64_t* weights_passes)
         {
             ProfScope ps(s, KC_EREDUCE); // (a class of its own: two passes of A, twice an evaluation's time, would upset t_eval_ms's floor rule)
             QnLseArgs la{};
-            QNCHK(lse_enqueue_weights(r.obj, s->V.x, la));
-            s->stats.launches += 4;
+            if (logit) QNCHK(logit_enqueue_weights(r.obj, s->V.x)); // ONE pass of A: d is known row by row the moment the margin is
+            else QNCHK(lse_enqueue_weights(r.obj, s->V.x, la));
+            s->stats.launches += logit ? 2 : 4;
             ++*weights_passes;
         }
         { ProfScope ps(s, KC_HPASS); hipLaunchKernelGGL(tn_init_kernel, wide, tpb, 0, st, r.a, t); }

@@ -1,9 +1,9 @@
-// qn_host_objective.hip.h -- host side, part 3 of 7: device-resident objectives (the synthetic quadratic, the log-sum-exp, the sparse quadratic) and their evaluation launches.
+// qn_host_objective.hip.h -- host side, part 3 of 7: device-resident objectives (the synthetic quadratic, the log-sum-exp, the sparse quadratic, the logistic) and their evaluation launches.
 #pragma once
 // ------------------------------------------------------------------------------------------------
 // objectives
 // ------------------------------------------------------------------------------------------------
-enum { OBJ_QUADRATIC = 1, OBJ_LOGSUMEXP = 2, OBJ_SPARSE_QUADRATIC = 3 };
+enum { OBJ_QUADRATIC = 1, OBJ_LOGSUMEXP = 2, OBJ_SPARSE_QUADRATIC = 3, OBJ_LOGISTIC = 4 };
 // the sparse quadratic's launch shape (qn_sparse.hip.h; the creation below cuts the rows for it)
 #define SPQ_MAXG 2048     // regular workgroups at the most: 8 per CU on 256 CUs
 #define SPQ_LONG_ROW 2048 // rows longer than this get a workgroup of their own
@@ -36,6 +36,10 @@ struct qn_objective {
     size_t sp_nnz = 0, sp_n_long = 0;
     int sp_G = 0;                    // regular workgroups; the long rows' run behind them in the same launch
     int sp_lanes = 1, sp_lanes_auto = 1; // lanes per row in use, and the choice made at creation from the mean row length
+    // logistic (qn_logistic.hip.h): A rows in Q, yw = y o w in b (m_pad); lse_G / lse_kch, lwgms (the workgroups' F) and lwgg as the one-pass log-sum-exp's;
+    // d at the accepted point in lw, the margins of one launch in lz, f and g of a weights pass in lscal and lgpart
+    DevBuf<double> lw_trial; // d of the evaluations that are not a weights pass (trial points): written, never read
+    DevBuf<double> lzero;    // n_pad zeros: what the Hessian-vector product's kernels take where log-sum-exp has gbar
 };
 
 static int objective_base(qn_context* ctx, size_t n, const double* b_host, qn_objective** out) {
@@ -130,6 +134,10 @@ extern "C" int qn_logsumexp_create(qn_context* ctx, size_t m, size_t n, const do
 
 // ---- the sparse quadratic: f = 1/2 x'Qx - b'x with Q in CSR (kernels and the evaluation's launches: qn_sparse.hip.h) ----
 static int spq_enqueue_eval(qn_objective* o, const double* x_dev, double* f_dev, double* g_dev, int which = 3);
+// ---- the logistic objective (kernels: qn_logistic.hip.h; creation and these launches: qn_host_logistic.hip.h) ----
+static int logit_enqueue_eval(qn_objective* o, const double* x_dev, double* f_dev, double* g_dev, double* d_dev, int which = 3);
+static int logit_enqueue_weights(qn_objective* o, const double* x_dev);
+static int logit_hess_vec_at(qn_objective* o, const double* x_host, const double* v_host, double* q_host, double* vhv);
 
 template <class I>
 static int spq_validate(size_t n, size_t nnz, const I* rp, const I* ci) {
@@ -249,6 +257,7 @@ extern "C" int qn_sparse_quadratic_set_lanes_per_row(qn_objective* o, int lanes)
 }
 
 extern "C" int qn_objective_sparse_info(qn_objective* o, size_t* nnz, int* lanes_per_row, size_t* n_long_rows, int* symmetric) {
+    if (o && o->kind == OBJ_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "a logistic objective is not a sparse quadratic (its A is dense)");
     if (!o || o->kind != OBJ_SPARSE_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "not a sparse quadratic");
     if (nnz) *nnz = o->sp_nnz;
     if (lanes_per_row) *lanes_per_row = o->sp_lanes;
@@ -367,7 +376,8 @@ extern "C" void qn_objective_destroy(qn_objective* o) {
 
 extern "C" int qn_objective_get_rows(qn_objective* o, size_t row0, size_t nrows, double* out_host) {
     if (o->kind == OBJ_SPARSE_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "a sparse quadratic has no dense rows / Hessian");
-    const bool lse = o->kind == OBJ_LOGSUMEXP;
+    if (o->kind != OBJ_QUADRATIC && o->kind != OBJ_LOGSUMEXP && o->kind != OBJ_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
+    const bool lse = o->kind == OBJ_LOGSUMEXP || o->kind == OBJ_LOGISTIC; // (rows of the dense A)
     const size_t lo = lse ? (size_t)o->TA.row_off : (size_t)o->T.row_off;
     const size_t hi = lse ? std::min(o->m, lo + (size_t)o->TA.rpr) : std::min(o->n, lo + (size_t)o->T.rpr);
     if (row0 < lo || row0 + nrows > hi) return fail(QN_ERROR_INPUT_PARAMS, "rows outside this rank's shard");
@@ -420,12 +430,13 @@ extern "C" int qn_objective_eval(qn_objective* o, const double* x_host, double* 
         HIPCHK(hipStreamSynchronize(c->stream));
         return QN_OK;
     }
-    if (o->kind == OBJ_SPARSE_QUADRATIC) {
+    if (o->kind == OBJ_SPARSE_QUADRATIC || o->kind == OBJ_LOGISTIC) {
         QNCHK(o->ex.ensure(2 * np, c->stream));
         QNCHK(o->eg.ensure(np, c->stream));
         QNCHK(o->ef.ensure(2, c->stream));
         HIPCHK(hipMemcpyAsync(o->ex, x_host, o->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        QNCHK(spq_enqueue_eval(o, o->ex, o->ef, o->eg));
+        if (o->kind == OBJ_LOGISTIC) QNCHK(logit_enqueue_eval(o, o->ex, o->ef, o->eg, o->lw_trial)); // (lw keeps the last weights pass's d)
+        else QNCHK(spq_enqueue_eval(o, o->ex, o->ef, o->eg));
         HIPCHK(hipMemcpyAsync(f, o->ef, sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(g_host, o->eg, o->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -456,6 +467,7 @@ extern "C" int qn_objective_eval(qn_objective* o, const double* x_host, double* 
 extern "C" int qn_objective_hessian(qn_objective* o, const double* x_host, double* h_colmajor_host) {
     if (!o || !x_host) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
     if (o->kind == OBJ_SPARSE_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "a sparse quadratic has no dense rows / Hessian");
+    if (o->kind == OBJ_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "the dense Hessian of a logistic objective is not built: hess_vec_at gives H(x) v in one stream of A");
     qn_context* c = o->ctx;
     if (c->world != 1) return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hessian is single-GPU");
     HIPCHK(hipSetDevice(c->device));

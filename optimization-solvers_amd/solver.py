@@ -572,7 +572,7 @@ class Objective:
 
     def hess_vec(self, v, download=True):
         """(Q v, v'Qv) of a Quadratic or a SparseQuadratic: one pass over the matrix, no evaluation of f -- the cost of the exact step
-        -g.d / d'Qd along d.  download=False: (None, v'Qv).  LogSumExp: ErrorInputParams (not built)."""
+        -g.d / d'Qd along d.  download=False: (None, v'Qv).  LogSumExp, Logistic: ErrorInputParams (their Hessian depends on x: hess_vec_at)."""
         if not self.h:
             raise ErrorInputParams("the objective is closed")
         v = _f64(v)
@@ -586,6 +586,7 @@ class Objective:
     def hess_vec_at(self, x, v, download=True):
         """(H(x) v, v'H(x)v) without the matrix.  LogSumExp: the softmax weights at x (two passes of A), then ONE stream of A for
         A'(p o (A v)) - gbar (p . (A v)) + mu v -- the bytes of one evaluation; n_pad <= 16384, one rank (otherwise ErrorInputParams, "not built").
+        Logistic: the weights d_i = w_i s_i (1 - s_i) at x (ONE pass of A), then one stream of A for A'(d o (A v)) + mu v.
         Quadratic / SparseQuadratic: x is not read and the call is `hess_vec(v)`, bit for bit.  download=False: (None, v'Hv)."""
         if not self.h:
             raise ErrorInputParams("the objective is closed")
@@ -739,6 +740,33 @@ class LogSumExp(Objective):
         m, n = a.shape
         h = C.c_void_p()
         _check(A.lib().qn_logsumexp_create(ctx.h, m, n, _dp(a), _dp(c), float(mu), C.byref(h)))
+        super().__init__(ctx, h, n)
+        self.m = m
+
+
+class Logistic(Objective):
+    """Regularised logistic regression on the device: f = sum_i w_i log(1 + exp(-y_i a_i'x)) + mu/2 ||x||^2 with a dense A (m x n row-major),
+    g = -A'(y o w o s) + mu x, s_i = 1 / (1 + exp(y_i a_i'x)), H = A' diag(d) A + mu I with d_i = w_i s_i (1 - s_i).
+
+    LABELS: every y_i is exactly -1 or +1.  Callers with 0 / 1 labels pass 2 y - 1; any other value is ErrorInputParams -- a 0 never masks a row silently.
+    MASKING: `weights` are sample weights >= 0 (default: ones; negative or non-finite: ErrorInputParams).  A row with weight 0 is masked: it adds nothing
+    to f, g or H wherever it falls in the cut of the rows over workgroups -- the value is that of the problem with the row deleted.
+
+    One evaluation is two launches and one stream of A, stable for every finite margin.  It runs under SpectralProjectedGradient,
+    ProjectedGradientDescent, LBFGS / ProjectedLBFGS, NonlinearCG and NewtonCG; `hess_vec_at(x, v)` gives (H(x) v, v'H(x)v) in one weights pass and one
+    product pass of A.  n_pad <= 16384, one rank (otherwise ErrorInputParams, "not built"); `hessian` and `hess_vec`: ErrorInputParams."""
+
+    def __init__(self, a, y, mu, weights=None, ctx=None):
+        ctx = ctx or default_context()
+        a, y = _f64(a), _f64(y)
+        if a.ndim != 2 or y.ndim != 1 or a.shape[0] != y.size:
+            raise ErrorInputParams("a must be m x n and y must have m entries")
+        m, n = a.shape
+        w = None if weights is None else _f64(weights)
+        if w is not None and (w.ndim != 1 or w.size != m):
+            raise ErrorInputParams(f"weights has {w.size} entries, a has {m} rows")
+        h = C.c_void_p()
+        _check(A.lib().qn_logistic_create(ctx.h, m, n, _dp(a), _dp(y), _dp(w) if w is not None else None, float(mu), C.byref(h)))
         super().__init__(ctx, h, n)
         self.m = m
 
@@ -1256,9 +1284,9 @@ class NonlinearCG(_SolverBase):
 
 class NewtonCG(_SolverBase):
     """Truncated Newton: `new(tol, x0, eta_max=0.5, max_inner=0, chunk=8)`; Newton's direction from a few conjugate-gradient steps on H z = g,
-    each costing one Hessian-vector product of the device LogSumExp objective (one stream of A, never a matrix).  The inner loop ends once
+    each costing one Hessian-vector product of the device LogSumExp or Logistic objective (one stream of A, never a matrix).  The inner loop ends once
     ||r|| <= min(eta_max, sqrt(||g||)) ||g||, after max_inner steps (0: min(n, 100)) or on curvature that is not positive; `chunk` inner steps
-    are enqueued per batch (it never changes a bit).  UNBOUNDED ONLY; objective: LogSumExp with n_pad <= 16384; line searches: BackTracking and
+    are enqueued per batch (it never changes a bit).  UNBOUNDED ONLY; objective: LogSumExp or Logistic with n_pad <= 16384; line searches: BackTracking and
     StrongWolfe, first trial t = 1.  Closures, quadratics, other searches: ErrorInputParams."""
     METHOD = A.NEWTON_CG
 

@@ -455,6 +455,18 @@ impl DeviceObjective {
         status_to_result(unsafe { qn_logsumexp_create(default_context(), m, n, a_rowmajor.as_ptr(), c.as_ptr(), mu, &mut h) })?;
         Ok(DeviceObjective { h, n })
     }
+    /// f = sum_i w_i log(1 + exp(-y_i a_i'x)) + mu/2 ||x||^2; `a_rowmajor` is m x n, `y` holds -1 / +1 exactly (0 / 1 labels: pass 2 y - 1),
+    /// `weights` (>= 0, a 0 masks its row) defaults to ones.  The objective of GpuLBFGS, GpuNonlinearCG, the spectral family and GpuNewtonCG.
+    pub fn logistic(a_rowmajor: &[Floating], y: &DVector<Floating>, weights: Option<&DVector<Floating>>, n: usize, mu: Floating) -> Result<Self, SolverError> {
+        let m = y.len();
+        if a_rowmajor.len() != m * n || weights.map_or(false, |w| w.len() != m) {
+            return Err(SolverError::ErrorInputParams);
+        }
+        let mut h = std::ptr::null_mut();
+        let w = weights.map_or(std::ptr::null(), |w| w.as_ptr());
+        status_to_result(unsafe { qn_logistic_create(default_context(), m, n, a_rowmajor.as_ptr(), y.as_ptr(), w, mu, &mut h) })?;
+        Ok(DeviceObjective { h, n })
+    }
     /// f = 1/2 x'Qx - b'x with a sparse Q in CSR (both triangles of a symmetric matrix; `indptr` has n + 1 entries, the columns of a row
     /// increase strictly): the large objective of the O(n) solvers (GpuSpectralProjectedGradient, GpuProjectedGradientDescent, GpuLBFGS).
     pub fn sparse_quadratic(indptr: &[i64], indices: &[i64], data: &[Floating], b: &DVector<Floating>) -> Result<Self, SolverError> {
