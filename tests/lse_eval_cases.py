@@ -43,7 +43,8 @@ search; qn_st_after_next sets s_norm, y_norm from the accepted point's staged su
 prologue copies the iterate only then).  Record k holds f = f(x_k), gnorm = ||g(x_k)||, t = t_k, s_norm = ||x_{k+1} - x_k||,
 y_norm = ||g(x_{k+1}) - g(x_k)||, updated = whether the pair (s_k, y_k) went into H, and the recorded iterate xs[k] is x_{k+1}; x_0 is the caller's.
 
-THE REPLAY checks every recorded iteration on its own, from the run's own iterates, so nothing accumulates:
+THE REPLAY (tests/qn_replay.py, shared with the quadratic objective's tests/quad_replay_cases.py; `replay` below hands it this objective's truth)
+checks every recorded iteration on its own, from the run's own iterates, so nothing accumulates:
   f       |trace.f - f(x_k)| <= bf(x_k);
   gnorm   against ||g(x_k)||: ||bg(x_k)||_2 for the gradient, (n + 2) eps relative for the sum of squares and eps for the square root;
   s_norm  against ||fl(x_{k+1} - x_k)||_2 (the library forms s with one subtraction: exact apart from the sum);
@@ -69,16 +70,12 @@ import math
 
 import numpy as np
 
-LD = np.longdouble
-EPS = 2.0 ** -52
-INF = float("inf")
+import qn_replay
+from qn_replay import (CAP, CHECKS, EPS, INF, LD, REPLAY, SKIP_SHARE, Y_CAP, InverseHessian, Report, Tally, _ratio, check, coefficients,  # noqa: F401
+                       point_ratios)
+
 MU = 0.1
-REPLAY = 3
 REPLAY_N = 4224      # above: iteration 0 only
-CAP = 1e-6           # discrimination of the direction check
-Y_CAP = 1e-3         # ... and of y_norm
-SKIP_SHARE = 0.10
-CHECKS = ("f", "gnorm", "s_norm", "y_norm", "dir")
 
 
 # ---- the grid ----
@@ -235,21 +232,6 @@ class Truth:
         self.bgnorm = float(np.linalg.norm(self.bg))
 
 
-def _ratio(err, bound):
-    """max |err| / bound; anything not finite, or an error against a zero bound, is inf"""
-    err, bound = np.abs(np.asarray(err, dtype=np.float64)), np.asarray(bound, dtype=np.float64)
-    if not (np.all(np.isfinite(err)) and np.all(np.isfinite(bound))):
-        return INF
-    with np.errstate(all="ignore"):
-        r = np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err == 0, 0.0, INF))
-    return float(np.max(r))
-
-
-def point_ratios(tr, f, g):
-    """(ratio of f, ratio of g entry by entry) of an evaluation against the truth `tr` at the same point"""
-    return _ratio(float(abs(LD(f) - tr.f)), tr.bf), _ratio((np.asarray(g, dtype=np.float64).astype(LD) - tr.g).astype(np.float64), tr.bg)
-
-
 # ---- float64 restatements of the evaluation, three orders ----
 def eval_plain(a, c, x, mu=MU):
     z = a @ x + c
@@ -320,12 +302,6 @@ def eval_fold(a, c, x, world=1, mu=MU, select=True, fault=None):
 
 
 # ---- a float64 DFP / BFGS run on a restatement (backtracking, the rank-2 form) ----
-def coefficients(method, ys, yu):
-    if method == "bfgs":
-        return (1 + yu / ys) / ys, -1 / ys, 0 * ys
-    return 1 / ys, 0 * ys, -1 / yu
-
-
 def reference_run(ev, x0, method, iters, perturb=None, tol=1e-10):
     """-> (trace records, xs) in the library's layout.  ev(x) -> (f, g).  perturb = (k, j, rel): entry j of the gradient the direction of iteration k
     is formed from is off by rel |g_j| (a wrong entry of the staged g+ that no sum sees)."""
@@ -364,111 +340,9 @@ def reference_run(ev, x0, method, iters, perturb=None, tol=1e-10):
     return tr, np.array(xs)
 
 
-# ---- the replay ----
-class Report:
-    def __init__(self, name):
-        self.name = name
-        self.rows = []  # (iteration, check, ratio, asserted)
-
-    def add(self, k, check, ratio, asserted=True):
-        self.rows.append((k, check, float(ratio), bool(asserted)))
-
-    @property
-    def worst(self):
-        return max([r for _, _, r, a in self.rows if a] + [0.0])
-
-    def worst_of(self, check):
-        return max([r for _, c, r, a in self.rows if a and c == check] + [0.0])
-
-    @property
-    def skipped(self):
-        return [(k, c) for k, c, _, a in self.rows if not a]
-
-    def line(self):
-        per = ", ".join(f"{c} {self.worst_of(c):.2e}" for c in CHECKS)
-        return f"lse replay {self.name}: worst {self.worst:.3e} ({per}), checks {len(self.rows)}, skipped {self.skipped}"
-
-
-def _inv_bound(v, dv):
-    """bound on |1 / v^ - 1 / v| for |v^ - v| <= dv, plus the division's own rounding"""
-    v = abs(float(v))
-    if not dv < v:
-        return INF
-    return dv / (v * (v - dv)) + 2.0 * EPS / (v - dv)
-
-
-def _outer(u, v):
-    return np.multiply.outer(u, v)
-
-
-class InverseHessian:
-    """H_k in longdouble from the replayed pairs, kept as H = I + sum coef p q' (products H v cost O(n k) longdouble operations; |H_k| is formed
-    densely in float64, where it only scales a bound), Habs >= |H_k| and DH >= |H_k of the device - H_k| in float64 (module docstring, `dir`)"""
-
-    def __init__(self, n, method):
-        self.n, self.method, self.terms, self.habs, self.dh, self.bounded = n, method, [], None, None, True
-
-    def times(self, v):
-        out = v.astype(LD)
-        for coef, p, q in self.terms:
-            out = out + (coef * np.dot(q, v)) * p
-        return out
-
-    def dense_abs(self):
-        h = np.eye(self.n)
-        for coef, p, q in self.terms:
-            h += float(coef) * _outer(p.astype(np.float64), q.astype(np.float64))
-        return np.abs(h) * (1.0 + 1e-9)
-
-    def apply(self, g, gabs, bg):
-        """(H g, |H| bg + (n + 4) eps |H| |g| + DH (|g| + bg))"""
-        if not self.terms:
-            return g, bg + (self.n + 4) * EPS * gabs
-        if not self.bounded:
-            return self.times(g), np.full(self.n, INF)
-        habs = self.dense_abs()
-        return self.times(g), (habs @ bg + (self.n + 4) * EPS * (habs @ gabs) + self.dh @ (gabs + bg)) * (1.0 + 1e-9)
-
-    def update(self, s, y, dy):
-        n = self.n
-        if self.habs is None:
-            self.habs, self.dh = np.eye(n), np.zeros((n, n))
-        sl, sa, ya = s.astype(LD), np.abs(s), np.abs(y).astype(np.float64)
-        u = self.times(y)
-        ua = np.abs(u).astype(np.float64)
-        ys, yu = np.dot(sl, y), np.dot(y, u)
-        css, csu, cuu = coefficients(self.method, ys, yu)
-        self.terms += [(css, sl, sl), (csu, sl, u), (csu, u, sl)] if self.method == "bfgs" else [(css, sl, sl), (cuu, u, u)]
-        du = self.dh @ ya + self.habs @ dy + (n + 4) * EPS * (self.habs @ (ya + dy))
-        ub = ua + du
-        dys = float(sa @ dy) + (n + 2) * EPS * float(sa @ (ya + dy))
-        dyu = float(dy @ ub) + float(ya @ du) + (n + 2) * EPS * float((ya + dy) @ ub)
-        ys, yu = float(ys), float(yu)
-        d_iys = _inv_bound(ys, dys)
-        if self.method == "bfgs":
-            acss, acsu, acuu = abs(float(css)), abs(float(csu)), 0.0
-            dcsu, dcuu = d_iys, 0.0
-            dcss = d_iys + ((abs(yu) + dyu) / (abs(ys) - dys) ** 2 - abs(yu) / ys ** 2 if dys < abs(ys) else INF) + 4.0 * EPS * acss
-        else:
-            acss, acsu, acuu = abs(float(css)), 0.0, abs(float(cuu))
-            dcss, dcsu, dcuu = d_iys, 0.0, _inv_bound(yu, dyu)
-        if not all(math.isfinite(v) for v in (dcss, dcsu, dcuu)) or not np.all(np.isfinite(du)):
-            self.bounded = False
-            return
-        if self.method == "bfgs":
-            self.habs += acss * _outer(sa, sa) + acsu * (_outer(sa, ua) + _outer(ua, sa))
-            dt = dcss * _outer(sa, sa) + acsu * (_outer(sa, du) + _outer(du, sa)) + dcsu * (_outer(sa, ub) + _outer(ub, sa))
-        else:
-            self.habs += acss * _outer(sa, sa) + acuu * _outer(ua, ua)
-            dt = dcss * _outer(sa, sa) + acuu * (_outer(ua, du) + _outer(du, ua) + _outer(du, du)) + dcuu * _outer(ub, ub)
-        self.dh = (self.dh + dt + 8.0 * EPS * self.habs) * (1.0 + 1e-9)
-
-
+# ---- the replay (tests/qn_replay.py: Report, InverseHessian, Tally, check) with this objective's truth ----
 def replay(name, a, c, x0, method, tr, xs, mu=MU, truth_cache=None):
     """Report of a run: tr the trace records (f, gnorm, t, s_norm, y_norm, updated), xs[k] = x_{k+1}"""
-    m, n = a.shape
-    rep = Report(name)
-    assert len(tr) >= 1 and len(xs) >= len(tr), (len(tr), len(xs))
     cache = truth_cache if truth_cache is not None else {}
 
     def truth(x):
@@ -477,58 +351,4 @@ def replay(name, a, c, x0, method, tr, xs, mu=MU, truth_cache=None):
             cache[key] = Truth(a, c, x, mu)
         return cache[key]
 
-    iters = min(len(tr), REPLAY if n <= REPLAY_N else 1)
-    hk = InverseHessian(n, method)
-    x = np.array(x0, dtype=np.float64)
-    for k in range(iters):
-        r, xn = tr[k], np.array(xs[k], dtype=np.float64)
-        if not np.all(np.isfinite(xn)):
-            rep.add(k, "dir", INF)
-            break
-        t0, t1 = truth(x), truth(xn)
-        rep.add(k, "f", _ratio(float(abs(LD(r["f"]) - t0.f)), t0.bf))
-        gsum = ((n + 2) * EPS + EPS) * (t0.gnorm + t0.bgnorm)
-        rep.add(k, "gnorm", _ratio(r["gnorm"] - t0.gnorm, t0.bgnorm + gsum))
-        s = xn - x
-        sl = s.astype(LD)
-        snorm = float(np.sqrt(np.dot(sl, sl)))
-        rep.add(k, "s_norm", _ratio(r["s_norm"] - snorm, ((n + 2) * EPS + EPS) * snorm))
-        y = t1.g - t0.g
-        dy = t1.bg + t0.bg + EPS * np.abs(y).astype(np.float64)
-        ynorm, dynorm = float(np.sqrt(np.dot(y, y))), float(np.linalg.norm(dy))
-        rep.add(k, "y_norm", _ratio(r["y_norm"] - ynorm, dynorm + ((n + 3) * EPS) * (ynorm + dynorm)), asserted=dynorm <= Y_CAP * ynorm)
-        t = float(r["t"])
-        gabs = np.abs(t0.g).astype(np.float64)
-        hg, spread = hk.apply(t0.g, gabs, t0.bg)
-        hw = (t * spread + 2.0 * EPS * (np.abs(x) + np.abs(xn))) * (1.0 + 1e-9)
-        smax = float(np.max(np.abs(s)))
-        bounded = bool(np.all(np.isfinite(hw)))
-        ratio = _ratio((sl + LD(t) * hg).astype(np.float64), hw) if bounded else INF
-        rep.add(k, "dir", ratio, asserted=bounded and float(np.max(hw)) <= CAP * smax)
-        if k + 1 < iters and r["updated"]:
-            hk.update(s, y, dy)
-        x = xn
-    return rep
-
-
-class Tally:
-    """the skip cap over everything that was replayed"""
-
-    def __init__(self):
-        self.triples = self.skipped = 0
-
-    def add(self, rep):
-        """per run: iteration 0 asserted, not every direction check skipped"""
-        self.triples += len(rep.rows)
-        self.skipped += len(rep.skipped)
-        assert not [kc for kc in rep.skipped if kc[0] == 0], (rep.name, "iteration 0 must be asserted", rep.skipped)
-        assert any(a for _, c, _, a in rep.rows if c == "dir"), (rep.name, "every direction check skipped")
-
-    def check(self):
-        assert self.skipped <= SKIP_SHARE * self.triples, (self.skipped, self.triples)
-
-
-def check(rep):
-    print(rep.line())
-    bad = [(k, c, r) for k, c, r, a in rep.rows if a and not r <= 1.0]
-    assert not bad, (rep.name, bad[:6])
+    return qn_replay.replay(name, truth, x0, method, tr, xs, iters=REPLAY if a.shape[1] <= REPLAY_N else 1, kind="lse")
