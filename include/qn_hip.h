@@ -237,6 +237,27 @@ int qn_logsumexp_create(qn_context* ctx, size_t m, size_t n, const double* a_row
  * qn_objective_hess_vec, qn_objective_hessian and qn_objective_sparse_info on it: QN_ERROR_INPUT_PARAMS; qn_objective_get_rows returns rows of A. */
 int qn_logistic_create(qn_context* ctx, size_t m, size_t n, const double* a_rowmajor_host, const double* y_host, const double* w_host, double mu,
                        qn_objective** out);
+/* The same objective with a SPARSE A: m x n in CSR (the columns of a row strictly increasing), with NO limit on n_pad -- logistic regression at the
+ * sizes the O(n) solvers are for.  Labels, weights, masking and mu follow qn_logistic_create's rules exactly.  The two index arrays travel as
+ * untyped pointers: `index_bytes` = 4 (int32) or 8 (int64) holds for BOTH; on the device they are int32.  At creation the host also builds the CSR
+ * of A' (a counting sort) and BOTH copies go to the device: 24 bytes per nonzero.  The transpose product g = A'coef walks the rows of A' with the
+ * kernel that walks the rows of A, so it uses no float atomic and every sum has one fixed order: the same bits for the same x from run to run and
+ * from object to object.  Each copy has its own static cut over workgroups, its own long rows (more than 2048 entries: a whole workgroup each --
+ * a dense column of A, such as an intercept column, is a long row of A') and its own lanes per row.  Validated on the host in O(nnz), each failure
+ * QN_ERROR_INPUT_PARAMS: a null pointer, m == 0 or n == 0, index_bytes not 4 or 8, m or n > 2^30, nnz > 2^31 - 1, row_ptr[0] != 0,
+ * row_ptr[m] != nnz, a decreasing row_ptr, a column outside [0, n), unsorted or duplicate columns, a bad label or weight, a non-finite mu, a
+ * row-sharded context ("single-GPU").  A failed creation leaks nothing and leaves *out alone.  One evaluation is THREE launches
+ * (csrc/qn_sparse_logistic.hip.h): the row pass (margins, coefficients, d, the loss), the column pass (g, ||x||^2) and a one-workgroup finish.
+ * It runs under QN_SPG, QN_PROJECTED_GRADIENT, QN_LBFGS, QN_NONLINEAR_CG and QN_NEWTON_CG with every line search those take but ExactQuadratic;
+ * every other method, qn_objective_hessian, qn_objective_hess_vec, qn_objective_get_rows and qn_objective_sparse_info: QN_ERROR_INPUT_PARAMS.
+ * qn_objective_eval works on it; qn_objective_hess_vec_at gives H(x) v = A'(d o (A v)) + mu v (a weights pass at x, the product's two passes, a fold). */
+int qn_sparse_logistic_create(qn_context* ctx, size_t m, size_t n, size_t nnz, const void* row_ptr_host, const void* col_idx_host, int index_bytes,
+                              const double* values_host, const double* y_host, const double* w_host, double mu, qn_objective** out);
+/* Lanes that share one row in the row pass (over A) and in the column pass (over A'): each 1, 2, 4, 8, 16, 32 or 64, or 0 for the choice made at
+ * creation from that copy's mean row length.  Another value may change the bits of f, g and H v; the results stay inside the same error bounds. */
+int qn_sparse_logistic_set_lanes(qn_objective* objective, int lanes_rows, int lanes_cols);
+/* nnz, the lanes per row in use for each pass, and the long rows of A and of A' (any pointer may be NULL).  Another objective: QN_ERROR_INPUT_PARAMS. */
+int qn_sparse_logistic_info(qn_objective* objective, size_t* nnz, int* lanes_rows, int* lanes_cols, size_t* n_long_rows, size_t* n_long_cols);
 /* f = 1/2 x'Qx - b'x, g = Qx - b with a SPARSE Q: n x n in CSR, both triangles of a symmetric matrix -- the device objective that exists at the
  * sizes the O(n) solvers are for.  It runs under QN_SPG, QN_PROJECTED_GRADIENT and QN_LBFGS with every line search those take; every other method:
  * QN_ERROR_INPUT_PARAMS ("unsupported objective"; the projected Newton pair: "Hessian not available in the oracle").  One rank (a row-sharded
@@ -369,7 +390,8 @@ enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton
         * matrix -- the method between dense Newton (O(m n^2) flops and 8 n^2 bytes per iteration) and the O(n) solvers that keep no curvature.  The
         * objectives are the device log-sum-exp (qn_logsumexp_create) and the device logistic regression (qn_logistic_create: H = A' diag(d) A +
         * mu I, the same kernels with a zero gbar, ONE pass of A for the weights d at x_k), n_pad <= 16384, one rank; the product is one stream of A
-        * (csrc/qn_lse_hv.hip.h, qn_objective_hess_vec_at); a closure or a quadratic: QN_ERROR_INPUT_PARAMS (on a quadratic the method is linear
+        * (csrc/qn_lse_hv.hip.h, qn_objective_hess_vec_at).  The sparse logistic regression (qn_sparse_logistic_create) has no limit on n_pad: its
+        * product is a row pass over A, a column pass over A' and a one-workgroup fold (csrc/qn_sparse_logistic.hip.h).  A closure or a quadratic: QN_ERROR_INPUT_PARAMS (on a quadratic the method is linear
         * conjugate gradients, which QN_NONLINEAR_CG with QN_LS_EXACT_QUADRATIC already is).  UNBOUNDED ONLY (qn_solver_set_bounds:
         * QN_ERROR_INPUT_PARAMS).  Line searches: QN_LS_BACKTRACKING and QN_LS_STRONG_WOLFE without a box of its own, first trial t = 1 (the Newton
         * direction is scaled); every other search: QN_ERROR_INPUT_PARAMS.  It runs on the first-order family's machine (QN_PATH_VECTOR |

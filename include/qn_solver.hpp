@@ -314,6 +314,47 @@ class Logistic {
     }
 };
 
+// the same logistic regression with a sparse A in CSR (m x n, the columns of a row strictly increasing) and no limit on n: the device keeps A and A'
+// (24 bytes per nonzero), so the transpose product uses no atomics and every sum has one fixed order.  Labels, weights and mu as Logistic's.  It runs
+// under SpectralProjectedGradient, ProjectedGradientDescent, LBFGS / ProjectedLBFGS, NonlinearCG and NewtonCG.  Index: int32_t or int64_t, for both arrays.
+class SparseLogistic {
+    qn_objective* h_ = nullptr;
+    size_t n_;
+  public:
+    template <class Index>
+    SparseLogistic(const std::vector<Index>& indptr, const std::vector<Index>& indices, const DVector& data, const DVector& y, size_t n, Floating mu,
+                   const DVector& weights = DVector(), Context& ctx = Context::default_context()) : n_(n) {
+        static_assert(sizeof(Index) == 4 || sizeof(Index) == 8, "CSR indices are 32 or 64 bits wide");
+        if (indptr.size() != y.size() + 1 || indices.size() != data.size()) throw SolverError{SolverError::ErrorInputParams, "CSR arrays do not match"};
+        if (!weights.empty() && weights.size() != y.size()) throw SolverError{SolverError::ErrorInputParams, "weights does not have one entry per row"};
+        const Index no_index = 0; // (an empty matrix: the library takes a null pointer for a missing argument)
+        const Floating no_value = 0;
+        check(qn_sparse_logistic_create(ctx.handle(), y.size(), n, data.size(), indptr.data(), indices.empty() ? &no_index : indices.data(), (int)sizeof(Index),
+                                        data.empty() ? &no_value : data.data(), y.data(), weights.empty() ? nullptr : weights.data(), mu, &h_));
+    }
+    SparseLogistic(const SparseLogistic&) = delete;
+    ~SparseLogistic() { qn_objective_destroy(h_); }
+    qn_objective* handle() const { return h_; }
+    FuncEvalMultivariate operator()(const DVector& x) const {
+        if (x.size() != n_) throw SolverError{SolverError::ErrorInputParams, "x does not have the objective's n entries"};
+        DVector g(n_);
+        Floating f = 0;
+        check(qn_objective_eval(h_, x.data(), &f, g.data()));
+        return FuncEvalMultivariate(f, std::move(g));
+    }
+    std::pair<DVector, Floating> hess_vec_at(const DVector& x, const DVector& v) const { // (H(x) v, v'H(x)v), H = A' diag(d) A + mu I: a weights pass at x, then the product's two passes; no matrix
+        if (x.size() != n_ || v.size() != n_) throw SolverError{SolverError::ErrorInputParams, "x or v does not have the objective's n entries"};
+        DVector q(n_);
+        Floating c = 0;
+        check(qn_objective_hess_vec_at(h_, x.data(), v.data(), q.data(), &c));
+        return {std::move(q), c};
+    }
+    void set_lanes(int rows, int cols) { check(qn_sparse_logistic_set_lanes(h_, rows, cols)); } // 0: automatic
+    size_t nnz() const { size_t v = 0; check(qn_sparse_logistic_info(h_, &v, nullptr, nullptr, nullptr, nullptr)); return v; }
+    size_t n_long_rows() const { size_t v = 0; check(qn_sparse_logistic_info(h_, nullptr, nullptr, nullptr, &v, nullptr)); return v; }
+    size_t n_long_cols() const { size_t v = 0; check(qn_sparse_logistic_info(h_, nullptr, nullptr, nullptr, nullptr, &v)); return v; }
+};
+
 // a device-resident objective f = 1/2 x'Qx - b'x with a sparse Q in CSR (both triangles of a symmetric matrix): the large objective of the O(n)
 // solvers -- SpectralProjectedGradient, ProjectedGradientDescent, LBFGS / ProjectedLBFGS.  Index: int32_t or int64_t, for both arrays.
 class SparseQuadratic {
@@ -410,7 +451,8 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
     // minimize with a host closure: the reference's exact oracle-call sequence (ls_solver.rs:66-111)
     // (a device objective is callable too: without the constraint a non-const Quadratic / LogSumExp lvalue would bind here, as a host closure)
     template <class LS, class Oracle, class = std::enable_if_t<!std::is_same_v<std::decay_t<Oracle>, Quadratic> && !std::is_same_v<std::decay_t<Oracle>, LogSumExp> &&
-                                                               !std::is_same_v<std::decay_t<Oracle>, SparseQuadratic> && !std::is_same_v<std::decay_t<Oracle>, Logistic>>>
+                                                               !std::is_same_v<std::decay_t<Oracle>, SparseQuadratic> && !std::is_same_v<std::decay_t<Oracle>, Logistic> &&
+                                                               !std::is_same_v<std::decay_t<Oracle>, SparseLogistic>>>
     Result minimize(LS& line_search, Oracle&& oracle, size_t max_iter_solver, size_t max_iter_line_search,
                     std::optional<std::function<void(const Self&)>> callback = std::nullopt) {
         using OracleT = std::remove_reference_t<Oracle>;
@@ -463,6 +505,14 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
     }
     template <class LS>
     Result minimize(LS& line_search, const Logistic& objective, size_t max_iter_solver, size_t max_iter_line_search) {
+        qn_oracle o{};
+        o.kind = QN_ORACLE_OBJECTIVE;
+        o.memoize = 1;
+        o.objective = objective.handle();
+        return make_result(qn_minimize(h_, &line_search.ffi(), &o, max_iter_solver, max_iter_line_search, nullptr, nullptr));
+    }
+    template <class LS>
+    Result minimize(LS& line_search, const SparseLogistic& objective, size_t max_iter_solver, size_t max_iter_line_search) {
         qn_oracle o{};
         o.kind = QN_ORACLE_OBJECTIVE;
         o.memoize = 1;

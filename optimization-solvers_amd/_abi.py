@@ -121,6 +121,11 @@ SYMBOLS = [
     ("qn_quadratic_create_synthetic", C.c_int, [C.c_void_p, C.c_size_t, C.c_uint64, dp, dp, C.POINTER(C.c_void_p)]),
     ("qn_logsumexp_create", C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, dp, dp, C.c_double, C.POINTER(C.c_void_p)]),
     ("qn_logistic_create", C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, dp, dp, dp, C.c_double, C.POINTER(C.c_void_p)]),
+    ("qn_sparse_logistic_create", C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, dp, dp, dp, C.c_double,
+                                            C.POINTER(C.c_void_p)]),
+    ("qn_sparse_logistic_set_lanes", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    ("qn_sparse_logistic_info", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t),
+                                          C.POINTER(C.c_size_t)]),
     ("qn_sparse_quadratic_create", C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, dp, dp, C.POINTER(C.c_void_p)]),
     ("qn_sparse_quadratic_set_lanes_per_row", C.c_int, [C.c_void_p, C.c_int]),
     ("qn_objective_sparse_info", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),

@@ -82,6 +82,9 @@ extern "C" const char* qn_status_string(int status) {
 // the logistic objective (two launches per evaluation; its Hessian-vector product is the log-sum-exp one's kernels): behind every existing kernel
 #include "qn_logistic.hip.h"
 #include "qn_host_logistic.hip.h"
+// the sparse logistic objective (A and A' in CSR; three launches per evaluation and per Hessian-vector product): behind every existing kernel
+#include "qn_sparse_logistic.hip.h"
+#include "qn_host_sparse_logistic.hip.h"
 // truncated Newton (NewtonCG) on the first-order family's machine: conjugate gradients on H z = g with that product, behind every existing kernel
 #include "qn_newton_cg.hip.h"
 #include "qn_host_newton_cg.hip.h"

@@ -3,10 +3,17 @@
 // ------------------------------------------------------------------------------------------------
 // objectives
 // ------------------------------------------------------------------------------------------------
-enum { OBJ_QUADRATIC = 1, OBJ_LOGSUMEXP = 2, OBJ_SPARSE_QUADRATIC = 3, OBJ_LOGISTIC = 4 };
+enum { OBJ_QUADRATIC = 1, OBJ_LOGSUMEXP = 2, OBJ_SPARSE_QUADRATIC = 3, OBJ_LOGISTIC = 4, OBJ_SPARSE_LOGISTIC = 5 };
 // the sparse quadratic's launch shape (qn_sparse.hip.h; the creation below cuts the rows for it)
 #define SPQ_MAXG 2048     // regular workgroups at the most: 8 per CU on 256 CUs
 #define SPQ_LONG_ROW 2048 // rows longer than this get a workgroup of their own
+// one CSR copy of the sparse logistic objective (qn_sparse_logistic.hip.h): the matrix, its static cut, its long rows, its shares, its lanes per row
+struct QnSlogCsr {
+    DevBuf<int> row_ptr, col, cut, longs;
+    DevBuf<double> val, part;
+    size_t rows = 0;
+    int G = 0, n_long = 0, lanes = 1, lanes_auto = 1;
+};
 static std::atomic<uint64_t> g_objective_serial{0}; // objectives are numbered at creation: an address can come back after a destroy, a serial cannot
 struct qn_objective {
     uint64_t serial = ++g_objective_serial;
@@ -40,6 +47,9 @@ struct qn_objective {
     // d at the accepted point in lw, the margins of one launch in lz, f and g of a weights pass in lscal and lgpart
     DevBuf<double> lw_trial; // d of the evaluations that are not a weights pass (trial points): written, never read
     DevBuf<double> lzero;    // n_pad zeros: what the Hessian-vector product's kernels take where log-sum-exp has gbar
+    // sparse logistic (qn_sparse_logistic.hip.h): A and A' in CSR (sp_nnz entries each), yw in b (m); lw, lw_trial, lzero, lgpart, lscal as the logistic's
+    QnSlogCsr sl_a, sl_at;
+    DevBuf<double> sl_coef, sl_t; // m each: -(yw s) of one evaluation, d o (A v) of one product -- what the column pass gathers
 };
 
 static int objective_base(qn_context* ctx, size_t n, const double* b_host, qn_objective** out) {
@@ -138,6 +148,12 @@ static int spq_enqueue_eval(qn_objective* o, const double* x_dev, double* f_dev,
 static int logit_enqueue_eval(qn_objective* o, const double* x_dev, double* f_dev, double* g_dev, double* d_dev, int which = 3);
 static int logit_enqueue_weights(qn_objective* o, const double* x_dev);
 static int logit_hess_vec_at(qn_objective* o, const double* x_host, const double* v_host, double* q_host, double* vhv);
+// ---- the sparse logistic objective (kernels: qn_sparse_logistic.hip.h; creation and these launches: qn_host_sparse_logistic.hip.h) ----
+static int slog_enqueue_eval(qn_objective* o, const double* x_dev, double* f_dev, double* g_dev, double* d_dev, int which = 3);
+static int slog_enqueue_weights(qn_objective* o, const double* x_dev);
+static int slog_hess_vec_at(qn_objective* o, const double* x_host, const double* v_host, double* q_host, double* vhv);
+static uint64_t slog_eval_bytes(const qn_objective* o);
+static uint64_t slog_product_bytes(const qn_objective* o);
 
 template <class I>
 static int spq_validate(size_t n, size_t nnz, const I* rp, const I* ci) {
@@ -258,6 +274,7 @@ extern "C" int qn_sparse_quadratic_set_lanes_per_row(qn_objective* o, int lanes)
 
 extern "C" int qn_objective_sparse_info(qn_objective* o, size_t* nnz, int* lanes_per_row, size_t* n_long_rows, int* symmetric) {
     if (o && o->kind == OBJ_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "a logistic objective is not a sparse quadratic (its A is dense)");
+    if (o && o->kind == OBJ_SPARSE_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "a sparse logistic objective is not a sparse quadratic: qn_sparse_logistic_info describes it");
     if (!o || o->kind != OBJ_SPARSE_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "not a sparse quadratic");
     if (nnz) *nnz = o->sp_nnz;
     if (lanes_per_row) *lanes_per_row = o->sp_lanes;
@@ -376,6 +393,7 @@ extern "C" void qn_objective_destroy(qn_objective* o) {
 
 extern "C" int qn_objective_get_rows(qn_objective* o, size_t row0, size_t nrows, double* out_host) {
     if (o->kind == OBJ_SPARSE_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "a sparse quadratic has no dense rows / Hessian");
+    if (o->kind == OBJ_SPARSE_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "a sparse logistic objective has no dense rows / Hessian");
     if (o->kind != OBJ_QUADRATIC && o->kind != OBJ_LOGSUMEXP && o->kind != OBJ_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
     const bool lse = o->kind == OBJ_LOGSUMEXP || o->kind == OBJ_LOGISTIC; // (rows of the dense A)
     const size_t lo = lse ? (size_t)o->TA.row_off : (size_t)o->T.row_off;
@@ -430,12 +448,13 @@ extern "C" int qn_objective_eval(qn_objective* o, const double* x_host, double* 
         HIPCHK(hipStreamSynchronize(c->stream));
         return QN_OK;
     }
-    if (o->kind == OBJ_SPARSE_QUADRATIC || o->kind == OBJ_LOGISTIC) {
+    if (o->kind == OBJ_SPARSE_QUADRATIC || o->kind == OBJ_LOGISTIC || o->kind == OBJ_SPARSE_LOGISTIC) {
         QNCHK(o->ex.ensure(2 * np, c->stream));
         QNCHK(o->eg.ensure(np, c->stream));
         QNCHK(o->ef.ensure(2, c->stream));
         HIPCHK(hipMemcpyAsync(o->ex, x_host, o->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
         if (o->kind == OBJ_LOGISTIC) QNCHK(logit_enqueue_eval(o, o->ex, o->ef, o->eg, o->lw_trial)); // (lw keeps the last weights pass's d)
+        else if (o->kind == OBJ_SPARSE_LOGISTIC) QNCHK(slog_enqueue_eval(o, o->ex, o->ef, o->eg, o->lw_trial));
         else QNCHK(spq_enqueue_eval(o, o->ex, o->ef, o->eg));
         HIPCHK(hipMemcpyAsync(f, o->ef, sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(g_host, o->eg, o->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -468,6 +487,7 @@ extern "C" int qn_objective_hessian(qn_objective* o, const double* x_host, doubl
     if (!o || !x_host) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
     if (o->kind == OBJ_SPARSE_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "a sparse quadratic has no dense rows / Hessian");
     if (o->kind == OBJ_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "the dense Hessian of a logistic objective is not built: hess_vec_at gives H(x) v in one stream of A");
+    if (o->kind == OBJ_SPARSE_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "a sparse logistic objective has no dense rows / Hessian: hess_vec_at gives H(x) v");
     qn_context* c = o->ctx;
     if (c->world != 1) return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hessian is single-GPU");
     HIPCHK(hipSetDevice(c->device));

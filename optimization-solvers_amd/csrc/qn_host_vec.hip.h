@@ -152,6 +152,13 @@ static int vec_enqueue_eval(VecRun& r) {
         s->stats.launches += 2;
         return QN_OK;
     }
+    if (r.obj && r.obj->kind == OBJ_SPARSE_LOGISTIC) {
+        // the row pass and the column pass, then the finish (qn_sparse_logistic.hip.h), timed apart as above.  d goes to the trial buffer, as the logistic's
+        { ProfScope ps(s, KC_EVAL); QNCHK(slog_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt, r.obj->lw_trial, 1)); }
+        { ProfScope ps(s, KC_CTL); QNCHK(slog_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt, r.obj->lw_trial, 2)); }
+        s->stats.launches += 3;
+        return QN_OK;
+    }
     ProfScope ps(s, KC_EVAL);
     if (r.o->kind == QN_ORACLE_HOST) { // s->hx holds xt (vec_peek)
         double f = NAN;
@@ -246,7 +253,8 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     const bool pn = pn_method(s->method), lbfgs = s->method == QN_LBFGS, cg = s->method == QN_NONLINEAR_CG, tn = s->method == QN_NEWTON_CG;
     VecRun r{s, o, nullptr, {}};
     QNCHK(check_oracle(c, s->n, o, &r.obj));
-    if (r.obj && r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_LOGSUMEXP && r.obj->kind != OBJ_SPARSE_QUADRATIC && r.obj->kind != OBJ_LOGISTIC)
+    if (r.obj && r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_LOGSUMEXP && r.obj->kind != OBJ_SPARSE_QUADRATIC && r.obj->kind != OBJ_LOGISTIC &&
+        r.obj->kind != OBJ_SPARSE_LOGISTIC)
         return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
     if (tn) QNCHK(tn_check(s, ls, r.obj, ls_only)); // unbounded, log-sum-exp, BackTracking or StrongWolfe without a box
     const bool exact = ls->kind == QN_LS_EXACT_QUADRATIC;
@@ -358,7 +366,10 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
             s->stats.obj_bytes += h->ex_passes * (12ull * (uint64_t)r.obj->sp_nnz + 4ull * ((uint64_t)s->n + 1) + 16ull * (uint64_t)s->n);
         if (r.obj && r.obj->kind == OBJ_LOGISTIC) // one stream of A per evaluation
             s->stats.obj_bytes = h->n_evals * (uint64_t)r.obj->m * (uint64_t)r.obj->T.n_pad * 8ull;
-        if (tn) // a product streams A once (8 m n_pad), the weights at x_k twice (16 m n_pad) for log-sum-exp, once for the logistic objective
+        if (r.obj && r.obj->kind == OBJ_SPARSE_LOGISTIC) { // both CSR copies per evaluation, per product and per weights pass (slog_eval_bytes)
+            s->stats.obj_bytes = h->n_evals * slog_eval_bytes(r.obj);
+            if (tn) s->stats.obj_bytes += (uint64_t)h->tn_hv_passes * slog_product_bytes(r.obj) + tn_weights * slog_eval_bytes(r.obj);
+        } else if (tn) // a product streams A once (8 m n_pad), the weights at x_k twice (16 m n_pad) for log-sum-exp, once for the logistic objective
             s->stats.obj_bytes += ((uint64_t)h->tn_hv_passes + (r.obj->kind == OBJ_LOGISTIC ? 1ull : 2ull) * tn_weights) * (uint64_t)r.obj->m * (uint64_t)r.obj->T.n_pad * 8ull;
         stats_add_totals(s); // (no update passes, one rank: total_h_* and total_xchg_* stay)
         s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u) | (lbfgs ? QN_PATH_LBFGS : 0u) | (cg ? QN_PATH_CG : 0u) | (exact ? QN_PATH_EXACT : 0u) | (tn ? QN_PATH_NEWTON_CG : 0u);

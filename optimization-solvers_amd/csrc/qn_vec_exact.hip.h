@@ -169,6 +169,8 @@ static int exact_enqueue_advance(VecRun& r) {
 
 extern "C" int qn_objective_hess_vec(qn_objective* o, const double* v_host, double* q_host, double* vqv) {
     if (!o || !v_host || !vqv) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
+    if (o->kind == OBJ_SPARSE_LOGISTIC)
+        return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hess_vec: the Hessian of a sparse logistic objective depends on x: use qn_objective_hess_vec_at");
     if (o->kind == OBJ_LOGISTIC)
         return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hess_vec: the Hessian of a logistic objective depends on x: use qn_objective_hess_vec_at");
     if (o->kind != OBJ_QUADRATIC && o->kind != OBJ_SPARSE_QUADRATIC)

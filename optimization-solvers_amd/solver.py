@@ -587,6 +587,7 @@ class Objective:
         """(H(x) v, v'H(x)v) without the matrix.  LogSumExp: the softmax weights at x (two passes of A), then ONE stream of A for
         A'(p o (A v)) - gbar (p . (A v)) + mu v -- the bytes of one evaluation; n_pad <= 16384, one rank (otherwise ErrorInputParams, "not built").
         Logistic: the weights d_i = w_i s_i (1 - s_i) at x (ONE pass of A), then one stream of A for A'(d o (A v)) + mu v.
+        SparseLogistic: the same product on the two CSR copies -- a weights pass at x, a row pass over A, a column pass over A', a fold; any n.
         Quadratic / SparseQuadratic: x is not read and the call is `hess_vec(v)`, bit for bit.  download=False: (None, v'Hv)."""
         if not self.h:
             raise ErrorInputParams("the objective is closed")
@@ -769,6 +770,89 @@ class Logistic(Objective):
         _check(A.lib().qn_logistic_create(ctx.h, m, n, _dp(a), _dp(y), _dp(w) if w is not None else None, float(mu), C.byref(h)))
         super().__init__(ctx, h, n)
         self.m = m
+
+
+class SparseLogistic(Objective):
+    """Regularised logistic regression on the device with a SPARSE A in CSR (m x n; the columns of a row strictly increasing) and no limit on n:
+    f = sum_i w_i log(1 + exp(-y_i a_i'x)) + mu/2 ||x||^2, g = -A'(y o w o s) + mu x, H(x) v = A'(d o (A v)) + mu v.  Labels (exactly -1 / +1), `weights`
+    (>= 0, finite; a 0 masks its row) and mu (finite) follow `Logistic`'s rules.
+
+    The device keeps A AND A' (the host transposes at creation): 24 bytes per nonzero.  The transpose product walks the rows of A' with the kernel
+    that walks the rows of A -- no float atomics, every sum in one fixed order, the same bits from run to run and from object to object.  A dense
+    column (an intercept column of ones) is a long row of A' and gets a whole workgroup.  One evaluation is three launches; it runs under
+    SpectralProjectedGradient, ProjectedGradientDescent, LBFGS / ProjectedLBFGS, NonlinearCG and NewtonCG; `hess_vec_at(x, v)` gives
+    (H(x) v, v'H(x)v).  One rank; `hessian`, `hess_vec` and `rows`: ErrorInputParams.
+    int32 or int64 index arrays are passed through as they are (one width for both: a mixed pair goes as int64), other integer types as int64."""
+
+    def __init__(self, indptr, indices, data, y, mu, n, weights=None, ctx=None):
+        ctx = ctx or default_context()
+        indptr, indices = np.asarray(indptr), np.asarray(indices)
+        if indptr.dtype.kind not in "iu" or (indices.size and indices.dtype.kind not in "iu"):
+            raise ErrorInputParams("indptr and indices must be integer arrays")
+        it = indptr.dtype if indptr.dtype == indices.dtype and indptr.dtype in (np.dtype(np.int32), np.dtype(np.int64)) else np.dtype(np.int64)
+        indptr, indices = np.ascontiguousarray(indptr, dtype=it), np.ascontiguousarray(indices, dtype=it)
+        data, y = _f64(data), _f64(y)
+        if indptr.ndim != 1 or indices.ndim != 1 or data.ndim != 1 or y.ndim != 1 or indptr.size != y.size + 1 or indices.size != data.size:
+            raise ErrorInputParams("CSR arrays do not match: indptr has m + 1 entries, indices and data nnz each, y has m")
+        m = y.size
+        w = None if weights is None else _f64(weights)
+        if w is not None and (w.ndim != 1 or w.size != m):
+            raise ErrorInputParams(f"weights has {w.size} entries, a has {m} rows")
+        # (an empty array's pointer may be null, which the library takes for a missing argument)
+        ci = indices if indices.size else np.zeros(1, dtype=it)
+        va = data if data.size else np.zeros(1)
+        h = C.c_void_p()
+        _check(A.lib().qn_sparse_logistic_create(ctx.h, m, int(n), data.size, indptr.ctypes.data_as(C.c_void_p), ci.ctypes.data_as(C.c_void_p),
+                                                 it.itemsize, _dp(va), _dp(y), _dp(w) if w is not None else None, float(mu), C.byref(h)))
+        super().__init__(ctx, h, int(n))
+        self.m = m
+
+    @classmethod
+    def from_scipy(cls, a, y, mu, weights=None, ctx=None):
+        """Any scipy sparse matrix (m x n): through .tocsr() with sorted indices and duplicates summed."""
+        import scipy.sparse  # noqa: F401 -- only this method needs scipy
+        a = a.tocsr().copy()
+        a.sum_duplicates()
+        a.sort_indices()
+        return cls(a.indptr, a.indices, a.data, y, mu, a.shape[1], weights=weights, ctx=ctx)
+
+    def __call__(self, x):
+        if not self.h:
+            raise ErrorInputParams("the objective is closed")
+        if np.size(x) != self.n:
+            raise ErrorInputParams(f"x has {np.size(x)} entries, the objective has {self.n}")
+        return super().__call__(x)
+
+    def _info(self):
+        if not self.h:
+            raise ErrorInputParams("the objective is closed")
+        nnz, lr, lc, nlr, nlc = C.c_size_t(), C.c_int(), C.c_int(), C.c_size_t(), C.c_size_t()
+        _check(A.lib().qn_sparse_logistic_info(self.h, C.byref(nnz), C.byref(lr), C.byref(lc), C.byref(nlr), C.byref(nlc)))
+        return nnz.value, (lr.value, lc.value), nlr.value, nlc.value
+
+    @property
+    def nnz(self):
+        return self._info()[0]
+
+    @property
+    def lanes(self):
+        """(lanes per row of the row pass over A, of the column pass over A')"""
+        return self._info()[1]
+
+    @property
+    def n_long_rows(self):
+        return self._info()[2]
+
+    @property
+    def n_long_cols(self):
+        return self._info()[3]
+
+    def set_lanes(self, rows, cols):
+        """Lanes that share one row of A (`rows`) and one row of A' (`cols`): 1, 2, 4, 8, 16, 32 or 64; 0: chosen from that copy's mean row length.
+        Another value may change the bits of f, g and H v."""
+        if not self.h:
+            raise ErrorInputParams("the objective is closed")
+        _check(A.lib().qn_sparse_logistic_set_lanes(self.h, int(rows), int(cols)))
 
 
 class _SolverBase:
@@ -1286,7 +1370,7 @@ class NewtonCG(_SolverBase):
     """Truncated Newton: `new(tol, x0, eta_max=0.5, max_inner=0, chunk=8)`; Newton's direction from a few conjugate-gradient steps on H z = g,
     each costing one Hessian-vector product of the device LogSumExp or Logistic objective (one stream of A, never a matrix).  The inner loop ends once
     ||r|| <= min(eta_max, sqrt(||g||)) ||g||, after max_inner steps (0: min(n, 100)) or on curvature that is not positive; `chunk` inner steps
-    are enqueued per batch (it never changes a bit).  UNBOUNDED ONLY; objective: LogSumExp or Logistic with n_pad <= 16384; line searches: BackTracking and
+    are enqueued per batch (it never changes a bit).  UNBOUNDED ONLY; objective: LogSumExp or Logistic with n_pad <= 16384, or SparseLogistic (any n); line searches: BackTracking and
     StrongWolfe, first trial t = 1.  Closures, quadratics, other searches: ErrorInputParams."""
     METHOD = A.NEWTON_CG
 
