@@ -258,6 +258,28 @@ int qn_sparse_logistic_create(qn_context* ctx, size_t m, size_t n, size_t nnz, c
 int qn_sparse_logistic_set_lanes(qn_objective* objective, int lanes_rows, int lanes_cols);
 /* nnz, the lanes per row in use for each pass, and the long rows of A and of A' (any pointer may be NULL).  Another objective: QN_ERROR_INPUT_PARAMS. */
 int qn_sparse_logistic_info(qn_objective* objective, size_t* nnz, int* lanes_rows, int* lanes_cols, size_t* n_long_rows, size_t* n_long_cols);
+/* Regularised softmax (multinomial logistic) regression on a dense A (m x n row-major): labels y_i in {0, .., K-1} (labels_i32_host: m int32 values),
+ * sample weights w_i >= 0 (w_host, NULL: all ones; a weight of 0 masks its row: it adds nothing to f, g or H), K = n_classes >= 2, any finite mu.
+ * The parameter vector is CLASS-MAJOR: x[k n + j] = W[k, j], N = K n entries with no padding between classes (sklearn's coef_ raveled); g and H v use
+ * the same layout, and the objective's dimension -- what a solver is created with -- is N.
+ *     f = sum_i w_i (logsumexp_k a_i.W_k - a_i.W_{y_i}) + mu/2 ||x||^2,   g_k = sum_i w_i (p_ik - [y_i = k]) a_i + mu W_k,   p_i = softmax_k(a_i.W_k)
+ *     (H v)_k = sum_i w_i p_ik (u_ik - sum_l p_il u_il) a_i + mu V_k,   u_ik = a_i.V_k
+ * A label outside [0, K), a negative or non-finite weight, a non-finite mu: QN_ERROR_INPUT_PARAMS, with the index.  A class that no row carries is
+ * legal.  Not built (QN_ERROR_INPUT_PARAMS before anything is allocated): a row-sharded context, a padded K n above 16384 (W stays on chip), K < 2,
+ * K > 256; every shape inside these limits runs.  One evaluation is TWO launches (csrc/qn_multinomial.hip.h): ONE stream of A serves all K classes, stable for every finite margin; no
+ * atomics, the same bits for the same x from run to run and from object to object.  It runs under QN_SPG, QN_PROJECTED_GRADIENT, QN_LBFGS,
+ * QN_NONLINEAR_CG and QN_NEWTON_CG with every line search those take but ExactQuadratic; every other method: QN_ERROR_INPUT_PARAMS.
+ * qn_objective_hess_vec_at gives H(x) v (one weights pass of A at x, one product pass); qn_objective_hess_vec, qn_objective_hessian,
+ * qn_objective_get_rows and qn_objective_sparse_info on it: QN_ERROR_INPUT_PARAMS. */
+int qn_multinomial_create(qn_context* ctx, size_t m, size_t n, size_t n_classes, const double* a_rowmajor_host, const void* labels_i32_host,
+                          const double* w_host, double mu, qn_objective** out);
+/* The class probabilities at x (N entries, class-major): p_host receives m x K row-major, P[i, k] = p_ik; a masked row's are stored as zeros (they are
+ * the Hessian's weights).  One weights pass of A. */
+int qn_multinomial_probabilities(qn_objective* objective, const double* x_host, double* p_host);
+/* Which kernel streams A: 1 the register-blocked kernel on the vector unit (every shape inside the limits), 2 the v_mfma_f64_16x16x4_f64 kernel (K <= 64
+ * where its cut and its LDS fit; otherwise QN_ERROR_INPUT_PARAMS and nothing changes), 0 the automatic choice, which a new objective has.  The two
+ * kernels sum in different orders: each gives the same bits from run to run, not the other's. */
+int qn_multinomial_set_kernel(qn_objective* objective, int kernel);
 /* f = 1/2 x'Qx - b'x, g = Qx - b with a SPARSE Q: n x n in CSR, both triangles of a symmetric matrix -- the device objective that exists at the
  * sizes the O(n) solvers are for.  It runs under QN_SPG, QN_PROJECTED_GRADIENT and QN_LBFGS with every line search those take; every other method:
  * QN_ERROR_INPUT_PARAMS ("unsupported objective"; the projected Newton pair: "Hessian not available in the oracle").  One rank (a row-sharded

@@ -355,6 +355,41 @@ class SparseLogistic {
     size_t n_long_cols() const { size_t v = 0; check(qn_sparse_logistic_info(h_, nullptr, nullptr, nullptr, nullptr, &v)); return v; }
 };
 
+// a device-resident regularised softmax (multinomial logistic) regression on a dense A (m x n row-major): labels in {0, .., n_classes - 1} (anything
+// else throws ErrorInputParams), weights >= 0 (a 0 masks its row; empty: all ones).  The parameter vector is CLASS-MAJOR, x[k n + j] = W[k, j], with
+// N = n_classes * n entries: that is the dimension a solver is created with.  It runs under SpectralProjectedGradient, ProjectedGradientDescent,
+// LBFGS / ProjectedLBFGS, NonlinearCG and NewtonCG.
+class Multinomial {
+    qn_objective* h_ = nullptr;
+    size_t n_, k_;
+  public:
+    Multinomial(const DVector& a_rowmajor, const std::vector<int32_t>& labels, size_t n, size_t n_classes, Floating mu, const DVector& weights = DVector(),
+                Context& ctx = Context::default_context()) : n_(n * n_classes), k_(n_classes) {
+        if (!weights.empty() && weights.size() != labels.size()) throw SolverError{SolverError::ErrorInputParams, "weights does not have one entry per row"};
+        if (a_rowmajor.size() != labels.size() * n) throw SolverError{SolverError::ErrorInputParams, "a_rowmajor is not labels.size() x n"};
+        check(qn_multinomial_create(ctx.handle(), labels.size(), n, n_classes, a_rowmajor.data(), labels.data(), weights.empty() ? nullptr : weights.data(), mu, &h_));
+    }
+    Multinomial(const Multinomial&) = delete;
+    ~Multinomial() { qn_objective_destroy(h_); }
+    qn_objective* handle() const { return h_; }
+    size_t n_classes() const { return k_; }
+    size_t size() const { return n_; } // N = n_classes * n
+    void set_kernel(int kernel) { check(qn_multinomial_set_kernel(h_, kernel)); } // 0: automatic, 1: register-blocked, 2: MFMA (K <= 64 where built)
+    FuncEvalMultivariate operator()(const DVector& x) const {
+        DVector g(n_);
+        Floating f = 0;
+        check(qn_objective_eval(h_, x.data(), &f, g.data()));
+        return FuncEvalMultivariate(f, std::move(g));
+    }
+    std::pair<DVector, Floating> hess_vec_at(const DVector& x, const DVector& v) const { // (H(x) v, v'H(x)v): P at x (one pass of A), then one stream of A; no matrix
+        if (x.size() != n_ || v.size() != n_) throw SolverError{SolverError::ErrorInputParams, "x or v does not have the objective's N entries"};
+        DVector q(n_);
+        Floating c = 0;
+        check(qn_objective_hess_vec_at(h_, x.data(), v.data(), q.data(), &c));
+        return {std::move(q), c};
+    }
+};
+
 // a device-resident objective f = 1/2 x'Qx - b'x with a sparse Q in CSR (both triangles of a symmetric matrix): the large objective of the O(n)
 // solvers -- SpectralProjectedGradient, ProjectedGradientDescent, LBFGS / ProjectedLBFGS.  Index: int32_t or int64_t, for both arrays.
 class SparseQuadratic {
@@ -452,7 +487,7 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
     // (a device objective is callable too: without the constraint a non-const Quadratic / LogSumExp lvalue would bind here, as a host closure)
     template <class LS, class Oracle, class = std::enable_if_t<!std::is_same_v<std::decay_t<Oracle>, Quadratic> && !std::is_same_v<std::decay_t<Oracle>, LogSumExp> &&
                                                                !std::is_same_v<std::decay_t<Oracle>, SparseQuadratic> && !std::is_same_v<std::decay_t<Oracle>, Logistic> &&
-                                                               !std::is_same_v<std::decay_t<Oracle>, SparseLogistic>>>
+                                                               !std::is_same_v<std::decay_t<Oracle>, SparseLogistic> && !std::is_same_v<std::decay_t<Oracle>, Multinomial>>>
     Result minimize(LS& line_search, Oracle&& oracle, size_t max_iter_solver, size_t max_iter_line_search,
                     std::optional<std::function<void(const Self&)>> callback = std::nullopt) {
         using OracleT = std::remove_reference_t<Oracle>;
@@ -505,6 +540,14 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
     }
     template <class LS>
     Result minimize(LS& line_search, const Logistic& objective, size_t max_iter_solver, size_t max_iter_line_search) {
+        qn_oracle o{};
+        o.kind = QN_ORACLE_OBJECTIVE;
+        o.memoize = 1;
+        o.objective = objective.handle();
+        return make_result(qn_minimize(h_, &line_search.ffi(), &o, max_iter_solver, max_iter_line_search, nullptr, nullptr));
+    }
+    template <class LS>
+    Result minimize(LS& line_search, const Multinomial& objective, size_t max_iter_solver, size_t max_iter_line_search) {
         qn_oracle o{};
         o.kind = QN_ORACLE_OBJECTIVE;
         o.memoize = 1;

@@ -530,6 +530,8 @@ static int minimize_impl(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, si
         return fail(QN_ERROR_INPUT_PARAMS, "a Logistic objective runs under SPG, projected gradient, LBFGS / ProjectedLBFGS, NonlinearCG and NewtonCG (the dense quasi-Newton family, the control-step solvers and Newton: out of scope)");
     else if (r.obj && r.obj->kind == OBJ_SPARSE_LOGISTIC)
         return fail(QN_ERROR_INPUT_PARAMS, "a SparseLogistic objective runs under SPG, projected gradient, LBFGS / ProjectedLBFGS, NonlinearCG and NewtonCG (the dense quasi-Newton family, the control-step solvers and Newton: out of scope)");
+    else if (r.obj && r.obj->kind == OBJ_MULTINOMIAL)
+        return fail(QN_ERROR_INPUT_PARAMS, "a Multinomial objective runs under SPG, projected gradient, LBFGS / ProjectedLBFGS, NonlinearCG and NewtonCG (the dense quasi-Newton family, the control-step solvers and Newton: out of scope)");
     else if (r.obj && r.obj->kind != OBJ_LOGSUMEXP) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective"); // (log-sum-exp: evaluated by its own kernels into (f_dev, gt))
     QNCHK(plan_run(r, s, ls, o, max_iter_solver, max_iter_line_search, ls_f0));
     if (r.sym2) QNCHK(plan_s2_args(r));

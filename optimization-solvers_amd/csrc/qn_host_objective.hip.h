@@ -1,9 +1,9 @@
-// qn_host_objective.hip.h -- host side, part 3 of 7: device-resident objectives (the synthetic quadratic, the log-sum-exp, the sparse quadratic, the logistic) and their evaluation launches.
+// qn_host_objective.hip.h -- host side, part 3 of 7: device-resident objectives (the synthetic quadratic, the log-sum-exp, the sparse quadratic, the logistic pair, the multinomial) and their evaluation launches.
 #pragma once
 // ------------------------------------------------------------------------------------------------
 // objectives
 // ------------------------------------------------------------------------------------------------
-enum { OBJ_QUADRATIC = 1, OBJ_LOGSUMEXP = 2, OBJ_SPARSE_QUADRATIC = 3, OBJ_LOGISTIC = 4, OBJ_SPARSE_LOGISTIC = 5 };
+enum { OBJ_QUADRATIC = 1, OBJ_LOGSUMEXP = 2, OBJ_SPARSE_QUADRATIC = 3, OBJ_LOGISTIC = 4, OBJ_SPARSE_LOGISTIC = 5, OBJ_MULTINOMIAL = 6 };
 // the sparse quadratic's launch shape (qn_sparse.hip.h; the creation below cuts the rows for it)
 #define SPQ_MAXG 2048     // regular workgroups at the most: 8 per CU on 256 CUs
 #define SPQ_LONG_ROW 2048 // rows longer than this get a workgroup of their own
@@ -14,6 +14,10 @@ struct QnSlogCsr {
     size_t rows = 0;
     int G = 0, n_long = 0, lanes = 1, lanes_auto = 1;
 };
+// the multinomial objective's cut of its 512 threads (qn_multinomial.hip.h: mnl_plan)
+struct QnMnlPlan { int tj_log2, KC, NC, R, RT, WQ; bool ok; };
+// mnl_mfma_kernel's cut (mnl_mfma_plan); `ok`: that kernel is built for the shape
+struct QnMnlMfmaPlan { int wk_log2, CTW; size_t lds; bool ok; };
 static std::atomic<uint64_t> g_objective_serial{0}; // objectives are numbered at creation: an address can come back after a destroy, a serial cannot
 struct qn_objective {
     uint64_t serial = ++g_objective_serial;
@@ -50,6 +54,14 @@ struct qn_objective {
     // sparse logistic (qn_sparse_logistic.hip.h): A and A' in CSR (sp_nnz entries each), yw in b (m); lw, lw_trial, lzero, lgpart, lscal as the logistic's
     QnSlogCsr sl_a, sl_at;
     DevBuf<double> sl_coef, sl_t; // m each: -(yw s) of one evaluation, d o (A v) of one product -- what the column pass gathers
+    // multinomial (qn_multinomial.hip.h): A rows in Q ([mrpr][mn_nfp]), the weights in b (m_pad), n = K n_features (class-major), T its padding; lse_G, lwgms,
+    // lwgg ([workgroup][N_pad]), lzero, lgpart, lscal as the logistic's; P (m_pad x K) at the accepted point in mn_P, of trial evaluations in mn_P_trial
+    int mn_k = 0, mn_nf = 0, mn_nfp = 0;
+    QnMnlPlan mn_plan{};
+    QnMnlMfmaPlan mn_mfma{};
+    int mn_kernel = 1; // the stream's kernel in use: 1 mnl_onepass_kernel (vector unit), 2 mnl_mfma_kernel (qn_multinomial_set_kernel)
+    DevBuf<int> mn_lab;
+    DevBuf<double> mn_P, mn_P_trial;
 };
 
 static int objective_base(qn_context* ctx, size_t n, const double* b_host, qn_objective** out) {
@@ -154,6 +166,12 @@ static int slog_enqueue_weights(qn_objective* o, const double* x_dev);
 static int slog_hess_vec_at(qn_objective* o, const double* x_host, const double* v_host, double* q_host, double* vhv);
 static uint64_t slog_eval_bytes(const qn_objective* o);
 static uint64_t slog_product_bytes(const qn_objective* o);
+// ---- the multinomial objective (kernel: qn_multinomial.hip.h; creation and these launches: qn_host_multinomial.hip.h) ----
+struct QnVecCtl;
+static int mnl_enqueue_eval(qn_objective* o, const double* x_dev, double* f_dev, double* g_dev, double* p_dev, int which = 3);
+static int mnl_enqueue_weights(qn_objective* o, const double* x_dev);
+static int mnl_enqueue_hess_vec(qn_objective* o, const double* v_dev, double* q_dev, const QnVecCtl* ctl, int which = 3);
+static int mnl_hess_vec_at(qn_objective* o, const double* x_host, const double* v_host, double* q_host, double* vhv);
 
 template <class I>
 static int spq_validate(size_t n, size_t nnz, const I* rp, const I* ci) {
@@ -275,6 +293,7 @@ extern "C" int qn_sparse_quadratic_set_lanes_per_row(qn_objective* o, int lanes)
 extern "C" int qn_objective_sparse_info(qn_objective* o, size_t* nnz, int* lanes_per_row, size_t* n_long_rows, int* symmetric) {
     if (o && o->kind == OBJ_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "a logistic objective is not a sparse quadratic (its A is dense)");
     if (o && o->kind == OBJ_SPARSE_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "a sparse logistic objective is not a sparse quadratic: qn_sparse_logistic_info describes it");
+    if (o && o->kind == OBJ_MULTINOMIAL) return fail(QN_ERROR_INPUT_PARAMS, "a multinomial objective is not a sparse quadratic (its A is dense)");
     if (!o || o->kind != OBJ_SPARSE_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "not a sparse quadratic");
     if (nnz) *nnz = o->sp_nnz;
     if (lanes_per_row) *lanes_per_row = o->sp_lanes;
@@ -394,6 +413,7 @@ extern "C" void qn_objective_destroy(qn_objective* o) {
 extern "C" int qn_objective_get_rows(qn_objective* o, size_t row0, size_t nrows, double* out_host) {
     if (o->kind == OBJ_SPARSE_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "a sparse quadratic has no dense rows / Hessian");
     if (o->kind == OBJ_SPARSE_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "a sparse logistic objective has no dense rows / Hessian");
+    if (o->kind == OBJ_MULTINOMIAL) return fail(QN_ERROR_INPUT_PARAMS, "get_rows is not built for a multinomial objective (its n is K n_features, not the width of A)");
     if (o->kind != OBJ_QUADRATIC && o->kind != OBJ_LOGSUMEXP && o->kind != OBJ_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
     const bool lse = o->kind == OBJ_LOGSUMEXP || o->kind == OBJ_LOGISTIC; // (rows of the dense A)
     const size_t lo = lse ? (size_t)o->TA.row_off : (size_t)o->T.row_off;
@@ -448,13 +468,14 @@ extern "C" int qn_objective_eval(qn_objective* o, const double* x_host, double* 
         HIPCHK(hipStreamSynchronize(c->stream));
         return QN_OK;
     }
-    if (o->kind == OBJ_SPARSE_QUADRATIC || o->kind == OBJ_LOGISTIC || o->kind == OBJ_SPARSE_LOGISTIC) {
+    if (o->kind == OBJ_SPARSE_QUADRATIC || o->kind == OBJ_LOGISTIC || o->kind == OBJ_SPARSE_LOGISTIC || o->kind == OBJ_MULTINOMIAL) {
         QNCHK(o->ex.ensure(2 * np, c->stream));
         QNCHK(o->eg.ensure(np, c->stream));
         QNCHK(o->ef.ensure(2, c->stream));
         HIPCHK(hipMemcpyAsync(o->ex, x_host, o->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
         if (o->kind == OBJ_LOGISTIC) QNCHK(logit_enqueue_eval(o, o->ex, o->ef, o->eg, o->lw_trial)); // (lw keeps the last weights pass's d)
         else if (o->kind == OBJ_SPARSE_LOGISTIC) QNCHK(slog_enqueue_eval(o, o->ex, o->ef, o->eg, o->lw_trial));
+        else if (o->kind == OBJ_MULTINOMIAL) QNCHK(mnl_enqueue_eval(o, o->ex, o->ef, o->eg, o->mn_P_trial)); // (mn_P keeps the last weights pass's P)
         else QNCHK(spq_enqueue_eval(o, o->ex, o->ef, o->eg));
         HIPCHK(hipMemcpyAsync(f, o->ef, sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipMemcpyAsync(g_host, o->eg, o->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -488,6 +509,7 @@ extern "C" int qn_objective_hessian(qn_objective* o, const double* x_host, doubl
     if (o->kind == OBJ_SPARSE_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "a sparse quadratic has no dense rows / Hessian");
     if (o->kind == OBJ_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "the dense Hessian of a logistic objective is not built: hess_vec_at gives H(x) v in one stream of A");
     if (o->kind == OBJ_SPARSE_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "a sparse logistic objective has no dense rows / Hessian: hess_vec_at gives H(x) v");
+    if (o->kind == OBJ_MULTINOMIAL) return fail(QN_ERROR_INPUT_PARAMS, "the dense Hessian of a multinomial objective is not built: hess_vec_at gives H(x) v in one stream of A");
     qn_context* c = o->ctx;
     if (c->world != 1) return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hessian is single-GPU");
     HIPCHK(hipSetDevice(c->device));

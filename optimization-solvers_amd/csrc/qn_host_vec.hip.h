@@ -159,6 +159,14 @@ static int vec_enqueue_eval(VecRun& r) {
         s->stats.launches += 3;
         return QN_OK;
     }
+    if (r.obj && r.obj->kind == OBJ_MULTINOMIAL) {
+        // the stream of A for all classes, then the logistic's combine on the flat vector (qn_multinomial.hip.h), timed apart as above.  P goes to the
+        // trial buffer: `mn_P` keeps NewtonCG's weights at x_k
+        { ProfScope ps(s, KC_EVAL); QNCHK(mnl_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt, r.obj->mn_P_trial, 1)); }
+        { ProfScope ps(s, KC_CTL); QNCHK(mnl_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt, r.obj->mn_P_trial, 2)); }
+        s->stats.launches += 2;
+        return QN_OK;
+    }
     ProfScope ps(s, KC_EVAL);
     if (r.o->kind == QN_ORACLE_HOST) { // s->hx holds xt (vec_peek)
         double f = NAN;
@@ -254,7 +262,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     VecRun r{s, o, nullptr, {}};
     QNCHK(check_oracle(c, s->n, o, &r.obj));
     if (r.obj && r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_LOGSUMEXP && r.obj->kind != OBJ_SPARSE_QUADRATIC && r.obj->kind != OBJ_LOGISTIC &&
-        r.obj->kind != OBJ_SPARSE_LOGISTIC)
+        r.obj->kind != OBJ_SPARSE_LOGISTIC && r.obj->kind != OBJ_MULTINOMIAL)
         return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
     if (tn) QNCHK(tn_check(s, ls, r.obj, ls_only)); // unbounded, log-sum-exp, BackTracking or StrongWolfe without a box
     const bool exact = ls->kind == QN_LS_EXACT_QUADRATIC;
@@ -369,6 +377,9 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         if (r.obj && r.obj->kind == OBJ_SPARSE_LOGISTIC) { // both CSR copies per evaluation, per product and per weights pass (slog_eval_bytes)
             s->stats.obj_bytes = h->n_evals * slog_eval_bytes(r.obj);
             if (tn) s->stats.obj_bytes += (uint64_t)h->tn_hv_passes * slog_product_bytes(r.obj) + tn_weights * slog_eval_bytes(r.obj);
+        } else if (r.obj && r.obj->kind == OBJ_MULTINOMIAL) { // A once, P once (written or read), the workgroups' shares: per evaluation, product and weights pass
+            const uint64_t one = 8ull * ((uint64_t)r.obj->m * ((uint64_t)r.obj->mn_nfp + (uint64_t)r.obj->mn_k) + (uint64_t)r.obj->lse_G * (uint64_t)r.obj->T.n_pad);
+            s->stats.obj_bytes = (h->n_evals + (tn ? (uint64_t)h->tn_hv_passes + tn_weights : 0ull)) * one;
         } else if (tn) // a product streams A once (8 m n_pad), the weights at x_k twice (16 m n_pad) for log-sum-exp, once for the logistic objective
             s->stats.obj_bytes += ((uint64_t)h->tn_hv_passes + (r.obj->kind == OBJ_LOGISTIC ? 1ull : 2ull) * tn_weights) * (uint64_t)r.obj->m * (uint64_t)r.obj->T.n_pad * 8ull;
         stats_add_totals(s); // (no update passes, one rank: total_h_* and total_xchg_* stay)

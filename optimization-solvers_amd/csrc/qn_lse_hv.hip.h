@@ -215,9 +215,10 @@ static int lse_enqueue_hess_vec(qn_objective* o, const double* v_dev, const doub
 extern "C" int qn_objective_hess_vec_at(qn_objective* o, const double* x_host, const double* v_host, double* q_host, double* vhv) {
     if (!o || !v_host || !vhv) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
     if (o->kind == OBJ_QUADRATIC || o->kind == OBJ_SPARSE_QUADRATIC) return qn_objective_hess_vec(o, v_host, q_host, vhv); // (x is not read: the Hessian is Q)
-    if (o->kind != OBJ_LOGSUMEXP && o->kind != OBJ_LOGISTIC && o->kind != OBJ_SPARSE_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
+    if (o->kind != OBJ_LOGSUMEXP && o->kind != OBJ_LOGISTIC && o->kind != OBJ_SPARSE_LOGISTIC && o->kind != OBJ_MULTINOMIAL) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
     if (!x_host) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
     if (o->kind == OBJ_SPARSE_LOGISTIC) return slog_hess_vec_at(o, x_host, v_host, q_host, vhv); // (a weights pass, the product's two passes, the fold)
+    if (o->kind == OBJ_MULTINOMIAL) return mnl_hess_vec_at(o, x_host, v_host, q_host, vhv); // (one weights pass, its own stream in product mode, this file's combine with a zero gbar)
     if (o->kind == OBJ_LOGISTIC) return logit_hess_vec_at(o, x_host, v_host, q_host, vhv); // (one weights pass, this file's product with a zero gbar)
     QNCHK(lse_hv_built(o));
     qn_context* c = o->ctx;

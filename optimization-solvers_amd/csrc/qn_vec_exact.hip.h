@@ -173,6 +173,8 @@ extern "C" int qn_objective_hess_vec(qn_objective* o, const double* v_host, doub
         return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hess_vec: the Hessian of a sparse logistic objective depends on x: use qn_objective_hess_vec_at");
     if (o->kind == OBJ_LOGISTIC)
         return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hess_vec: the Hessian of a logistic objective depends on x: use qn_objective_hess_vec_at");
+    if (o->kind == OBJ_MULTINOMIAL)
+        return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hess_vec: the Hessian of a multinomial objective depends on x: use qn_objective_hess_vec_at");
     if (o->kind != OBJ_QUADRATIC && o->kind != OBJ_SPARSE_QUADRATIC)
         return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hess_vec: not built for this objective (a dense or a sparse quadratic has a Hessian-vector product)");
     qn_context* c = o->ctx;

@@ -772,6 +772,61 @@ class Logistic(Objective):
         self.m = m
 
 
+class Multinomial(Objective):
+    """Regularised softmax (multinomial logistic) regression on the device, with a dense A (m x n row-major), labels y_i in {0, .., K-1} and K =
+    `n_classes` >= 2.  The parameter vector is CLASS-MAJOR: x[k n + j] = W[k, j], N = K n entries (sklearn's `coef_` raveled); g and H v use the same
+    layout and `self.n` is N.
+        f = sum_i w_i (logsumexp_k a_i.W_k - a_i.W_{y_i}) + mu/2 ||x||^2,   g_k = sum_i w_i (p_ik - [y_i = k]) a_i + mu W_k
+        (H v)_k = sum_i w_i p_ik (u_ik - sum_l p_il u_il) a_i + mu V_k,   u_ik = a_i.V_k
+
+    LABELS: integers in [0, K); anything else (K, -1, 1.5) is ErrorInputParams with the index.  A class no row carries is legal.
+    MASKING: `weights` are sample weights >= 0 (default: ones; negative or non-finite: ErrorInputParams).  A row with weight 0 adds nothing to f, g or H.
+
+    One evaluation is two launches and ONE stream of A for all K classes, stable for every finite margin.  It runs under SpectralProjectedGradient,
+    ProjectedGradientDescent, LBFGS / ProjectedLBFGS, NonlinearCG and NewtonCG; `hess_vec_at(x, v)` gives (H(x) v, v'H(x)v) in one weights pass and
+    one product pass; `probabilities(x)` the m x K matrix P; `set_kernel` selects the kernel that streams A.  Padded K n <= 16384, K <= 256, one rank (otherwise ErrorInputParams, "not built");
+    `hessian`, `hess_vec` and `rows`: ErrorInputParams."""
+
+    def __init__(self, a, y, n_classes, mu, weights=None, ctx=None):
+        ctx = ctx or default_context()
+        a = _f64(a)
+        yf = np.asarray(y, dtype=np.float64)
+        if a.ndim != 2 or yf.ndim != 1 or a.shape[0] != yf.size:
+            raise ErrorInputParams("a must be m x n and y must have m entries")
+        m, n = a.shape
+        k = int(n_classes)
+        bad = np.flatnonzero(~((yf >= 0) & (yf < max(k, 0)) & (yf == np.floor(yf))))
+        if bad.size:
+            raise ErrorInputParams(f"multinomial: labels[{int(bad[0])}] = {yf[bad[0]]} is not an integer in [0, n_classes)")
+        lab = np.ascontiguousarray(yf, dtype=np.int32)
+        w = None if weights is None else _f64(weights)
+        if w is not None and (w.ndim != 1 or w.size != m):
+            raise ErrorInputParams(f"weights has {w.size} entries, a has {m} rows")
+        h = C.c_void_p()
+        _check(A.lib().qn_multinomial_create(ctx.h, m, n, max(k, 0), _dp(a), lab.ctypes.data_as(C.c_void_p), _dp(w) if w is not None else None, float(mu),
+                                             C.byref(h)))
+        super().__init__(ctx, h, n * k)
+        self.m, self.n_features, self.n_classes = m, n, k
+
+    def probabilities(self, x):
+        """P at x, m x K: P[i, k] = p_ik (a masked row's are zeros).  One weights pass of A."""
+        if not self.h:
+            raise ErrorInputParams("the objective is closed")
+        x = _f64(x)
+        if x.size != self.n:
+            raise ErrorInputParams(f"x has {x.size} entries, the objective has {self.n}")
+        p = np.empty((self.m, self.n_classes))
+        _check(A.lib().qn_multinomial_probabilities(self.h, _dp(x), _dp(p)))
+        return p
+
+    def set_kernel(self, kernel):
+        """Which kernel streams A: 1 the register-blocked kernel on the vector unit, 2 the MFMA kernel (K <= 64 where it is built, otherwise
+        ErrorInputParams), 0 the automatic choice.  The two sum in different orders: each is repeatable bit for bit, not equal to the other."""
+        if not self.h:
+            raise ErrorInputParams("the objective is closed")
+        _check(A.lib().qn_multinomial_set_kernel(self.h, int(kernel)))
+
+
 class SparseLogistic(Objective):
     """Regularised logistic regression on the device with a SPARSE A in CSR (m x n; the columns of a row strictly increasing) and no limit on n:
     f = sum_i w_i log(1 + exp(-y_i a_i'x)) + mu/2 ||x||^2, g = -A'(y o w o s) + mu x, H(x) v = A'(d o (A v)) + mu v.  Labels (exactly -1 / +1), `weights`

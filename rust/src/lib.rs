@@ -485,6 +485,18 @@ impl DeviceObjective {
         })?;
         Ok(DeviceObjective { h, n })
     }
+    /// Softmax regression, class-major: x[k n + j] = W[k, j], N = n_classes * n entries.  `a_rowmajor` is m x n, `labels` holds m classes in
+    /// 0 .. n_classes, `weights` (>= 0, a 0 masks its row) defaults to ones.  The objective of GpuLBFGS, GpuNonlinearCG, the spectral family and GpuNewtonCG.
+    pub fn multinomial(a_rowmajor: &[Floating], labels: &[i32], n_classes: usize, weights: Option<&DVector<Floating>>, n: usize, mu: Floating) -> Result<Self, SolverError> {
+        let m = labels.len();
+        if a_rowmajor.len() != m * n || weights.map_or(false, |w| w.len() != m) {
+            return Err(SolverError::ErrorInputParams);
+        }
+        let mut h = std::ptr::null_mut();
+        let w = weights.map_or(std::ptr::null(), |w| w.as_ptr());
+        status_to_result(unsafe { qn_multinomial_create(default_context(), m, n, n_classes, a_rowmajor.as_ptr(), labels.as_ptr() as *const c_void, w, mu, &mut h) })?;
+        Ok(DeviceObjective { h, n: n * n_classes })
+    }
     /// f = 1/2 x'Qx - b'x with a sparse Q in CSR (both triangles of a symmetric matrix; `indptr` has n + 1 entries, the columns of a row
     /// increase strictly): the large objective of the O(n) solvers (GpuSpectralProjectedGradient, GpuProjectedGradientDescent, GpuLBFGS).
     pub fn sparse_quadratic(indptr: &[i64], indices: &[i64], data: &[Floating], b: &DVector<Floating>) -> Result<Self, SolverError> {
