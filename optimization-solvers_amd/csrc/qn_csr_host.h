@@ -1,7 +1,7 @@
-// qn_csr_host.h -- pure-host CSR helpers of the sparse logistic objective (qn_host_sparse_logistic.hip.h): validation of a rows x cols pattern,
-// the int32 copy the device keeps, the transpose by a counting sort, and the static cut of the rows over workgroups.  NO HIP include and no
-// dependency on the library: tests/test_ref_sparse_logistic.py compiles it into a stand-alone program under the host sanitizers.
-// (The sparse quadratic keeps its own spq_* code in qn_host_objective.hip.h, untouched; the rules here are the same ones.)
+// qn_csr_host.h -- pure-host CSR helpers of the two sparse objectives (qn_host_sparse_logistic.hip.h; the sparse quadratic's creation in
+// qn_host_objective.hip.h, which keeps only its own validation texts): validation of a rows x cols pattern, the int32 copy the device keeps, the
+// transpose by a counting sort, and the static cut of the rows over workgroups.  NO HIP include and no dependency on the library:
+// tests/test_ref_sparse_logistic.py compiles it into a stand-alone program under the host sanitizers.
 #pragma once
 
 #include <algorithm>

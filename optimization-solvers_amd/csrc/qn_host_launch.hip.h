@@ -65,14 +65,14 @@ static QnS2GArgs s2g_args(const Run& r) {
     qn_objective* o = r.obj;
     qn_context* c = s->ctx;
     QnS2GArgs g{};
-    g.L.A = o->Q; g.L.c = o->b; g.L.mu = o->mu;
-    g.L.m = (int)o->m; g.L.m_pad = o->TA.n_pad; g.L.mrpr = o->TA.rpr; g.L.n = (int)o->n; g.L.n_pad = o->T.n_pad;
+    g.L.A = o->dn.rows; g.L.c = o->dn.rhs; g.L.mu = o->dn.mu;
+    g.L.m = (int)o->dn.m; g.L.m_pad = o->dn.TA.n_pad; g.L.mrpr = o->dn.TA.rpr; g.L.n = (int)o->n; g.L.n_pad = o->T.n_pad;
     g.L.world = c->world; g.L.rank = c->rank; g.L.rs = 1;
-    g.wgms = o->lwgms; g.wgg = o->lwgg; g.G = o->lse_G;
+    g.wgms = o->os.wgms; g.wgg = o->os.wgg; g.G = o->os.G;
     g.ctl = s->s2_ctl + (r.s2_launches & 1); // what the last prologue launch has written
     g.F = s->V.F;
     g.wgS = nullptr; g.trows = s->s2_trows;
-    g.gall = o->lgall; g.ev_slice = nullptr;
+    g.gall = o->lse.gall; g.ev_slice = nullptr;
     return g;
 }
 template <int KCH, bool NTA>
@@ -102,7 +102,7 @@ static int s2g_enqueue_onepass(Run& r) {
     hipStream_t st = s->ctx->stream;
     const QnS2GArgs g = s2g_args(r);
     ProfScope ps(s, KC_EVAL);
-    switch (r.obj->lse_kch) {
+    switch (r.obj->os.kch) {
     case 1: QNCHK(s2g_launch_onepass<1>(st, g)); break;
     case 2: QNCHK(s2g_launch_onepass<2>(st, g)); break;
     case 4: QNCHK(s2g_launch_onepass<4>(st, g)); break;
@@ -321,7 +321,7 @@ static int s2_do_vec(Run& r) {
         {
             ProfScope ps(s, KC_COMM);
             c->n_xchg_vector++;
-            if (r.gobj) QNCHK(exchange(c, r.obj->lgall, (size_t)s->T.n_pad)); // the ranks' G_r of the accepted point (weighed and added in rank order by s2g_vec_kernel)
+            if (r.gobj) QNCHK(exchange(c, r.obj->lse.gall, (size_t)s->T.n_pad)); // the ranks' G_r of the accepted point (weighed and added in rank order by s2g_vec_kernel)
             else QNCHK(xchg_sum_or_gather(c, s->symsh_xg, (size_t)s->T.n_pad));
         }
         return s2_launch(r, QN_S2_VEC);
@@ -502,11 +502,11 @@ static int enqueue_eval_fused(Run& r, int after_h) {
     qn_solver* s = r.s;
     qn_context* c = s->ctx;
     QnEvalFusedArgs a{};
-    a.Q = r.obj->Q; a.T = s->T; a.T.cs = 1; a.F = s->V.F; a.ctl = s->ctl; a.expect_phase = QN_PH_REQ_EVAL;
+    a.Q = r.obj->dn.rows; a.T = s->T; a.T.cs = 1; a.F = s->V.F; a.ctl = s->ctl; a.expect_phase = QN_PH_REQ_EVAL;
     a.after_h = after_h; a.world = c->world;
     if (r.sym) {
         QnSymEvalArgs y{};
-        y.Q = r.obj->Q; y.T = a.T; y.F = a.F; y.ctl = s->ctl; y.expect_phase = QN_PH_REQ_EVAL; y.after_h = after_h; y.nb = s->sym_nb; y.part = s->sym_part;
+        y.Q = r.obj->dn.rows; y.T = a.T; y.F = a.F; y.ctl = s->ctl; y.expect_phase = QN_PH_REQ_EVAL; y.after_h = after_h; y.nb = s->sym_nb; y.part = s->sym_part;
         y.nt = 0; // Q is only read: non-temporal loads measured no gain at n = 32768 and -4 % at n = 16384
         if (c->world > 1) { // row-sharded: this rank's circulant half, partial sums gathered, epilogue on every rank
             y.sh = sym_shard(s);
@@ -619,7 +619,7 @@ static int enqueue_eval(Run& r, int after_h = 0) {
     if (r.fused) return enqueue_eval_fused(r, after_h);
     if (r.oracle_tpl == QN_ORACLE_QUAD) {
         QnQuadArgs a{};
-        a.Q = r.obj->Q; a.T = s->T; a.T.cs = s->qcs;
+        a.Q = r.obj->dn.rows; a.T = s->T; a.T.cs = s->qcs;
         a.x = s->V.x; a.d = s->V.d; a.xt = s->V.xt;
         a.llb = s->V.llb; a.lub = s->V.lub;
         a.out = s->V.q + (size_t)c->rank * s->qcs * s->T.rpr;

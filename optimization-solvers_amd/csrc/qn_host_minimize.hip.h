@@ -44,7 +44,7 @@ static int plan_run(Run& r, qn_solver* s, qn_linesearch* ls, const qn_oracle* o,
     }
     if (s->method == QN_NEWTON) {
         if (c->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "Newton is single-GPU (SURVEY.md 8(f) row f2)");
-        if (!(r.obj && (r.obj->kind == OBJ_QUADRATIC || r.obj->kind == OBJ_LOGSUMEXP)) && !(o->kind == QN_ORACLE_HOST && o->host_hessian_fn))
+        if (!(r.obj && !r.obj->ops->no_hessian) && !(o->kind == QN_ORACLE_HOST && o->host_hessian_fn))
             return fail(QN_ERROR_INPUT_PARAMS, "Hessian not available in the oracle"); // newton/mod.rs:34 .expect(...)
         QNCHK(newton_alloc(s));
     }
@@ -83,7 +83,7 @@ static int plan_run(Run& r, qn_solver* s, qn_linesearch* ls, const qn_oracle* o,
     // holds (one rank, whole 128-blocks without padding, a symmetric Q, bitwise symmetric H) -- s2_dir_kernel, qn_sym2.hip.h; BackTrackingB's
     // projected trial points by s2_proj_kernel (round 6).  Everything else bounded keeps the generic path.  QN_S2_BND=0 switches it off (tests: generic path).
     const bool s2bnd_off = getenv("QN_S2_BND") && atoi(getenv("QN_S2_BND")) == 0;
-    const bool s2_struct = !ls_only && s2_shape && r.obj && r.obj->q_symmetric && !s->no_s2bnd && !s2bnd_off;
+    const bool s2_struct = !ls_only && s2_shape && r.obj && r.obj->quad.symmetric && !s->no_s2bnd && !s2bnd_off;
     const bool s2b = (s->bounded || ls_bounded) && s2_struct;
     // SR1 (sr1_b.rs; row f4) has its three-term update only in the second-generation kernels (s2_hpass_kernel<.., SR1>): it takes the fused path
     // exactly when that path will be taken -- the same structural conditions as the bounded variants'.
@@ -93,13 +93,13 @@ static int plan_run(Run& r, qn_solver* s, qn_linesearch* ls, const qn_oracle* o,
     // ... and the log-sum-exp objective in the structure of the second-generation path (qn_sym2g.hip.h; round 5): its one-pass evaluation
     // (n <= 16384), whole 128-blocks without padding, a bitwise symmetric H; one rank, or row-sharded over an exchange that is there.  Everything
     // else keeps the generic path.
-    r.gobj = r.obj && r.obj->kind == OBJ_LOGSUMEXP && r.obj->lse_kch && !r.obj->lse_two_pass && h->memoize && (s->method == QN_BFGS || s->method == QN_DFP) &&
+    r.gobj = r.obj && r.obj->kind == OBJ_LOGSUMEXP && r.obj->os.kch && !r.obj->lse.two_pass && h->memoize && (s->method == QN_BFGS || s->method == QN_DFP) &&
              !callback && s->hcs == 1 && !h->small_n && !s->no_fused && !s->bounded && !ls_bounded && !ls_only &&
              (s2_shape || (s2sh_shape && (c->comm || c->host_xchg || c->host_async))) && !(getenv("QN_S2G") && atoi(getenv("QN_S2G")) == 0);
     if (r.gobj) r.fused = true;
     h->fused = r.fused ? 1 : 0;
     s->V.fused_hint = h->fused;
-    r.sym = r.fused && (sym_ok || symsh_ok) && r.obj && (r.obj->q_symmetric || r.gobj);
+    r.sym = r.fused && (sym_ok || symsh_ok) && r.obj && (r.obj->quad.symmetric || r.gobj);
     // the generic path's H pass alone (closures, log-sum-exp objective, SR1, bounded variants): same tiles, sums into V.hp
     r.sym_generic = !r.fused && (sym_ok || symsh_ok) && s->H && s->hcs == 1 && (s->method == QN_BFGS || s->method == QN_DFP || s->method == QN_SR1);
     // Broyden's H is not symmetric after its first update: none of the predicates above admits the method (fused, gobj, sym, sym_generic, and sym2
@@ -154,7 +154,7 @@ static int plan_run(Run& r, qn_solver* s, qn_linesearch* ls, const qn_oracle* o,
         QNCHK(solver_alloc_fused(s, r.sym));
         s->V.F.pworld = r.sym ? 1 : c->world; // symmetric storage: every rank forms all the per-block partial sums itself
         if (r.sym && c->world > 1) QNCHK(s->symsh_xg.ensure((size_t)c->world * 2 * s->T.n_pad, c->stream));
-        s->V.F.b = r.gobj ? nullptr : r.obj->b; // (the quadratic's linear term; the log-sum-exp path's kernels do not read it)
+        s->V.F.b = r.gobj ? nullptr : r.obj->dn.rhs; // (the quadratic's linear term; the log-sum-exp path's kernels do not read it)
         if (!s->fused_live) { // import the canonical state (x, pending s and u) into the fused buffers
             const size_t vb = (size_t)s->T.n_pad * sizeof(double);
             HIPCHK(hipMemcpyAsync(s->V.F.X0, s->V.x, vb, hipMemcpyDeviceToDevice, c->stream));
@@ -201,11 +201,11 @@ static int plan_s2_args(Run& r) {
     qn_context* c = s->ctx;
     QNCHK(solver_alloc_sym2(s));
     QnS2Args& a = r.s2;
-    a.Q = r.obj->Q; a.H = s->H; a.n = (int)s->n; a.np = s->T.n_pad; a.nb = s->s2_nb; a.G = s->s2_G;
+    a.Q = r.obj->dn.rows; a.H = s->H; a.n = (int)s->n; a.np = s->T.n_pad; a.nb = s->s2_nb; a.G = s->s2_G;
     a.item_ij = s->s2_items; a.maxk = s->s2_maxk; a.inorder = s->s2_inorder; a.F = s->V.F; a.part = s->sym_part;
     a.wgS = s->s2_wgS; a.trows = s->s2_trows; a.ctl2 = s->s2_ctl; a.partE = s->s2_partE;
     a.gw = r.gobj ? s->T.n_pad / 64 : 0;
-    a.gmu = r.gobj ? r.obj->mu : 0.0;
+    a.gmu = r.gobj ? r.obj->dn.mu : 0.0;
     // (allocated only for the runs that use them: the tail reduce's counters, the sharded log-sum-exp path's weights)
     if (r.gobj && c->world > 1) QNCHK(s->s2_gws.ensure(80, c->stream)); // the ranks' weights and S, world <= 64
     a.gws = s->s2_gws;
@@ -502,8 +502,7 @@ static void finish_stats(Run& r) {
                                                              //  what the roofline fractions are quoted against; h_bytes_moved below is what went over the fabric)
     s->stats.h_bytes_moved = s->stats.h_bytes - h->n_hpass_nostore * shard; // (a pass that did not store moved its tiles once: s2_hpass_kernel's read pass)
     s->stats.obj_bytes = (r.oracle_tpl == QN_ORACLE_QUAD) ? h->n_oracle_evals * (r.sym ? shard : full_shard) : 0;
-    if (r.obj && r.obj->kind == OBJ_LOGSUMEXP) // one pass over this rank's rows of A per evaluation (two for n > 16384)
-        s->stats.obj_bytes = h->n_oracle_evals * (uint64_t)r.obj->TA.rpr * (uint64_t)r.obj->T.n_pad * 8ull * ((r.obj->lse_kch && !r.obj->lse_two_pass) ? 1ull : 2ull);
+    if (r.obj && r.oracle_tpl != QN_ORACLE_QUAD) s->stats.obj_bytes = h->n_oracle_evals * r.obj->ops->eval_bytes(r.obj); // (the quadratic's depend on the tiles above)
     s->stats.matrix_bytes_per_pass = shard;
     stats_add_totals(s);
     s->stats.total_xchg_vector += c->n_xchg_vector - r.xv0;
@@ -525,14 +524,9 @@ static int minimize_impl(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, si
     r.ls = ls; r.callback = callback; r.callback_user = callback_user; r.ls_only = ls_only;
     r.xv0 = c->n_xchg_vector; r.xs0 = c->n_xchg_scalar;
     QNCHK(check_oracle(c, s->n, o, &r.obj));
-    if (r.obj && r.obj->kind == OBJ_QUADRATIC) { r.oracle_tpl = QN_ORACLE_QUAD; s->V.b = r.obj->b; }
-    else if (r.obj && r.obj->kind == OBJ_LOGISTIC)
-        return fail(QN_ERROR_INPUT_PARAMS, "a Logistic objective runs under SPG, projected gradient, LBFGS / ProjectedLBFGS, NonlinearCG and NewtonCG (the dense quasi-Newton family, the control-step solvers and Newton: out of scope)");
-    else if (r.obj && r.obj->kind == OBJ_SPARSE_LOGISTIC)
-        return fail(QN_ERROR_INPUT_PARAMS, "a SparseLogistic objective runs under SPG, projected gradient, LBFGS / ProjectedLBFGS, NonlinearCG and NewtonCG (the dense quasi-Newton family, the control-step solvers and Newton: out of scope)");
-    else if (r.obj && r.obj->kind == OBJ_MULTINOMIAL)
-        return fail(QN_ERROR_INPUT_PARAMS, "a Multinomial objective runs under SPG, projected gradient, LBFGS / ProjectedLBFGS, NonlinearCG and NewtonCG (the dense quasi-Newton family, the control-step solvers and Newton: out of scope)");
-    else if (r.obj && r.obj->kind != OBJ_LOGSUMEXP) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective"); // (log-sum-exp: evaluated by its own kernels into (f_dev, gt))
+    if (r.obj && r.obj->kind == OBJ_QUADRATIC) { r.oracle_tpl = QN_ORACLE_QUAD; s->V.b = r.obj->dn.rhs; }
+    else if (r.obj && r.obj->ops->no_dense_family) return fail(QN_ERROR_INPUT_PARAMS, r.obj->ops->no_dense_family);
+    // (everything else -- log-sum-exp -- is evaluated by its own kernels into (f_dev, gt))
     QNCHK(plan_run(r, s, ls, o, max_iter_solver, max_iter_line_search, ls_f0));
     if (r.sym2) QNCHK(plan_s2_args(r));
     else QNCHK(poke_ctl(s));

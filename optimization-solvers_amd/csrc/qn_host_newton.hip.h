@@ -387,13 +387,13 @@ static int newton_stage_hessian(qn_solver* s, const qn_oracle* o, qn_objective* 
     const double* hsrc = nullptr;
     size_t ld_src = 0;
     bool symmetric = true; // the Cholesky path reads the lower triangle only: it needs H == H' bit for bit
-    if (obj && obj->kind == OBJ_LOGSUMEXP) { // (the mirrored store of lse_hess_kernel: symmetric by construction)
+    if (obj && obj->ops->hessian) { // formed at x_k (log-sum-exp: the mirrored store of lse_hess_kernel, symmetric by construction)
         const size_t np = (size_t)obj->T.n_pad;
         QNCHK(s->newton_hsrc.ensure(np * np));
-        QNCHK(lse_enqueue_hessian(obj, s->V.x, s->newton_hsrc, np));
-        s->stats.launches += 5;
+        QNCHK(obj->ops->hessian(obj, s->V.x, s->newton_hsrc, np));
+        s->stats.launches += obj->ops->hessian_launches;
         hsrc = s->newton_hsrc; ld_src = np;
-    } else if (obj) { hsrc = obj->Q; ld_src = (size_t)obj->T.n_pad; symmetric = obj->q_symmetric; }
+    } else if (obj) { hsrc = obj->dn.rows; ld_src = (size_t)obj->T.n_pad; symmetric = obj->quad.symmetric; }
     else {
         QNCHK(s->newton_hsrc.ensure((size_t)n * n));
         s->newton_hhost.resize((size_t)n * n * 2);

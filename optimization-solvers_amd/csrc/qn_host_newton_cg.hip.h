@@ -43,15 +43,13 @@ extern "C" int qn_solver_newton_cg_state(qn_solver* s, size_t* inner_last, size_
 static int tn_check(const qn_solver* s, const qn_linesearch* ls, const qn_objective* obj, int ls_only) {
     if (ls_only) return fail(QN_ERROR_INPUT_PARAMS, "compute_step_len runs on a first-order solver");
     if (!obj) return fail(QN_ERROR_INPUT_PARAMS, "NewtonCG needs a device LogSumExp or Logistic / SparseLogistic / Multinomial objective: a closure has no Hessian-vector product");
-    if (obj->kind != OBJ_LOGSUMEXP && obj->kind != OBJ_LOGISTIC && obj->kind != OBJ_SPARSE_LOGISTIC && obj->kind != OBJ_MULTINOMIAL)
+    if (!obj->ops->hess_vec)
         return fail(QN_ERROR_INPUT_PARAMS, "NewtonCG runs on a LogSumExp or Logistic / SparseLogistic / Multinomial objective only: on a quadratic the method is linear conjugate gradients, which NonlinearCG with ExactQuadratic already is");
     if (ls->kind != QN_LS_BACKTRACKING && ls->kind != QN_LS_STRONG_WOLFE)
         return fail(QN_ERROR_INPUT_PARAMS, "NewtonCG takes BackTracking or StrongWolfe (GLLQuadratic, BackTrackingB, ExactQuadratic, NoSearch and More-Thuente: out of scope)");
     if (ls->lower_bound_host || ls->upper_bound_host) return fail(QN_ERROR_INPUT_PARAMS, "NewtonCG is unbounded only: StrongWolfe's box is out of scope");
     if (s->bounded) return fail(QN_ERROR_INPUT_PARAMS, "NewtonCG is unbounded only");
-    if (obj->kind == OBJ_MULTINOMIAL) return QN_OK; // (N_pad <= 16384 and one rank were checked at creation)
-    if (obj->kind == OBJ_SPARSE_LOGISTIC) return QN_OK; // (its product has kernels of its own: no n_pad limit; one rank was checked at creation)
-    return lse_hv_built(obj); // n_pad <= 16384, one rank: "not built" otherwise
+    return obj->ops->hv_built ? obj->ops->hv_built(obj) : QN_OK; // (log-sum-exp, logistic: n_pad <= 16384, one rank -- "not built" otherwise)
 }
 
 // phase QN_VP_NSOLVE.  fresh: behind the loop top's own two launches, in the batch that saw it pass -- the weights at x, init, start; then (and in
@@ -63,22 +61,16 @@ static int tn_enqueue_direction(VecRun& r, bool fresh, uint64_t* weights_passes)
     const size_t np = s->T.n_pad;
     QnTnArgs t{};
     t.r = s->tn_block; t.p = s->tn_block + np; t.q = s->tn_block + 2 * np; t.gbar = s->tn_block + 3 * np; t.tpart = s->tn_block + 4 * np;
-    const bool logit = r.obj->kind == OBJ_LOGISTIC; // H = A' diag(d) A + mu I: the product's kernels with pw = d and zeros where gbar goes
-    const bool slog = r.obj->kind == OBJ_SPARSE_LOGISTIC; // the same H on two CSR copies: kernels of its own, v'Hv folded into one value (kcount = 1)
-    const bool mnl = r.obj->kind == OBJ_MULTINOMIAL; // H on the flat class-major vector: its own stream in product mode, the same combine with zeros where gbar goes
-    t.gbar_src = (logit || slog || mnl) ? r.obj->lzero : r.obj->lgall; t.kcount = slog ? 1 : (int)((np + 63) / 64);
-    if (!slog) QNCHK(r.obj->lhv_shares.ensure(257, st));
-    t.kshares = slog ? (const double*)(r.obj->lscal + 1) : (const double*)r.obj->lhv_shares;
+    const QnObjOps* ops = r.obj->ops;
+    QnHvOut vhv{};
+    QNCHK(ops->hv_out(r.obj, &vhv)); // the shares of v'Hv that tn_step_kernel adds, or the one value a kind folds itself
+    t.gbar_src = ops->gbar(r.obj); t.kcount = vhv.count; t.kshares = vhv.shares;
     const dim3 one(1), wide(r.a.G), tpb(QN_VEC_TPB);
     if (fresh) {
         {
             ProfScope ps(s, KC_EREDUCE); // (a class of its own: two passes of A, twice an evaluation's time, would upset t_eval_ms's floor rule)
-            QnLseArgs la{};
-            if (logit) QNCHK(logit_enqueue_weights(r.obj, s->V.x)); // ONE pass of A: d is known row by row the moment the margin is
-            else if (mnl) QNCHK(mnl_enqueue_weights(r.obj, s->V.x)); // ONE pass of A: the evaluation into scratch, P into `mn_P`
-            else if (slog) QNCHK(slog_enqueue_weights(r.obj, s->V.x)); // one evaluation's three launches into scratch, d into `lw`
-            else QNCHK(lse_enqueue_weights(r.obj, s->V.x, la));
-            s->stats.launches += (logit || mnl) ? 2 : slog ? 3 : 4;
+            QNCHK(ops->weights(r.obj, s->V.x)); // unpredicated: it writes the objective's scratch only
+            s->stats.launches += ops->weights_launches;
             ++*weights_passes;
         }
         { ProfScope ps(s, KC_HPASS); hipLaunchKernelGGL(tn_init_kernel, wide, tpb, 0, st, r.a, t); }
@@ -88,23 +80,14 @@ static int tn_enqueue_direction(VecRun& r, bool fresh, uint64_t* weights_passes)
     }
     const int chunk = s->hvctl->tn_chunk;
     for (int i = 0; i < chunk; ++i) {
-        if (slog) { // rows(product), cols(product), then the fold of up to SPQ_MAXG + n_long shares that tn_step_kernel reads as one
-            { ProfScope ps(s, KC_NEWTON); QNCHK(slog_enqueue_hess_vec(r.obj, t.p, t.q, s->vctl, 1)); }
-            { ProfScope ps(s, KC_CTL); QNCHK(slog_enqueue_hess_vec(r.obj, t.p, t.q, s->vctl, 2)); }
-            s->stats.launches += 1;
-        } else if (mnl) {
-            { ProfScope ps(s, KC_NEWTON); QNCHK(mnl_enqueue_hess_vec(r.obj, t.p, t.q, s->vctl, 1)); }
-            { ProfScope ps(s, KC_NEWTON); QNCHK(mnl_enqueue_hess_vec(r.obj, t.p, t.q, s->vctl, 2)); }
-        } else {
-            { ProfScope ps(s, KC_NEWTON); QNCHK(lse_enqueue_hess_vec(r.obj, t.p, t.gbar, t.q, s->vctl, 1)); }
-            { ProfScope ps(s, KC_NEWTON); QNCHK(lse_enqueue_hess_vec(r.obj, t.p, t.gbar, t.q, s->vctl, 2)); }
-        }
+        { ProfScope ps(s, KC_NEWTON); QNCHK(ops->hess_vec(r.obj, t.p, t.gbar, t.q, s->vctl, 1)); }
+        { ProfScope ps(s, ops->hv_fold_ctl ? KC_CTL : KC_NEWTON); QNCHK(ops->hess_vec(r.obj, t.p, t.gbar, t.q, s->vctl, 2)); }
         { ProfScope ps(s, KC_CTL); hipLaunchKernelGGL(tn_step_kernel, one, tpb, 0, st, r.a, t); }
         { ProfScope ps(s, KC_HPASS); hipLaunchKernelGGL(tn_update_kernel, wide, tpb, 0, st, r.a, t); }
         { ProfScope ps(s, KC_CTL); hipLaunchKernelGGL(tn_commit_kernel, one, tpb, 0, st, r.a, t); }
         { ProfScope ps(s, KC_HPASS); hipLaunchKernelGGL(tn_next_kernel, wide, tpb, 0, st, r.a, t); }
         HIPCHK(hipGetLastError());
-        s->stats.launches += 6;
+        s->stats.launches += 4 + ops->hv_launches;
     }
     { ProfScope ps(s, KC_HPASS); hipLaunchKernelGGL(tn_dir_kernel, wide, tpb, 0, st, r.a); }
     { ProfScope ps(s, KC_CTL); hipLaunchKernelGGL(tn_top_kernel, one, tpb, 0, st, r.a); }

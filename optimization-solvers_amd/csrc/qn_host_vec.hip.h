@@ -137,34 +137,17 @@ static int vec_enqueue_eval(VecRun& r) {
     qn_solver* s = r.s;
     qn_context* c = s->ctx;
     hipStream_t st = c->stream;
-    if (r.obj && r.obj->kind == OBJ_SPARSE_QUADRATIC) {
-        // the CSR product with g and f's shares out of the same launch, then the shares' sum (qn_sparse.hip.h).  Profiling mode times the two apart:
-        // t_eval_ms is spq_eval_kernel alone (what tools/bench_sparse.py reports), the finish counts under t_ctl_ms
-        { ProfScope ps(s, KC_EVAL); QNCHK(spq_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt, 1)); }
-        { ProfScope ps(s, KC_CTL); QNCHK(spq_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt, 2)); }
-        s->stats.launches += 2;
-        return QN_OK;
-    }
-    if (r.obj && r.obj->kind == OBJ_LOGISTIC) {
-        // the stream of A, then the combine (qn_logistic.hip.h), timed apart as above.  d goes to the trial buffer: `lw` keeps NewtonCG's weights at x_k
-        { ProfScope ps(s, KC_EVAL); QNCHK(logit_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt, r.obj->lw_trial, 1)); }
-        { ProfScope ps(s, KC_CTL); QNCHK(logit_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt, r.obj->lw_trial, 2)); }
-        s->stats.launches += 2;
-        return QN_OK;
-    }
-    if (r.obj && r.obj->kind == OBJ_SPARSE_LOGISTIC) {
-        // the row pass and the column pass, then the finish (qn_sparse_logistic.hip.h), timed apart as above.  d goes to the trial buffer, as the logistic's
-        { ProfScope ps(s, KC_EVAL); QNCHK(slog_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt, r.obj->lw_trial, 1)); }
-        { ProfScope ps(s, KC_CTL); QNCHK(slog_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt, r.obj->lw_trial, 2)); }
-        s->stats.launches += 3;
-        return QN_OK;
-    }
-    if (r.obj && r.obj->kind == OBJ_MULTINOMIAL) {
-        // the stream of A for all classes, then the logistic's combine on the flat vector (qn_multinomial.hip.h), timed apart as above.  P goes to the
-        // trial buffer: `mn_P` keeps NewtonCG's weights at x_k
-        { ProfScope ps(s, KC_EVAL); QNCHK(mnl_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt, r.obj->mn_P_trial, 1)); }
-        { ProfScope ps(s, KC_CTL); QNCHK(mnl_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt, r.obj->mn_P_trial, 2)); }
-        s->stats.launches += 2;
+    if (r.obj) { // a device objective: its table's launches.  d or P goes to the kind's trial buffer (the weights at x_k stay NewtonCG's)
+        const QnObjOps* ops = r.obj->ops;
+        const QnObjWork w{s->V.q, s->V.s}; // the dense quadratic's (row-block 0 stores its copy of the point: V.s is free here)
+        if (ops->eval_split) { // the streaming launches, then the finish: profiling mode times the two apart, t_eval_ms is the stream alone
+            { ProfScope ps(s, KC_EVAL); QNCHK(ops->eval(r.obj, s->V.xt, s->f_dev, s->V.gt, 1, &w)); }
+            { ProfScope ps(s, KC_CTL); QNCHK(ops->eval(r.obj, s->V.xt, s->f_dev, s->V.gt, 2, &w)); }
+        } else {
+            ProfScope ps(s, KC_EVAL);
+            QNCHK(ops->eval(r.obj, s->V.xt, s->f_dev, s->V.gt, 3, &w));
+        }
+        if (ops->vec_counted) s->stats.launches += ops->eval_launches;
         return QN_OK;
     }
     ProfScope ps(s, KC_EVAL);
@@ -181,18 +164,7 @@ static int vec_enqueue_eval(VecRun& r) {
             return fail(QN_ABNORMAL_TERMINATION, "device oracle returned non-zero");
         return QN_OK;
     }
-    if (r.obj->kind == OBJ_LOGSUMEXP) return lse_enqueue_eval(r.obj, s->V.xt, s->f_dev, s->V.gt);
-    // quadratic: the unconditional launches of qn_objective_eval -- Q xt by the row kernel, then f and g = Q xt - b
-    QnQuadArgs q{};
-    q.Q = r.obj->Q; q.T = r.obj->T; q.T.cs = 1; q.x = s->V.xt; q.d = s->V.xt; q.xt = s->V.s; // (row-block 0 stores its copy of the point: V.s is free here)
-    q.out = s->V.q; q.ctl = nullptr; q.expect_phase = -1; q.force_kind = QN_REQ_X; q.force_t = 0.0;
-    QNCHK(launch_quad_R(8, st, q));
-    QnVecs V{};
-    V.q = s->V.q; V.xt = s->V.xt; V.b = r.obj->b; V.n = (int)s->n; V.n_pad = s->T.n_pad; V.rpr = s->T.rpr; V.world = 1; V.qcs = 1; V.hcs = 1;
-    hipLaunchKernelGGL(quad_finish_kernel, dim3(1), dim3(QN_CTL_TPB), 0, st, V, s->f_dev, s->V.gt);
-    HIPCHK(hipGetLastError());
-    s->stats.launches += 2;
-    return QN_OK;
+    return fail(QN_ERROR_INPUT_PARAMS, "unknown oracle kind");
 }
 
 // ProjectedNewton / SpectralProjectedNewton, phase QN_VP_NSOLVE: z = H^-1 g into V.y -- `hessian.cholesky().unwrap().solve(eval.g())`
@@ -261,15 +233,12 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     const bool pn = pn_method(s->method), lbfgs = s->method == QN_LBFGS, cg = s->method == QN_NONLINEAR_CG, tn = s->method == QN_NEWTON_CG;
     VecRun r{s, o, nullptr, {}};
     QNCHK(check_oracle(c, s->n, o, &r.obj));
-    if (r.obj && r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_LOGSUMEXP && r.obj->kind != OBJ_SPARSE_QUADRATIC && r.obj->kind != OBJ_LOGISTIC &&
-        r.obj->kind != OBJ_SPARSE_LOGISTIC && r.obj->kind != OBJ_MULTINOMIAL)
-        return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
     if (tn) QNCHK(tn_check(s, ls, r.obj, ls_only)); // unbounded, log-sum-exp, BackTracking or StrongWolfe without a box
     const bool exact = ls->kind == QN_LS_EXACT_QUADRATIC;
     if (exact) { // the exact step -g.d / d'Qd: a device quadratic under the four O(n) methods (qn_vec_exact.hip.h)
         if (pn) return fail(QN_ERROR_INPUT_PARAMS, "ExactQuadratic is not built for the projected Newton pair: it runs under SPG, projected gradient, L-BFGS and NonlinearCG");
         if (ls_only) return fail(QN_ERROR_INPUT_PARAMS, "ExactQuadratic: compute_step_len on its own is not built: use qn_minimize");
-        if (!r.obj || (r.obj->kind != OBJ_QUADRATIC && r.obj->kind != OBJ_SPARSE_QUADRATIC))
+        if (!r.obj || !r.obj->ops->curvature)
             return fail(QN_ERROR_INPUT_PARAMS, "ExactQuadratic: the exact step needs a device quadratic (Quadratic or SparseQuadratic), not a closure or log-sum-exp");
         if (ls->lower_bound_host || ls->upper_bound_host)
             return fail(QN_ERROR_INPUT_PARAMS, "ExactQuadratic holds no box of its own: lower_bound_host / upper_bound_host must not be set (the solver's box caps the step at 1)");
@@ -299,7 +268,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         return fail(QN_ERROR_INPUT_PARAMS, "GLLQuadratic: the look-back m must be 1 .. 64 (the history is a fixed device ring)");
     if (pn) {
         if (ls_only) return fail(QN_ERROR_INPUT_PARAMS, "compute_step_len runs on a first-order solver");
-        if (!(r.obj && r.obj->kind == OBJ_QUADRATIC) && !(o->kind == QN_ORACLE_HOST && o->host_hessian_fn))
+        if (!(r.obj && !r.obj->ops->no_hessian && !r.obj->ops->hessian) && !(o->kind == QN_ORACLE_HOST && o->host_hessian_fn)) // (a device quadratic: its matrix is the Hessian)
             return fail(QN_ERROR_INPUT_PARAMS, "Hessian not available in the oracle"); // projected_newton.rs:73, spn.rs:85 .expect(...)
     }
     QNCHK(vec_state_alloc(s));
@@ -366,22 +335,12 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         s->stats.oracle_evals = h->n_evals;
         s->stats.h_passes = 0; s->stats.h_bytes = 0; s->stats.matrix_bytes_per_pass = 0;
         s->stats.obj_bytes = 0;
-        if (r.obj && r.obj->kind == OBJ_QUADRATIC) s->stats.obj_bytes = h->n_evals * (uint64_t)r.obj->T.rpr * (uint64_t)r.obj->T.n_pad * 8ull;
-        if (r.obj && r.obj->kind == OBJ_SPARSE_QUADRATIC) // values + columns, the row offsets, and x, b, g of one evaluation
-            s->stats.obj_bytes = h->n_evals * (12ull * (uint64_t)r.obj->sp_nnz + 4ull * ((uint64_t)s->n + 1) + 24ull * (uint64_t)s->n);
-        if (exact && r.obj->kind == OBJ_QUADRATIC) s->stats.obj_bytes += h->ex_passes * (uint64_t)r.obj->T.rpr * (uint64_t)r.obj->T.n_pad * 8ull;
-        if (exact && r.obj->kind == OBJ_SPARSE_QUADRATIC) // a curvature pass: values + columns, the row offsets, d and q -- no b
-            s->stats.obj_bytes += h->ex_passes * (12ull * (uint64_t)r.obj->sp_nnz + 4ull * ((uint64_t)s->n + 1) + 16ull * (uint64_t)s->n);
-        if (r.obj && r.obj->kind == OBJ_LOGISTIC) // one stream of A per evaluation
-            s->stats.obj_bytes = h->n_evals * (uint64_t)r.obj->m * (uint64_t)r.obj->T.n_pad * 8ull;
-        if (r.obj && r.obj->kind == OBJ_SPARSE_LOGISTIC) { // both CSR copies per evaluation, per product and per weights pass (slog_eval_bytes)
-            s->stats.obj_bytes = h->n_evals * slog_eval_bytes(r.obj);
-            if (tn) s->stats.obj_bytes += (uint64_t)h->tn_hv_passes * slog_product_bytes(r.obj) + tn_weights * slog_eval_bytes(r.obj);
-        } else if (r.obj && r.obj->kind == OBJ_MULTINOMIAL) { // A once, P once (written or read), the workgroups' shares: per evaluation, product and weights pass
-            const uint64_t one = 8ull * ((uint64_t)r.obj->m * ((uint64_t)r.obj->mn_nfp + (uint64_t)r.obj->mn_k) + (uint64_t)r.obj->lse_G * (uint64_t)r.obj->T.n_pad);
-            s->stats.obj_bytes = (h->n_evals + (tn ? (uint64_t)h->tn_hv_passes + tn_weights : 0ull)) * one;
-        } else if (tn) // a product streams A once (8 m n_pad), the weights at x_k twice (16 m n_pad) for log-sum-exp, once for the logistic objective
-            s->stats.obj_bytes += ((uint64_t)h->tn_hv_passes + (r.obj->kind == OBJ_LOGISTIC ? 1ull : 2ull) * tn_weights) * (uint64_t)r.obj->m * (uint64_t)r.obj->T.n_pad * 8ull;
+        if (r.obj) { // the kind's byte models: evaluations, ExactQuadratic's curvature passes, NewtonCG's products and weights passes
+            const QnObjOps* ops = r.obj->ops;
+            if (ops->vec_counted) s->stats.obj_bytes += h->n_evals * ops->eval_bytes(r.obj);
+            if (exact) s->stats.obj_bytes += h->ex_passes * ops->curv_bytes(r.obj);
+            if (tn) s->stats.obj_bytes += (uint64_t)h->tn_hv_passes * ops->hv_bytes(r.obj) + tn_weights * ops->weights_bytes(r.obj);
+        }
         stats_add_totals(s); // (no update passes, one rank: total_h_* and total_xchg_* stay)
         s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u) | (lbfgs ? QN_PATH_LBFGS : 0u) | (cg ? QN_PATH_CG : 0u) | (exact ? QN_PATH_EXACT : 0u) | (tn ? QN_PATH_NEWTON_CG : 0u);
         if (s->method == QN_PROJECTED_NEWTON) { // s_norm() / y_norm() (projected_newton.rs:10-11) through the getters every solver answers

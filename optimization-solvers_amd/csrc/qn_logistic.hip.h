@@ -6,7 +6,7 @@
 // The device keeps yw_i = y_i w_i (the objective's `b`, m_pad entries, zero past m): the sign is the label, the magnitude the weight, and a row with
 // yw_i = 0 is masked -- it adds nothing to f, g or H wherever it falls in the cut of the rows over workgroups (log-sum-exp's c_i = -inf).
 //
-//   logit_onepass_kernel<KCH, NTA>    lse_hv_onepass_kernel's sibling (qn_lse_hv.hip.h): its geometry (512 threads, the same row cut over lse_G
+//   logit_onepass_kernel<KCH, NTA>    lse_hv_onepass_kernel's sibling (qn_lse_hv.hip.h): its geometry (512 threads, the same row cut over os.G
 //                                     workgroups), x staged in LDS, each thread's KCH x 2 columns of the current row, of the prefetched row and of G
 //                                     in registers, predicated loads past n_pad, ONE barrier per row for u_r = a_r . x in lse_onepass_kernel's order
 //                                     (FMA chain per thread, wave butterfly, eight partials added in index order), the same non-temporal rule for A.

@@ -3,7 +3,7 @@
 //   H(x) = A' diag(p) A - gbar gbar' + mu I,   p = softmax(A x + c),   gbar = A' p.
 //
 // p and gbar come from the launches of the two-pass evaluation (lse_enqueue_hessian, qn_host_objective.hip.h): z = A x, the
-// single-workgroup softmax that leaves the NORMALISED weights in `lw` (zero past row m), the column sums and their fixed-order fold.
+// single-workgroup softmax that leaves the NORMALISED weights in `wp.w` (zero past row m), the column sums and their fixed-order fold.
 // What is new here is the one dense contraction the library lacked:
 //
 //   lse_hess_kernel<R, KC>   C = sum_k p_k a_k a_k' on the lower block triangle with v_mfma_f64_16x16x4_f64, then, in the same launch,

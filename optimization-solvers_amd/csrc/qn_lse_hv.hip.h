@@ -3,9 +3,9 @@
 //     H v = A'(p o (A v)) - gbar (p . (A v)) + mu v,      p = softmax(A x + c),  gbar = A'p
 //
 // ONE stream of A (8 m n bytes, what one evaluation moves) where the dense Hessian (qn_lse_hess.hip.h) costs O(m n^2) flops and 8 n^2 bytes.
-// p and gbar are what lse_enqueue_weights leaves in `lw` and `lgall` at x (two passes of A, once per point x; any number of products follow).
+// p and gbar are what lse_enqueue_weights leaves in `wp.w` and `lse.gall` at x (two passes of A, once per point x; any number of products follow).
 //
-//   lse_hv_onepass_kernel<KCH, NTA>   lse_onepass_kernel's sibling (qn_kernels.hip.h): its geometry (512 threads, the same row cut over lse_G
+//   lse_hv_onepass_kernel<KCH, NTA>   lse_onepass_kernel's sibling (qn_kernels.hip.h): its geometry (512 threads, the same row cut over os.G
 //                                     workgroups), v staged in LDS where that kernel stages x, each thread's KCH x 2 columns of the current and of
 //                                     the prefetched row in registers, ONE barrier per row for u_r = a_r . v in that kernel's order (FMA chain per
 //                                     thread, wave butterfly, eight partials added in index order), the same non-temporal rule for A.  No exp, no
@@ -21,7 +21,7 @@
 // Both kernels take a `const QnVecCtl*`: non-null, they return at once unless QN_NEWTON_CG's inner loop is running; null, they always run.
 //
 // No atomics, no workgroup waits for another, every order is fixed: the same bits for the same (x, v) from run to run and from object to object.
-// Built for n_pad <= 16384 -- where the one-pass evaluation exists (lse_kch != 0) -- and on one rank.
+// Built for n_pad <= 16384 -- where the one-pass evaluation exists (os.kch != 0) -- and on one rank.
 #pragma once
 
 template <int KCH, bool NTA>
@@ -176,51 +176,80 @@ static int lse_hv_launch(hipStream_t st, int G, const QnLseArgs& a, const double
     return nt ? lse_hv_launch_nt<KCH, true>(st, G, a, v, pw, wgs, wgg, ctl) : lse_hv_launch_nt<KCH, false>(st, G, a, v, pw, wgs, wgg, ctl);
 }
 
+// what the one-rank kernels of the dense kinds read of QnLseArgs: A, mu and the shapes (the multinomial's: the flat vector of N entries in N_pad)
+static QnLseArgs dense_stream_args(const qn_objective* o) {
+    QnLseArgs a{};
+    a.A = o->dn.rows; a.mu = o->dn.mu;
+    a.m = (int)o->dn.m; a.m_pad = o->dn.TA.n_pad; a.mrpr = o->dn.TA.rpr; a.n = (int)o->n; a.n_pad = o->T.n_pad;
+    a.world = 1; a.rank = 0; a.rs = 1;
+    return a;
+}
+
 static int lse_hv_built(const qn_objective* o) {
     if (o->ctx->world != 1) return fail(QN_ERROR_INPUT_PARAMS, "the log-sum-exp Hessian-vector product is single-GPU (not built for a row-sharded context)");
-    if (!o->lse_kch) return fail(QN_ERROR_INPUT_PARAMS, "the log-sum-exp Hessian-vector product is not built for n_pad > 16384 (it exists where the one-pass evaluation does)");
+    if (!o->os.kch) return fail(QN_ERROR_INPUT_PARAMS, "the log-sum-exp Hessian-vector product is not built for n_pad > 16384 (it exists where the one-pass evaluation does)");
     return QN_OK;
 }
 
-// enqueue q = H v into q_dev (n_pad entries, zero past n) and the shares of v'Hv into o->lhv_shares, with p in o->lw and gbar in gbar_dev
-// (o->lgall after lse_enqueue_weights at the point x; QN_NEWTON_CG keeps a copy, an evaluation in between overwrites lgall).  v_dev: n_pad entries.
+// enqueue q = H v into q_dev (n_pad entries, zero past n) and the shares of v'Hv into o->os.hv_shares, with p in o->wp.w and gbar in gbar_dev
+// (o->lse.gall after lse_enqueue_weights at the point x; QN_NEWTON_CG keeps a copy, an evaluation in between overwrites it).  v_dev: n_pad entries.
 // The evaluation's per-workgroup scratch is reused: one stream, and every evaluation rewrites all of it.  `ctl` != NULL (QN_NEWTON_CG's inner
 // loop): both launches return at once unless the control block says that loop is running; NULL (qn_objective_hess_vec_at): unconditional --
 // spq_curv_kernel's pattern.  `which`: 1 the stream of A, 2 the combine, 3 both (profiling mode times the two apart).
-static int lse_enqueue_hess_vec(qn_objective* o, const double* v_dev, const double* gbar_dev, double* q_dev, const QnVecCtl* ctl, int which = 3) {
+static int lse_enqueue_hess_vec(qn_objective* o, const double* v_dev, const double* gbar_dev, double* q_dev, const QnVecCtl* ctl, int which) {
     QNCHK(lse_hv_built(o));
     hipStream_t st = o->ctx->stream;
     const int np = o->T.n_pad;
-    QNCHK(o->lhv_shares.ensure(257, st));
-    QnLseArgs a{};
-    a.A = o->Q; a.mu = o->mu;
-    a.m = (int)o->m; a.m_pad = o->TA.n_pad; a.mrpr = o->TA.rpr; a.n = (int)o->n; a.n_pad = np;
-    a.world = 1; a.rank = 0; a.rs = 1;
+    QNCHK(o->os.hv_shares.ensure(257, st));
+    const QnLseArgs a = dense_stream_args(o);
     int lst = QN_OK;
-    if (which & 1) switch (o->lse_kch) {
-    case 1: lst = lse_hv_launch<1>(st, o->lse_G, a, v_dev, o->lw, o->lwgms, o->lwgg, ctl); break;
-    case 2: lst = lse_hv_launch<2>(st, o->lse_G, a, v_dev, o->lw, o->lwgms, o->lwgg, ctl); break;
-    case 4: lst = lse_hv_launch<4>(st, o->lse_G, a, v_dev, o->lw, o->lwgms, o->lwgg, ctl); break;
-    case 8: lst = lse_hv_launch<8>(st, o->lse_G, a, v_dev, o->lw, o->lwgms, o->lwgg, ctl); break;
-    default: lst = lse_hv_launch<16>(st, o->lse_G, a, v_dev, o->lw, o->lwgms, o->lwgg, ctl); break;
-    }
+    if (which & 1) lst = lse_kch_call(o->os.kch, [&](auto K) { return lse_hv_launch<decltype(K)::value>(st, o->os.G, a, v_dev, o->wp.w, o->os.wgms, o->os.wgg, ctl); });
     QNCHK(lst);
     if (which & 2)
-        hipLaunchKernelGGL(lse_hv_combine_kernel, dim3((np + 63) / 64), dim3(256), 0, st, a, o->lse_G, (const double*)o->lwgms, (const double*)o->lwgg, v_dev,
-                           gbar_dev, q_dev, (double*)o->lhv_shares, ctl);
+        hipLaunchKernelGGL(lse_hv_combine_kernel, dim3((np + 63) / 64), dim3(256), 0, st, a, o->os.G, (const double*)o->os.wgms, (const double*)o->os.wgg, v_dev,
+                           gbar_dev, q_dev, (double*)o->os.hv_shares, ctl);
     HIPCHK(hipGetLastError());
     return QN_OK;
 }
 
+// ---- what the kinds that share these kernels (LogSumExp, Logistic, Multinomial) put into their tables ----
+// v'Hv: the combine kernel's shares, one per 64 columns
+static int lse_hv_out(qn_objective* o, QnHvOut* out) {
+    QNCHK(o->os.hv_shares.ensure(257, o->ctx->stream));
+    *out = QnHvOut{o->os.hv_shares, (o->T.n_pad + 63) / 64, true};
+    return QN_OK;
+}
+// H = A' diag(d) A + mu I (the logistic pair, the multinomial): zeros where log-sum-exp has gbar
+static const double* wp_zero_gbar(const qn_objective* o) { return o->wp.zero; }
+// qn_stats.obj_bytes: one stream of the dense A (a product; the logistic's evaluation and weights pass)
+static uint64_t dense_stream_bytes(const qn_objective* o) { return (uint64_t)o->dn.m * (uint64_t)o->T.n_pad * 8ull; }
+
+static int lse_weights_op(qn_objective* o, const double* x_dev) { QnLseArgs a{}; return lse_enqueue_weights(o, x_dev, a); } // p -> wp.w, gbar -> lse.gall
+static const double* lse_gbar(const qn_objective* o) { return o->lse.gall; }
+// one pass over this rank's rows of A per evaluation (two for n > 16384), as the dense family counts it
+static uint64_t lse_eval_bytes(const qn_objective* o) {
+    return (uint64_t)o->dn.TA.rpr * (uint64_t)o->T.n_pad * 8ull * ((o->os.kch && !o->lse.two_pass) ? 1ull : 2ull);
+}
+static uint64_t lse_weights_bytes(const qn_objective* o) { return 2ull * dense_stream_bytes(o); }
+
+static const QnObjOps kLseOps = {
+    /* eval */ lse_enqueue_eval, /* eval_launches */ 0, /* eval_split */ false, /* vec_counted */ false,
+    /* weights */ lse_weights_op, 4,
+    /* hv_built, hess_vec, gbar, hv_out */ lse_hv_built, lse_enqueue_hess_vec, lse_gbar, lse_hv_out, 2, false,
+    /* curvature, curv_shares; hessian */ nullptr, nullptr, lse_enqueue_hessian, 5,
+    /* bytes: eval, product, weights, curvature */ lse_eval_bytes, dense_stream_bytes, lse_weights_bytes, nullptr,
+    /* no_dense_family */ nullptr, /* no_rows */ nullptr, /* no_hessian */ nullptr,
+    /* no_curvature */ "qn_objective_hess_vec: not built for this objective (a dense or a sparse quadratic has a Hessian-vector product)",
+};
+static const QnObjOps* lse_ops() { return &kLseOps; }
+
+// (H(x) v, v'H(x)v) of any kind: the weights at x, one product, the shares' sum where the kind leaves shares.  A quadratic's Hessian is Q: x is not read
 extern "C" int qn_objective_hess_vec_at(qn_objective* o, const double* x_host, const double* v_host, double* q_host, double* vhv) {
     if (!o || !v_host || !vhv) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
-    if (o->kind == OBJ_QUADRATIC || o->kind == OBJ_SPARSE_QUADRATIC) return qn_objective_hess_vec(o, v_host, q_host, vhv); // (x is not read: the Hessian is Q)
-    if (o->kind != OBJ_LOGSUMEXP && o->kind != OBJ_LOGISTIC && o->kind != OBJ_SPARSE_LOGISTIC && o->kind != OBJ_MULTINOMIAL) return fail(QN_ERROR_INPUT_PARAMS, "unsupported objective");
+    const QnObjOps* ops = o->ops;
+    if (ops->curvature) return qn_objective_hess_vec(o, v_host, q_host, vhv);
     if (!x_host) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
-    if (o->kind == OBJ_SPARSE_LOGISTIC) return slog_hess_vec_at(o, x_host, v_host, q_host, vhv); // (a weights pass, the product's two passes, the fold)
-    if (o->kind == OBJ_MULTINOMIAL) return mnl_hess_vec_at(o, x_host, v_host, q_host, vhv); // (one weights pass, its own stream in product mode, this file's combine with a zero gbar)
-    if (o->kind == OBJ_LOGISTIC) return logit_hess_vec_at(o, x_host, v_host, q_host, vhv); // (one weights pass, this file's product with a zero gbar)
-    QNCHK(lse_hv_built(o));
+    if (ops->hv_built) QNCHK(ops->hv_built(o));
     qn_context* c = o->ctx;
     HIPCHK(hipSetDevice(c->device));
     const size_t np = o->T.n_pad;
@@ -228,13 +257,15 @@ extern "C" int qn_objective_hess_vec_at(qn_objective* o, const double* x_host, c
     QNCHK(o->eg.ensure(np, c->stream));
     HIPCHK(hipMemcpyAsync(o->ex, x_host, o->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(o->ex + np, v_host, o->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    QnLseArgs a{};
-    QNCHK(lse_enqueue_weights(o, o->ex, a)); // p -> lw, gbar -> lgall
-    QNCHK(lse_enqueue_hess_vec(o, o->ex + np, o->lgall, o->eg, nullptr));
-    const int count = (int)((np + 63) / 64);
-    hipLaunchKernelGGL(lse_hv_shares_kernel, dim3(1), dim3(256), 0, c->stream, (const double*)o->lhv_shares, count, (double*)o->lhv_shares + 256);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(vhv, o->lhv_shares + 256, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    QNCHK(ops->weights(o, o->ex));
+    QNCHK(ops->hess_vec(o, o->ex + np, ops->gbar(o), o->eg, nullptr, 3));
+    QnHvOut out{};
+    QNCHK(ops->hv_out(o, &out));
+    if (out.sum) {
+        hipLaunchKernelGGL(lse_hv_shares_kernel, dim3(1), dim3(256), 0, c->stream, out.shares, out.count, (double*)out.shares + 256);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipMemcpyAsync(vhv, out.sum ? out.shares + 256 : out.shares, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (q_host) HIPCHK(hipMemcpyAsync(q_host, o->eg, o->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
     return QN_OK;

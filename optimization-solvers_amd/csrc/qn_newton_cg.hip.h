@@ -35,7 +35,7 @@
 struct QnTnArgs {
     double *r, *p, *q;     // the residual, the inner direction, H p: n_pad each
     double* gbar;          // the method's copy of A'p
-    const double* gbar_src; // the objective's (lgall, as lse_enqueue_weights left it)
+    const double* gbar_src; // the objective's (its table's `gbar`: lse.gall as lse_enqueue_weights left it, or zeros)
     double* tpart;         // [QN_TN_NPART][QN_VEC_MAXG]
     const double* kshares; // lse_hv_combine_kernel's shares of p.q
     int kcount;

@@ -114,14 +114,14 @@ static int spq_launch(hipStream_t st, const QnSpqArgs& a, int lanes, double* f_d
     return QN_OK;
 }
 
-// enqueue one evaluation of a sparse quadratic at x_dev: f -> f_dev, g -> g_dev[0 .. n) (declared in qn_host_objective.hip.h).  `which`: 1 = the
-// evaluation launch alone, 2 = the finish alone (the vector pump times the two apart in profiling mode), 3 = both
-static int spq_enqueue_eval(qn_objective* o, const double* x_dev, double* f_dev, double* g_dev, int which) {
+// enqueue one evaluation of a sparse quadratic at x_dev: f -> f_dev, g -> g_dev[0 .. n).  `which`: 1 = the evaluation launch alone, 2 = the finish
+// alone (the vector pump times the two apart in profiling mode: t_eval_ms is spq_eval_kernel alone, what tools/bench_sparse.py reports), 3 = both
+static int spq_enqueue_eval(qn_objective* o, const double* x_dev, double* f_dev, double* g_dev, int which, const QnObjWork*) {
     QnSpqArgs a{};
-    a.row_ptr = o->sp_row_ptr; a.col = o->sp_col; a.val = o->sp_val; a.b = o->b; a.wg_row_start = o->sp_wg_row_start; a.long_rows = o->sp_long_rows;
-    a.x = x_dev; a.g = g_dev; a.part = o->sp_part;
-    a.n = (int)o->n; a.G = o->sp_G; a.n_long = (int)o->sp_n_long;
-    return spq_launch(o->ctx->stream, a, o->sp_lanes, f_dev, which);
+    a.row_ptr = o->sp.row_ptr; a.col = o->sp.col; a.val = o->sp.val; a.b = o->sp.b; a.wg_row_start = o->sp.wg_row_start; a.long_rows = o->sp.long_rows;
+    a.x = x_dev; a.g = g_dev; a.part = o->sp.part;
+    a.n = (int)o->n; a.G = o->sp.G; a.n_long = (int)o->sp.n_long;
+    return spq_launch(o->ctx->stream, a, o->sp.lanes, f_dev, which);
 }
 
 // ---- the curvature pass: q = Q d and the shares of c = d'Qd (qn_objective_hess_vec; QN_LS_EXACT_QUADRATIC's search, qn_vec_exact.hip.h) ----
@@ -178,13 +178,13 @@ static void spq_launch_curv_L(hipStream_t st, const QnSpqArgs& a, const QnVecCtl
 
 // enqueue one curvature pass of a sparse quadratic, with the lanes per row of the evaluation: q = Q d -> q_dev[0 .. n) and the shares (which & 1), then
 // d'Qd -> c_dev by spq_finish_kernel (which & 2; the search adds the shares in exact_step_kernel instead, in the same order)
-static int spq_enqueue_curvature(qn_objective* o, const double* d_dev, double* c_dev, double* q_dev, const QnVecCtl* ctl, int which) {
+static int spq_enqueue_curvature(qn_objective* o, const double* d_dev, double* c_dev, double* q_dev, const QnVecCtl* ctl, int which, const QnObjWork*) {
     QnSpqArgs a{};
-    a.row_ptr = o->sp_row_ptr; a.col = o->sp_col; a.val = o->sp_val; a.b = nullptr; a.wg_row_start = o->sp_wg_row_start; a.long_rows = o->sp_long_rows;
-    a.x = d_dev; a.g = q_dev; a.part = o->sp_part;
-    a.n = (int)o->n; a.G = o->sp_G; a.n_long = (int)o->sp_n_long;
+    a.row_ptr = o->sp.row_ptr; a.col = o->sp.col; a.val = o->sp.val; a.b = nullptr; a.wg_row_start = o->sp.wg_row_start; a.long_rows = o->sp.long_rows;
+    a.x = d_dev; a.g = q_dev; a.part = o->sp.part;
+    a.n = (int)o->n; a.G = o->sp.G; a.n_long = (int)o->sp.n_long;
     hipStream_t st = o->ctx->stream;
-    if (which & 1) switch (o->sp_lanes) {
+    if (which & 1) switch (o->sp.lanes) {
     case 1: spq_launch_curv_L<1>(st, a, ctl); break;
     case 2: spq_launch_curv_L<2>(st, a, ctl); break;
     case 4: spq_launch_curv_L<4>(st, a, ctl); break;
@@ -198,3 +198,19 @@ static int spq_enqueue_curvature(qn_objective* o, const double* d_dev, double* c
     HIPCHK(hipGetLastError());
     return QN_OK;
 }
+
+static void spq_curv_shares(const qn_objective* o, const double** part, int* count) { *part = o->sp.part; *count = o->sp.G + (int)o->sp.n_long; }
+// qn_stats.obj_bytes: values + columns, the row offsets, and x, b, g of one evaluation; a curvature pass reads d, writes q and reads no b
+static uint64_t spq_eval_bytes(const qn_objective* o) { return 12ull * (uint64_t)o->sp.nnz + 4ull * ((uint64_t)o->n + 1) + 24ull * (uint64_t)o->n; }
+static uint64_t spq_curv_bytes(const qn_objective* o) { return 12ull * (uint64_t)o->sp.nnz + 4ull * ((uint64_t)o->n + 1) + 16ull * (uint64_t)o->n; }
+
+static const QnObjOps kSpqOps = {
+    /* eval */ spq_enqueue_eval, /* eval_launches */ 2, /* eval_split */ true, /* vec_counted */ true,
+    /* weights */ nullptr, 0,
+    /* hv_built, hess_vec, gbar, hv_out */ nullptr, nullptr, nullptr, nullptr, 0, false,
+    /* curvature, curv_shares; hessian */ spq_enqueue_curvature, spq_curv_shares, nullptr, 0,
+    /* bytes: eval, product, weights, curvature */ spq_eval_bytes, nullptr, nullptr, spq_curv_bytes,
+    /* no_dense_family */ "unsupported objective",
+    /* no_rows, no_hessian, no_curvature */ "a sparse quadratic has no dense rows / Hessian", "a sparse quadratic has no dense rows / Hessian", nullptr,
+};
+static const QnObjOps* spq_ops() { return &kSpqOps; }

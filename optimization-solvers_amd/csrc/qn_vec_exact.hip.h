@@ -125,33 +125,49 @@ static int exact_state_alloc(qn_solver* s) {
     return QN_OK;
 }
 
+// the dense quadratic's curvature pass: q = Q d by the row kernel (which & 1), then d'Qd -> c_dev and q -> q_dev (which & 2).  `w`: as
+// quad_enqueue_eval's; one rank
+static int quad_enqueue_curvature(qn_objective* o, const double* d_dev, double* c_dev, double* q_dev, const QnVecCtl* ctl, int which, const QnObjWork* w) {
+    QnVecs V{};
+    double* xcopy = nullptr;
+    QNCHK(quad_vecs(o, d_dev, w, &V, &xcopy));
+    if (which & 1) QNCHK(quad_enqueue_rows(o, d_dev, V, xcopy));
+    if (which & 2) hipLaunchKernelGGL(quad_curv_finish_kernel, dim3(1), dim3(QN_CTL_TPB), 0, o->ctx->stream, V, c_dev, q_dev, ctl);
+    HIPCHK(hipGetLastError());
+    return QN_OK;
+}
+static uint64_t quad_pass_bytes(const qn_objective* o) { return (uint64_t)o->T.rpr * (uint64_t)o->T.n_pad * 8ull; } // this rank's rows of Q, once
+
+// the dense family evaluates a quadratic with kernels of its own (oracle_tpl = QN_ORACLE_QUAD); the first-order family and the host entry points use
+// these.  One KC_EVAL scope for the two launches, as ever
+static const QnObjOps kQuadOps = {
+    /* eval */ quad_enqueue_eval, /* eval_launches */ 2, /* eval_split */ false, /* vec_counted */ true,
+    /* weights */ nullptr, 0,
+    /* hv_built, hess_vec, gbar, hv_out */ nullptr, nullptr, nullptr, nullptr, 0, false,
+    /* curvature, curv_shares; hessian */ quad_enqueue_curvature, nullptr, nullptr, 0,
+    /* bytes: eval, product, weights, curvature */ quad_pass_bytes, nullptr, nullptr, quad_pass_bytes,
+    /* no_dense_family */ nullptr, /* no_rows */ nullptr, /* no_hessian */ nullptr, /* no_curvature */ nullptr,
+};
+static const QnObjOps* quad_ops() { return &kQuadOps; }
+
 // phase QN_VP_EXACT: the curvature pass along V.d and the step, behind the loop top -- no peek in between
 static int exact_enqueue_step(VecRun& r) {
     qn_solver* s = r.s;
-    hipStream_t st = s->ctx->stream;
+    const QnObjOps* ops = r.obj->ops;
     QnExactArgs e{};
     e.ctl = s->vctl; e.c_dev = s->ex_c; e.bounded = (s->bounded && s->box_finite) ? 1 : 0;
-    if (r.obj->kind == OBJ_SPARSE_QUADRATIC) {
-        { ProfScope ps(s, KC_NEWTON); QNCHK(spq_enqueue_curvature(r.obj, s->V.d, nullptr, s->ex_q, s->vctl, 1)); }
-        e.part = r.obj->sp_part; e.count = r.obj->sp_G + (int)r.obj->sp_n_long;
+    const QnObjWork w{s->V.q, s->V.s}; // (row-block 0 stores its copy of the point: V.s is free here)
+    { ProfScope ps(s, KC_NEWTON); QNCHK(ops->curvature(r.obj, s->V.d, s->ex_c, s->ex_q, s->vctl, 1, &w)); }
+    if (ops->curv_shares) { // exact_step_kernel adds the shares itself, in the finish kernel's order
+        ops->curv_shares(r.obj, &e.part, &e.count);
         s->stats.launches += 1;
     } else {
-        {
-            ProfScope ps(s, KC_NEWTON);
-            QnQuadArgs q{};
-            q.Q = r.obj->Q; q.T = r.obj->T; q.T.cs = 1; q.x = s->V.d; q.d = s->V.d; q.xt = s->V.s; // (row-block 0 stores its copy of the point: V.s is free here)
-            q.out = s->V.q; q.ctl = nullptr; q.expect_phase = -1; q.force_kind = QN_REQ_X; q.force_t = 0.0;
-            QNCHK(launch_quad_R(8, st, q));
-        }
         ProfScope ps(s, KC_CTL);
-        QnVecs V{};
-        V.q = s->V.q; V.xt = s->V.d; V.n = (int)s->n; V.n_pad = s->T.n_pad; V.rpr = s->T.rpr; V.world = 1; V.qcs = 1; V.hcs = 1;
-        hipLaunchKernelGGL(quad_curv_finish_kernel, dim3(1), dim3(QN_CTL_TPB), 0, st, V, (double*)s->ex_c, (double*)s->ex_q, (const QnVecCtl*)s->vctl);
-        HIPCHK(hipGetLastError());
+        QNCHK(ops->curvature(r.obj, s->V.d, s->ex_c, s->ex_q, s->vctl, 2, &w));
         s->stats.launches += 2;
     }
     ProfScope ps(s, KC_CTL);
-    hipLaunchKernelGGL(exact_step_kernel, dim3(1), dim3(SPQ_TPB), 0, st, e);
+    hipLaunchKernelGGL(exact_step_kernel, dim3(1), dim3(SPQ_TPB), 0, s->ctx->stream, e);
     HIPCHK(hipGetLastError());
     s->stats.launches++;
     return QN_OK;
@@ -169,14 +185,7 @@ static int exact_enqueue_advance(VecRun& r) {
 
 extern "C" int qn_objective_hess_vec(qn_objective* o, const double* v_host, double* q_host, double* vqv) {
     if (!o || !v_host || !vqv) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
-    if (o->kind == OBJ_SPARSE_LOGISTIC)
-        return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hess_vec: the Hessian of a sparse logistic objective depends on x: use qn_objective_hess_vec_at");
-    if (o->kind == OBJ_LOGISTIC)
-        return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hess_vec: the Hessian of a logistic objective depends on x: use qn_objective_hess_vec_at");
-    if (o->kind == OBJ_MULTINOMIAL)
-        return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hess_vec: the Hessian of a multinomial objective depends on x: use qn_objective_hess_vec_at");
-    if (o->kind != OBJ_QUADRATIC && o->kind != OBJ_SPARSE_QUADRATIC)
-        return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hess_vec: not built for this objective (a dense or a sparse quadratic has a Hessian-vector product)");
+    if (o->ops->no_curvature) return fail(QN_ERROR_INPUT_PARAMS, o->ops->no_curvature);
     qn_context* c = o->ctx;
     if (c->world != 1) return fail(QN_ERROR_INPUT_PARAMS, "qn_objective_hess_vec is single-GPU");
     HIPCHK(hipSetDevice(c->device));
@@ -185,20 +194,7 @@ extern "C" int qn_objective_hess_vec(qn_objective* o, const double* v_host, doub
     QNCHK(o->eg.ensure(np, c->stream));
     QNCHK(o->ef.ensure(2, c->stream));
     HIPCHK(hipMemcpyAsync(o->ex, v_host, o->n * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    if (o->kind == OBJ_SPARSE_QUADRATIC) {
-        QNCHK(spq_enqueue_curvature(o, o->ex, o->ef, o->eg, nullptr, 3));
-    } else {
-        QNCHK(o->eq.ensure(np, c->stream));
-        QnQuadArgs a{};
-        a.Q = o->Q; a.T = o->T; a.x = o->ex; a.d = o->ex; a.xt = o->ex + np;
-        a.out = o->eq;
-        a.ctl = nullptr; a.expect_phase = -1; a.force_kind = QN_REQ_X; a.force_t = 0.0;
-        QNCHK(launch_quad_R(8, c->stream, a));
-        QnVecs V{};
-        V.q = o->eq; V.xt = o->ex + np; V.n = (int)o->n; V.n_pad = (int)np; V.rpr = o->T.rpr; V.world = 1; V.qcs = 1; V.hcs = 1;
-        hipLaunchKernelGGL(quad_curv_finish_kernel, dim3(1), dim3(QN_CTL_TPB), 0, c->stream, V, (double*)o->ef, (double*)o->eg, (const QnVecCtl*)nullptr);
-        HIPCHK(hipGetLastError());
-    }
+    QNCHK(o->ops->curvature(o, o->ex, o->ef, o->eg, nullptr, 3, nullptr));
     HIPCHK(hipMemcpyAsync(vqv, o->ef, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (q_host) HIPCHK(hipMemcpyAsync(q_host, o->eg, o->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
