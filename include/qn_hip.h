@@ -280,6 +280,30 @@ int qn_multinomial_probabilities(qn_objective* objective, const double* x_host, 
  * where its cut and its LDS fit; otherwise QN_ERROR_INPUT_PARAMS and nothing changes), 0 the automatic choice, which a new objective has.  The two
  * kernels sum in different orders: each gives the same bits from run to run, not the other's. */
 int qn_multinomial_set_kernel(qn_objective* objective, int kernel);
+/* The same softmax regression on a SPARSE A (m x n in CSR, the columns of a row strictly increasing; the index arrays as qn_sparse_logistic_create
+ * takes them): qn_multinomial_create's function, labels, weights, mu and CLASS-MAJOR parameter vector x[k n + j] = W[k, j] of N = K n entries, with
+ * no limit on K n and none on K.  The device holds A AND A' (24 bytes per nonzero) and feature-major copies of x and of A'C with the padded leading
+ * dimension Kp (qn_sparse_multinomial_info); no float atomic, every sum in one fixed order: the same bits for the same x from run to run, from
+ * object to object and for int32 and int64 indices.  Each failure QN_ERROR_INPUT_PARAMS before anything is allocated: a null pointer, m == 0 or
+ * n == 0, index_bytes not 4 or 8, K < 2, m or n > 2^30, nnz > 2^31 - 1, m K > 2^31 - 1, K n > 2^30, a bad CSR pattern (qn_sparse_logistic_create's
+ * rules), a label outside [0, K) or a negative or non-finite weight (with the index), a non-finite mu, a row-sharded context ("single-GPU").  A
+ * failed creation leaks nothing and leaves *out alone.  One evaluation is FIVE launches (csrc/qn_sparse_multinomial.hip.h): x to feature-major, the
+ * row pass (margins, softmax, C, P, the loss), the column pass (A'C), back to class-major (+ mu x, ||x||^2) and a one-workgroup finish.  It runs
+ * under QN_SPG, QN_PROJECTED_GRADIENT, QN_LBFGS, QN_NONLINEAR_CG and QN_NEWTON_CG with every line search those take but ExactQuadratic; every other
+ * method, qn_objective_hessian, qn_objective_hess_vec, qn_objective_get_rows, qn_objective_sparse_info and the qn_multinomial_* / qn_sparse_logistic_*
+ * calls: QN_ERROR_INPUT_PARAMS.  qn_objective_eval works on it; qn_objective_hess_vec_at gives H(x) v (a weights pass at x, the product's five launches). */
+int qn_sparse_multinomial_create(qn_context* ctx, size_t m, size_t n, size_t n_classes, size_t nnz, const void* row_ptr_host, const void* col_idx_host,
+                                 int index_bytes, const double* values_host, const void* labels_i32_host, const double* w_host, double mu,
+                                 qn_objective** out);
+/* nnz, the entry lanes per row in use for each pass, the long rows of A and of A', and Kp (any pointer may be NULL).  Another objective:
+ * QN_ERROR_INPUT_PARAMS. */
+int qn_sparse_multinomial_info(qn_objective* objective, size_t* nnz, int* lanes_rows, int* lanes_cols, size_t* n_long_rows, size_t* n_long_cols, int* kp);
+/* Entry lanes L that share one row in the row pass (over A) and in the column pass (over A'): each 1, 2, 4, 8, 16, 32 or 64, or 0 for the choice made
+ * at creation; min(64 / L, the next power of two of K) class lanes stand beside each.  Another value may change the bits of f, g and H v; the
+ * results stay inside the same error bounds. */
+int qn_sparse_multinomial_set_lanes(qn_objective* objective, int lanes_rows, int lanes_cols);
+/* The class probabilities at x (N entries, class-major): p_host receives m x K row-major; a masked row's are zeros.  One weights pass. */
+int qn_sparse_multinomial_probabilities(qn_objective* objective, const double* x_host, double* p_host);
 /* f = 1/2 x'Qx - b'x, g = Qx - b with a SPARSE Q: n x n in CSR, both triangles of a symmetric matrix -- the device objective that exists at the
  * sizes the O(n) solvers are for.  It runs under QN_SPG, QN_PROJECTED_GRADIENT and QN_LBFGS with every line search those take; every other method:
  * QN_ERROR_INPUT_PARAMS ("unsupported objective"; the projected Newton pair: "Hessian not available in the oracle").  One rank (a row-sharded

@@ -390,6 +390,58 @@ class Multinomial {
     }
 };
 
+// the same softmax regression with a sparse A in CSR (m x n, the columns of a row strictly increasing) and no limit on n_classes * n: the device keeps
+// A and A' (24 bytes per nonzero) and feature-major copies of the class-major vectors, so both halves of an evaluation are a sparse matrix times a
+// skinny dense one, with no atomics and every sum in one fixed order.  Labels, weights, mu and the CLASS-MAJOR parameter vector as Multinomial's.  It
+// runs under SpectralProjectedGradient, ProjectedGradientDescent, LBFGS / ProjectedLBFGS, NonlinearCG and NewtonCG.  Index: int32_t or int64_t.
+class SparseMultinomial {
+    qn_objective* h_ = nullptr;
+    size_t n_, k_, m_;
+  public:
+    template <class Index>
+    SparseMultinomial(const std::vector<Index>& indptr, const std::vector<Index>& indices, const DVector& data, const std::vector<int32_t>& labels, size_t n,
+                      size_t n_classes, Floating mu, const DVector& weights = DVector(), Context& ctx = Context::default_context())
+        : n_(n * n_classes), k_(n_classes), m_(labels.size()) {
+        static_assert(sizeof(Index) == 4 || sizeof(Index) == 8, "CSR indices are 32 or 64 bits wide");
+        if (indptr.size() != labels.size() + 1 || indices.size() != data.size()) throw SolverError{SolverError::ErrorInputParams, "CSR arrays do not match"};
+        if (!weights.empty() && weights.size() != labels.size()) throw SolverError{SolverError::ErrorInputParams, "weights does not have one entry per row"};
+        const Index no_index = 0; // (an empty matrix: the library takes a null pointer for a missing argument)
+        const Floating no_value = 0;
+        check(qn_sparse_multinomial_create(ctx.handle(), labels.size(), n, n_classes, data.size(), indptr.data(), indices.empty() ? &no_index : indices.data(),
+                                           (int)sizeof(Index), data.empty() ? &no_value : data.data(), labels.data(), weights.empty() ? nullptr : weights.data(), mu, &h_));
+    }
+    SparseMultinomial(const SparseMultinomial&) = delete;
+    ~SparseMultinomial() { qn_objective_destroy(h_); }
+    qn_objective* handle() const { return h_; }
+    size_t n_classes() const { return k_; }
+    size_t size() const { return n_; } // N = n_classes * n
+    FuncEvalMultivariate operator()(const DVector& x) const {
+        if (x.size() != n_) throw SolverError{SolverError::ErrorInputParams, "x does not have the objective's N entries"};
+        DVector g(n_);
+        Floating f = 0;
+        check(qn_objective_eval(h_, x.data(), &f, g.data()));
+        return FuncEvalMultivariate(f, std::move(g));
+    }
+    std::pair<DVector, Floating> hess_vec_at(const DVector& x, const DVector& v) const { // (H(x) v, v'H(x)v): a weights pass at x, then the product's five launches; no matrix
+        if (x.size() != n_ || v.size() != n_) throw SolverError{SolverError::ErrorInputParams, "x or v does not have the objective's N entries"};
+        DVector q(n_);
+        Floating c = 0;
+        check(qn_objective_hess_vec_at(h_, x.data(), v.data(), q.data(), &c));
+        return {std::move(q), c};
+    }
+    DVector probabilities(const DVector& x) const { // m x n_classes, row-major; a masked row's are zeros
+        if (x.size() != n_) throw SolverError{SolverError::ErrorInputParams, "x does not have the objective's N entries"};
+        DVector p(m_ * k_);
+        check(qn_sparse_multinomial_probabilities(h_, x.data(), p.data()));
+        return p;
+    }
+    void set_lanes(int rows, int cols) { check(qn_sparse_multinomial_set_lanes(h_, rows, cols)); } // 0: automatic
+    size_t nnz() const { size_t v = 0; check(qn_sparse_multinomial_info(h_, &v, nullptr, nullptr, nullptr, nullptr, nullptr)); return v; }
+    size_t n_long_rows() const { size_t v = 0; check(qn_sparse_multinomial_info(h_, nullptr, nullptr, nullptr, &v, nullptr, nullptr)); return v; }
+    size_t n_long_cols() const { size_t v = 0; check(qn_sparse_multinomial_info(h_, nullptr, nullptr, nullptr, nullptr, &v, nullptr)); return v; }
+    int kp() const { int v = 0; check(qn_sparse_multinomial_info(h_, nullptr, nullptr, nullptr, nullptr, nullptr, &v)); return v; }
+};
+
 // a device-resident objective f = 1/2 x'Qx - b'x with a sparse Q in CSR (both triangles of a symmetric matrix): the large objective of the O(n)
 // solvers -- SpectralProjectedGradient, ProjectedGradientDescent, LBFGS / ProjectedLBFGS.  Index: int32_t or int64_t, for both arrays.
 class SparseQuadratic {
@@ -487,7 +539,8 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
     // (a device objective is callable too: without the constraint a non-const Quadratic / LogSumExp lvalue would bind here, as a host closure)
     template <class LS, class Oracle, class = std::enable_if_t<!std::is_same_v<std::decay_t<Oracle>, Quadratic> && !std::is_same_v<std::decay_t<Oracle>, LogSumExp> &&
                                                                !std::is_same_v<std::decay_t<Oracle>, SparseQuadratic> && !std::is_same_v<std::decay_t<Oracle>, Logistic> &&
-                                                               !std::is_same_v<std::decay_t<Oracle>, SparseLogistic> && !std::is_same_v<std::decay_t<Oracle>, Multinomial>>>
+                                                               !std::is_same_v<std::decay_t<Oracle>, SparseLogistic> && !std::is_same_v<std::decay_t<Oracle>, Multinomial> &&
+                                                               !std::is_same_v<std::decay_t<Oracle>, SparseMultinomial>>>
     Result minimize(LS& line_search, Oracle&& oracle, size_t max_iter_solver, size_t max_iter_line_search,
                     std::optional<std::function<void(const Self&)>> callback = std::nullopt) {
         using OracleT = std::remove_reference_t<Oracle>;
@@ -548,6 +601,14 @@ class LineSearchSolver { // ls_solver.rs:23-112 for the three solvers on the pat
     }
     template <class LS>
     Result minimize(LS& line_search, const Multinomial& objective, size_t max_iter_solver, size_t max_iter_line_search) {
+        qn_oracle o{};
+        o.kind = QN_ORACLE_OBJECTIVE;
+        o.memoize = 1;
+        o.objective = objective.handle();
+        return make_result(qn_minimize(h_, &line_search.ffi(), &o, max_iter_solver, max_iter_line_search, nullptr, nullptr));
+    }
+    template <class LS>
+    Result minimize(LS& line_search, const SparseMultinomial& objective, size_t max_iter_solver, size_t max_iter_line_search) {
         qn_oracle o{};
         o.kind = QN_ORACLE_OBJECTIVE;
         o.memoize = 1;

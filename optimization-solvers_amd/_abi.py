@@ -129,6 +129,12 @@ SYMBOLS = [
     ("qn_multinomial_create", C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, dp, C.c_void_p, dp, C.c_double, C.POINTER(C.c_void_p)]),
     ("qn_multinomial_probabilities", C.c_int, [C.c_void_p, dp, dp]),
     ("qn_multinomial_set_kernel", C.c_int, [C.c_void_p, C.c_int]),
+    ("qn_sparse_multinomial_create", C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, dp, C.c_void_p,
+                                               dp, C.c_double, C.POINTER(C.c_void_p)]),
+    ("qn_sparse_multinomial_info", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t),
+                                             C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    ("qn_sparse_multinomial_set_lanes", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    ("qn_sparse_multinomial_probabilities", C.c_int, [C.c_void_p, dp, dp]),
     ("qn_sparse_quadratic_create", C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, dp, dp, C.POINTER(C.c_void_p)]),
     ("qn_sparse_quadratic_set_lanes_per_row", C.c_int, [C.c_void_p, C.c_int]),
     ("qn_objective_sparse_info", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),

@@ -89,6 +89,9 @@ extern "C" const char* qn_status_string(int status) {
 // the multinomial objective (one stream of A for K classes; the logistic's and the product's combine kernels fold its shares): behind every existing kernel
 #include "qn_multinomial.hip.h"
 #include "qn_host_multinomial.hip.h"
+// the sparse multinomial objective (A and A' in CSR, two SpMM passes on feature-major copies; five launches per evaluation and per product): behind every existing kernel
+#include "qn_sparse_multinomial.hip.h"
+#include "qn_host_sparse_multinomial.hip.h"
 // truncated Newton (NewtonCG) on the first-order family's machine: conjugate gradients on H z = g with that product, behind every existing kernel
 #include "qn_newton_cg.hip.h"
 #include "qn_host_newton_cg.hip.h"

@@ -1,13 +1,13 @@
 // qn_host_objective.hip.h -- host side, device-resident objectives: the state blocks of qn_objective and the operations table every kind fills
 // (QnObjOps), the creation of the dense quadratic, the log-sum-exp and the sparse quadratic, the first two's evaluation launches, and the host entry
 // points every kind answers through its table (qn_objective_eval, _hessian, _get_rows).  The logistic pair and the multinomial are created in
-// qn_host_logistic.hip.h, qn_host_sparse_logistic.hip.h and qn_host_multinomial.hip.h.
+// qn_host_logistic.hip.h, qn_host_sparse_logistic.hip.h, qn_host_multinomial.hip.h and qn_host_sparse_multinomial.hip.h.
 #pragma once
 #include "qn_csr_host.h"
 // ------------------------------------------------------------------------------------------------
 // objectives
 // ------------------------------------------------------------------------------------------------
-enum { OBJ_QUADRATIC = 1, OBJ_LOGSUMEXP = 2, OBJ_SPARSE_QUADRATIC = 3, OBJ_LOGISTIC = 4, OBJ_SPARSE_LOGISTIC = 5, OBJ_MULTINOMIAL = 6 };
+enum { OBJ_QUADRATIC = 1, OBJ_LOGSUMEXP = 2, OBJ_SPARSE_QUADRATIC = 3, OBJ_LOGISTIC = 4, OBJ_SPARSE_LOGISTIC = 5, OBJ_MULTINOMIAL = 6, OBJ_SPARSE_MULTINOMIAL = 7 };
 // the sparse quadratic's launch shape (qn_sparse.hip.h; the creation below cuts the rows for it)
 #define SPQ_MAXG 2048     // regular workgroups at the most: 8 per CU on 256 CUs
 #define SPQ_LONG_ROW 2048 // rows longer than this get a workgroup of their own
@@ -81,6 +81,19 @@ struct QnMnlState {
     DevBuf<int> lab;
     DevBuf<double> P, P_trial; // P (m_pad x K) at the accepted point, and of trial evaluations (written, never read)
 };
+// SparseMultinomial (qn_sparse_multinomial.hip.h): A and A' in CSR, n = K nf (class-major), T its padding; the skinny matrices have the leading dimension kp
+struct QnSmnState {
+    QnSlogCsr a, at;              // (`lanes`: the entry lanes L of the pass over that copy; at.part is not used)
+    DevBuf<int> lab;              // m labels
+    DevBuf<double> wt;            // m sample weights
+    DevBuf<double> Wt, Gt;        // nf x kp: x or v feature-major; A'C or A'T before it goes back to class-major
+    DevBuf<double> C, T;          // m x kp: the coefficients of one evaluation, t of one product -- what the column pass gathers
+    DevBuf<double> P, P_trial;    // m x kp: P at the accepted point, and of trial evaluations (written, never read)
+    DevBuf<double> tpart;         // the shares of ||x||^2 or v.q (smn_out_kernel)
+    size_t m = 0, nnz = 0;
+    int k = 0, nf = 0, kp = 0;
+    double mu = 0.0;
+};
 
 struct QnObjOps;
 struct qn_objective {
@@ -100,6 +113,7 @@ struct qn_objective {
     QnSpqState sp;
     QnSlogState sl;
     QnMnlState mn;
+    QnSmnState sm;
 };
 
 // ---- operations: one table per kind, defined next to the kind's launches and set at creation ----
@@ -315,6 +329,7 @@ extern "C" int qn_objective_sparse_info(qn_objective* o, size_t* nnz, int* lanes
     if (o && o->kind == OBJ_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "a logistic objective is not a sparse quadratic (its A is dense)");
     if (o && o->kind == OBJ_SPARSE_LOGISTIC) return fail(QN_ERROR_INPUT_PARAMS, "a sparse logistic objective is not a sparse quadratic: qn_sparse_logistic_info describes it");
     if (o && o->kind == OBJ_MULTINOMIAL) return fail(QN_ERROR_INPUT_PARAMS, "a multinomial objective is not a sparse quadratic (its A is dense)");
+    if (o && o->kind == OBJ_SPARSE_MULTINOMIAL) return fail(QN_ERROR_INPUT_PARAMS, "a sparse multinomial objective is not a sparse quadratic: qn_sparse_multinomial_info describes it");
     if (!o || o->kind != OBJ_SPARSE_QUADRATIC) return fail(QN_ERROR_INPUT_PARAMS, "not a sparse quadratic");
     if (nnz) *nnz = o->sp.nnz;
     if (lanes_per_row) *lanes_per_row = o->sp.lanes;

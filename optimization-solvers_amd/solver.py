@@ -910,6 +910,110 @@ class SparseLogistic(Objective):
         _check(A.lib().qn_sparse_logistic_set_lanes(self.h, int(rows), int(cols)))
 
 
+class SparseMultinomial(Objective):
+    """Regularised softmax regression on the device with a SPARSE A in CSR (m x n; the columns of a row strictly increasing): `Multinomial`'s function,
+    labels (integers in [0, K), the failing index named), `weights` (>= 0, finite; a 0 masks its row), mu (finite) and CLASS-MAJOR parameter vector
+    x[k n + j] = W[k, j] -- `self.n` is N = K n -- with no limit on K n and none on K.
+
+    The device keeps A AND A' (24 bytes per nonzero) and works on feature-major copies with the padded leading dimension `kp`: both halves of an
+    evaluation are a sparse matrix times a skinny dense one.  No float atomics, every sum in one fixed order: the same bits from run to run, from
+    object to object and for int32 and int64 indices.  One evaluation is five launches; it runs under SpectralProjectedGradient,
+    ProjectedGradientDescent, LBFGS / ProjectedLBFGS, NonlinearCG and NewtonCG; `hess_vec_at(x, v)` gives (H(x) v, v'H(x)v); `probabilities(x)` the
+    m x K matrix P.  One rank; `hessian`, `hess_vec` and `rows`: ErrorInputParams."""
+
+    def __init__(self, indptr, indices, data, y, n_classes, mu, n, weights=None, ctx=None):
+        ctx = ctx or default_context()
+        indptr, indices = np.asarray(indptr), np.asarray(indices)
+        if indptr.dtype.kind not in "iu" or (indices.size and indices.dtype.kind not in "iu"):
+            raise ErrorInputParams("indptr and indices must be integer arrays")
+        it = indptr.dtype if indptr.dtype == indices.dtype and indptr.dtype in (np.dtype(np.int32), np.dtype(np.int64)) else np.dtype(np.int64)
+        indptr, indices = np.ascontiguousarray(indptr, dtype=it), np.ascontiguousarray(indices, dtype=it)
+        data = _f64(data)
+        yf = np.asarray(y, dtype=np.float64)
+        if indptr.ndim != 1 or indices.ndim != 1 or data.ndim != 1 or yf.ndim != 1 or indptr.size != yf.size + 1 or indices.size != data.size:
+            raise ErrorInputParams("CSR arrays do not match: indptr has m + 1 entries, indices and data nnz each, y has m")
+        m, k = yf.size, int(n_classes)
+        bad = np.flatnonzero(~((yf >= 0) & (yf < max(k, 0)) & (yf == np.floor(yf))))
+        if bad.size:
+            raise ErrorInputParams(f"sparse multinomial: labels[{int(bad[0])}] = {yf[bad[0]]} is not an integer in [0, n_classes)")
+        lab = np.ascontiguousarray(yf, dtype=np.int32)
+        w = None if weights is None else _f64(weights)
+        if w is not None and (w.ndim != 1 or w.size != m):
+            raise ErrorInputParams(f"weights has {w.size} entries, a has {m} rows")
+        # (an empty array's pointer may be null, which the library takes for a missing argument)
+        ci = indices if indices.size else np.zeros(1, dtype=it)
+        va = data if data.size else np.zeros(1)
+        h = C.c_void_p()
+        _check(A.lib().qn_sparse_multinomial_create(ctx.h, m, int(n), max(k, 0), data.size, indptr.ctypes.data_as(C.c_void_p), ci.ctypes.data_as(C.c_void_p),
+                                                    it.itemsize, _dp(va), lab.ctypes.data_as(C.c_void_p), _dp(w) if w is not None else None, float(mu),
+                                                    C.byref(h)))
+        super().__init__(ctx, h, int(n) * k)
+        self.m, self.n_features, self.n_classes = m, int(n), k
+
+    @classmethod
+    def from_scipy(cls, a, y, n_classes, mu, weights=None, ctx=None):
+        """Any scipy sparse matrix (m x n): through .tocsr() with sorted indices and duplicates summed."""
+        import scipy.sparse  # noqa: F401 -- only this method needs scipy
+        a = a.tocsr().copy()
+        a.sum_duplicates()
+        a.sort_indices()
+        return cls(a.indptr, a.indices, a.data, y, n_classes, mu, a.shape[1], weights=weights, ctx=ctx)
+
+    def __call__(self, x):
+        if not self.h:
+            raise ErrorInputParams("the objective is closed")
+        if np.size(x) != self.n:
+            raise ErrorInputParams(f"x has {np.size(x)} entries, the objective has {self.n}")
+        return super().__call__(x)
+
+    def _info(self):
+        if not self.h:
+            raise ErrorInputParams("the objective is closed")
+        nnz, lr, lc, nlr, nlc, kp = C.c_size_t(), C.c_int(), C.c_int(), C.c_size_t(), C.c_size_t(), C.c_int()
+        _check(A.lib().qn_sparse_multinomial_info(self.h, C.byref(nnz), C.byref(lr), C.byref(lc), C.byref(nlr), C.byref(nlc), C.byref(kp)))
+        return nnz.value, (lr.value, lc.value), nlr.value, nlc.value, kp.value
+
+    @property
+    def nnz(self):
+        return self._info()[0]
+
+    @property
+    def lanes(self):
+        """(entry lanes per row of the row pass over A, of the column pass over A')"""
+        return self._info()[1]
+
+    @property
+    def n_long_rows(self):
+        return self._info()[2]
+
+    @property
+    def n_long_cols(self):
+        return self._info()[3]
+
+    @property
+    def kp(self):
+        """The padded leading dimension of the feature-major copies: the next power of two of K up to 16, a multiple of 16 above."""
+        return self._info()[4]
+
+    def set_lanes(self, rows, cols):
+        """Entry lanes that share one row of A (`rows`) and one row of A' (`cols`): 1, 2, 4, 8, 16, 32 or 64; 0: the choice made at creation.
+        Another value may change the bits of f, g and H v."""
+        if not self.h:
+            raise ErrorInputParams("the objective is closed")
+        _check(A.lib().qn_sparse_multinomial_set_lanes(self.h, int(rows), int(cols)))
+
+    def probabilities(self, x):
+        """P at x, m x K: P[i, k] = p_ik (a masked row's are zeros).  One weights pass."""
+        if not self.h:
+            raise ErrorInputParams("the objective is closed")
+        x = _f64(x)
+        if x.size != self.n:
+            raise ErrorInputParams(f"x has {x.size} entries, the objective has {self.n}")
+        p = np.empty((self.m, self.n_classes))
+        _check(A.lib().qn_sparse_multinomial_probabilities(self.h, _dp(x), _dp(p)))
+        return p
+
+
 class _SolverBase:
     METHOD = None
 

@@ -248,6 +248,10 @@ extern "C" {
     pub fn qn_multinomial_create(ctx: *mut qn_context, m: usize, n: usize, n_classes: usize, a_rowmajor_host: *const f64, labels_i32_host: *const c_void, w_host: *const f64, mu: f64, out: *mut *mut qn_objective) -> c_int;
     pub fn qn_multinomial_probabilities(obj: *mut qn_objective, x_host: *const f64, p_host: *mut f64) -> c_int;
     pub fn qn_multinomial_set_kernel(obj: *mut qn_objective, kernel: c_int) -> c_int;
+    pub fn qn_sparse_multinomial_create(ctx: *mut qn_context, m: usize, n: usize, n_classes: usize, nnz: usize, row_ptr_host: *const c_void, col_idx_host: *const c_void, index_bytes: c_int, values_host: *const f64, labels_i32_host: *const c_void, w_host: *const f64, mu: f64, out: *mut *mut qn_objective) -> c_int;
+    pub fn qn_sparse_multinomial_info(obj: *mut qn_objective, nnz: *mut usize, lanes_rows: *mut c_int, lanes_cols: *mut c_int, n_long_rows: *mut usize, n_long_cols: *mut usize, kp: *mut c_int) -> c_int;
+    pub fn qn_sparse_multinomial_set_lanes(obj: *mut qn_objective, lanes_rows: c_int, lanes_cols: c_int) -> c_int;
+    pub fn qn_sparse_multinomial_probabilities(obj: *mut qn_objective, x_host: *const f64, p_host: *mut f64) -> c_int;
     pub fn qn_sparse_quadratic_create(ctx: *mut qn_context, n: usize, nnz: usize, row_ptr_host: *const c_void, col_idx_host: *const c_void, index_bytes: c_int, values_host: *const f64, b_host: *const f64, out: *mut *mut qn_objective) -> c_int;
     pub fn qn_sparse_quadratic_set_lanes_per_row(obj: *mut qn_objective, lanes: c_int) -> c_int;
     pub fn qn_objective_sparse_info(obj: *mut qn_objective, nnz: *mut usize, lanes_per_row: *mut c_int, n_long_rows: *mut usize, symmetric: *mut c_int) -> c_int;

@@ -497,6 +497,26 @@ impl DeviceObjective {
         status_to_result(unsafe { qn_multinomial_create(default_context(), m, n, n_classes, a_rowmajor.as_ptr(), labels.as_ptr() as *const c_void, w, mu, &mut h) })?;
         Ok(DeviceObjective { h, n: n * n_classes })
     }
+    /// Softmax regression with a sparse A in CSR (m x n; `indptr` has m + 1 entries, the columns of a row increase strictly), class-major as
+    /// `multinomial`: N = n_classes * n entries, with no limit on N.  The device keeps A and A' (24 bytes per nonzero) and feature-major copies of
+    /// the class-major vectors: no atomics, every sum in one fixed order.  Labels, weights and mu as `multinomial`.
+    pub fn sparse_multinomial(indptr: &[i64], indices: &[i64], data: &[Floating], labels: &[i32], n_classes: usize, weights: Option<&DVector<Floating>>,
+                              n: usize, mu: Floating) -> Result<Self, SolverError> {
+        let m = labels.len();
+        if indptr.len() != m + 1 || indices.len() != data.len() || weights.map_or(false, |w| w.len() != m) {
+            return Err(SolverError::ErrorInputParams);
+        }
+        let (no_index, no_value) = ([0i64; 1], [0.0; 1]); // an empty matrix: the library takes a dangling pointer for what it is
+        let ci = if indices.is_empty() { no_index.as_ptr() } else { indices.as_ptr() };
+        let va = if data.is_empty() { no_value.as_ptr() } else { data.as_ptr() };
+        let w = weights.map_or(std::ptr::null(), |w| w.as_ptr());
+        let mut h = std::ptr::null_mut();
+        status_to_result(unsafe {
+            qn_sparse_multinomial_create(default_context(), m, n, n_classes, data.len(), indptr.as_ptr() as *const c_void, ci as *const c_void, 8, va,
+                                         labels.as_ptr() as *const c_void, w, mu, &mut h)
+        })?;
+        Ok(DeviceObjective { h, n: n * n_classes })
+    }
     /// f = 1/2 x'Qx - b'x with a sparse Q in CSR (both triangles of a symmetric matrix; `indptr` has n + 1 entries, the columns of a row
     /// increase strictly): the large objective of the O(n) solvers (GpuSpectralProjectedGradient, GpuProjectedGradientDescent, GpuLBFGS).
     pub fn sparse_quadratic(indptr: &[i64], indices: &[i64], data: &[Floating], b: &DVector<Floating>) -> Result<Self, SolverError> {
