@@ -351,6 +351,14 @@ int qn_objective_hess_vec(qn_objective* obj, const double* v_host, double* q_hos
  * QN_ERROR_INPUT_PARAMS ("not built").  A dense or a sparse quadratic: x is not read (it may be NULL) and the call IS qn_objective_hess_vec -- the
  * same launches, the same bits.  (qn_objective_hess_vec itself still answers "not built" on log-sum-exp: it has no point to form p at.) */
 int qn_objective_hess_vec_at(qn_objective* obj, const double* x_host, const double* v_host, double* q_host, double* vhv);
+/* the DIAGONAL of the Hessian at a point: diag_host[j] = H(x)_jj for j < n, without the matrix -- what a Jacobi preconditioner divides by, and a
+ * scaling a binding may want for its own conjugate-gradient loop.  The weights at x (the kind's weights pass), then one pass over A with squared
+ * entries.  Logistic: M_j = sum_i d_i a_ij^2 + mu; log-sum-exp: M_j = sum_i p_i a_ij^2 - gbar_j^2 + mu (ONE stream of the dense A, 8 m n bytes, and a
+ * combine launch: csrc/qn_hess_diag.hip.h); sparse logistic: M_j = sum_{i in column j} d_i a_ij^2 + mu in one launch over the device's copy of A'
+ * (an empty column gives mu).  Rows with a zero weight add nothing.  Fixed summation orders, no atomics: the same bits for the same x from run to
+ * run, from object to object, and for int32 / int64 indices.  The dense kinds: built where the product is (n_pad <= 16384, one rank).  A multinomial
+ * or a sparse multinomial objective and the two quadratics: QN_ERROR_INPUT_PARAMS before anything is launched (not built). */
+int qn_objective_hess_diag_at(qn_objective* obj, const double* x_host, double* diag_host);
 
 /* ---------------------------------------------------------------------------------------------
  * Solvers: BFGS (bfgs.rs:4-127), DFP (dfp.rs), Broyden (broyden.rs), GradientDescent (gradient_descent.rs:7-82), Newton (newton/mod.rs).
@@ -504,6 +512,22 @@ int qn_solver_set_newton_cg(qn_solver* s, double eta_max, size_t max_inner, size
  * step started), the times rule 4 met curvature that was not positive, and the times rule 8 replaced z by g.  Any pointer may be NULL.
  * Another method: QN_ERROR_INPUT_PARAMS. */
 int qn_solver_newton_cg_state(qn_solver* s, size_t* inner_last, size_t* inner_total, size_t* hv_passes, size_t* neg_curv, size_t* fallbacks);
+/* NewtonCG's preconditioner for the inner conjugate-gradient loop.  QN_PRECOND_NONE (the default): plain CG, nothing changes.  QN_PRECOND_JACOBI: the
+ * diagonal of H(x_k), by the objective's own diagonal pass (qn_objective_hess_diag_at's launches) once per outer iteration behind the weights -- one
+ * more stream of A, about the price of one inner step.  minv_j = 1 / M_j where M_j > 0 and finite, else 1; p = minv o r + beta p with alpha = rz / kappa,
+ * beta = rz' / rz, rz = r.(minv o r); the loop still ends on the EUCLIDEAN residual, sqrt(r.r) <= eta sqrt(g.g), so eta means the same with and
+ * without it.  It pays where the columns of A differ in scale by orders of magnitude (2 to 4 times fewer inner steps); it buys nothing on
+ * well-scaled columns, where the extra pass is pure cost, and it can lose with m < n and a small mu.  QN_ERROR_INPUT_PARAMS: another method, another
+ * value; at qn_minimize, an objective without a Hessian diagonal (a multinomial pair, before anything is launched).  The setting survives calls and
+ * qn_solver_reset. */
+enum { QN_PRECOND_NONE = 0, QN_PRECOND_JACOBI = 1 };
+int qn_solver_set_newton_cg_preconditioner(qn_solver* s, int kind);
+/* the setting, and of the last qn_minimize: the directions that started with a diagonal pass, and how many entries of the LAST minv rule 2' set to 1
+ * (M_j not positive or not finite).  Any pointer may be NULL. */
+int qn_solver_newton_cg_precond_state(qn_solver* s, int* kind, size_t* diag_passes, size_t* floored_last);
+/* what the last diagonal pass of a preconditioned run left: M = diag H(x) into m_host and 1 / M by the rule above into minv_host, n entries each
+ * (either may be NULL).  x is the point of the run's last loop top: the last direction's, or the final point of a run that ended there.  QN_ERROR_INPUT_PARAMS: another method, or no run with QN_PRECOND_JACOBI has been made. */
+int qn_solver_newton_cg_precond_diag(qn_solver* s, double* m_host, double* minv_host);
 /* QN_LS_EXACT_QUADRATIC, of the last qn_minimize: the curvature passes, the accepted points (and forced re-evaluations of x) that the objective
  * evaluated -- the first evaluation at x is not counted --, and the last search's step and curvature d'Qd.  Any pointer may be NULL.  A solver
  * outside the first-order family: QN_ERROR_INPUT_PARAMS. */

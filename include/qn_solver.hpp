@@ -281,6 +281,12 @@ class LogSumExp {
         check(qn_objective_hess_vec_at(h_, x.data(), v.data(), q.data(), &c));
         return {std::move(q), c};
     }
+    DVector hess_diag_at(const DVector& x) const { // diag H(x): the weights at x, then one pass over A with squared entries; no matrix
+        if (x.size() != n_) throw SolverError{SolverError::ErrorInputParams, "x does not have the objective's n entries"};
+        DVector d(n_);
+        check(qn_objective_hess_diag_at(h_, x.data(), d.data()));
+        return d;
+    }
 };
 
 // a device-resident regularised logistic regression, f = sum_i w_i log(1 + exp(-y_i a_i'x)) + mu/2 ||x||^2 (A is m x n row-major and dense).  y_i is
@@ -311,6 +317,12 @@ class Logistic {
         Floating c = 0;
         check(qn_objective_hess_vec_at(h_, x.data(), v.data(), q.data(), &c));
         return {std::move(q), c};
+    }
+    DVector hess_diag_at(const DVector& x) const { // diag H(x): the weights at x, then one pass over A with squared entries; no matrix
+        if (x.size() != n_) throw SolverError{SolverError::ErrorInputParams, "x does not have the objective's n entries"};
+        DVector d(n_);
+        check(qn_objective_hess_diag_at(h_, x.data(), d.data()));
+        return d;
     }
 };
 
@@ -348,6 +360,12 @@ class SparseLogistic {
         Floating c = 0;
         check(qn_objective_hess_vec_at(h_, x.data(), v.data(), q.data(), &c));
         return {std::move(q), c};
+    }
+    DVector hess_diag_at(const DVector& x) const { // diag H(x): the weights at x, then one pass over A with squared entries; no matrix
+        if (x.size() != n_) throw SolverError{SolverError::ErrorInputParams, "x does not have the objective's n entries"};
+        DVector d(n_);
+        check(qn_objective_hess_diag_at(h_, x.data(), d.data()));
+        return d;
     }
     void set_lanes(int rows, int cols) { check(qn_sparse_logistic_set_lanes(h_, rows, cols)); } // 0: automatic
     size_t nnz() const { size_t v = 0; check(qn_sparse_logistic_info(h_, &v, nullptr, nullptr, nullptr, nullptr)); return v; }
@@ -822,6 +840,13 @@ class NewtonCG : public LineSearchSolver<QN_NEWTON_CG> {
         check(qn_solver_set_newton_cg(this->handle(), eta_max, max_inner, chunk));
         return std::move(*this);
     }
+    // the inner loop's preconditioner: QN_PRECOND_NONE (the default) or QN_PRECOND_JACOBI, the diagonal of H(x_k) by one more pass of A per outer
+    // iteration.  It pays where the columns of A differ in scale by orders of magnitude; on well-scaled columns, or with m < n and a small mu, it buys
+    // nothing or loses.  LogSumExp, Logistic and SparseLogistic only (another objective: ErrorInputParams at minimize)
+    void set_preconditioner(int kind) { check(qn_solver_set_newton_cg_preconditioner(this->handle(), kind)); }
+    int preconditioner() const { int v = 0; check(qn_solver_newton_cg_precond_state(this->handle(), &v, nullptr, nullptr)); return v; }
+    size_t diag_passes() const { size_t v = 0; check(qn_solver_newton_cg_precond_state(this->handle(), nullptr, &v, nullptr)); return v; }
+    size_t diag_floored() const { size_t v = 0; check(qn_solver_newton_cg_precond_state(this->handle(), nullptr, nullptr, &v)); return v; }
     size_t inner_last() const { size_t v = 0; check(qn_solver_newton_cg_state(this->handle(), &v, nullptr, nullptr, nullptr, nullptr)); return v; }
     size_t inner_total() const { size_t v = 0; check(qn_solver_newton_cg_state(this->handle(), nullptr, &v, nullptr, nullptr, nullptr)); return v; }
     size_t hv_passes() const { size_t v = 0; check(qn_solver_newton_cg_state(this->handle(), nullptr, nullptr, &v, nullptr, nullptr)); return v; }

@@ -20,6 +20,7 @@ LBFGS_MAX_M = 32
 NONLINEAR_CG = 13  # nonlinear conjugate gradient (unbounded only); no counterpart in the reference
 NEWTON_CG = 14  # truncated Newton on the log-sum-exp Hessian-vector product (unbounded only); no counterpart in the reference
 CG_FR, CG_PR_PLUS, CG_HS_PLUS, CG_DY, CG_HZ = 0, 1, 2, 3, 4  # qn_solver_set_cg's variants
+PRECOND_NONE, PRECOND_JACOBI = 0, 1  # qn_solver_set_newton_cg_preconditioner's kinds
 UNIQUE_ID_BYTES = 128
 
 dp = C.POINTER(C.c_double)
@@ -144,6 +145,7 @@ SYMBOLS = [
     ("qn_objective_hessian", C.c_int, [C.c_void_p, dp, dp]),
     ("qn_objective_hess_vec", C.c_int, [C.c_void_p, dp, dp, dp]),
     ("qn_objective_hess_vec_at", C.c_int, [C.c_void_p, dp, dp, dp, dp]),
+    ("qn_objective_hess_diag_at", C.c_int, [C.c_void_p, dp, dp]),
     ("qn_solver_create", C.c_int, [C.c_void_p, C.c_int, C.c_double, dp, C.c_size_t, C.POINTER(C.c_void_p)]),
     ("qn_solver_destroy", None, [C.c_void_p]),
     ("qn_solver_reset", C.c_int, [C.c_void_p, dp]),
@@ -159,6 +161,9 @@ SYMBOLS = [
     ("qn_solver_cg_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int), dp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     ("qn_solver_set_newton_cg", C.c_int, [C.c_void_p, C.c_double, C.c_size_t, C.c_size_t]),
     ("qn_solver_newton_cg_state", C.c_int, [C.c_void_p] + [C.POINTER(C.c_size_t)] * 5),
+    ("qn_solver_set_newton_cg_preconditioner", C.c_int, [C.c_void_p, C.c_int]),
+    ("qn_solver_newton_cg_precond_state", C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    ("qn_solver_newton_cg_precond_diag", C.c_int, [C.c_void_p, dp, dp]),
     ("qn_solver_exact_state", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), dp, dp]),
     ("qn_minimize", C.c_int, [C.c_void_p, C.POINTER(LineSearchStruct), C.POINTER(OracleStruct), C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("qn_compute_step_len", C.c_int, [C.c_void_p, C.POINTER(LineSearchStruct), dp, C.c_double, dp, dp, C.c_size_t, C.POINTER(OracleStruct), C.c_size_t,

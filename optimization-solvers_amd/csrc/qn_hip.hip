@@ -80,6 +80,8 @@ extern "C" const char* qn_status_string(int status) {
 #include "qn_vec_exact.hip.h"
 // the log-sum-exp Hessian-vector product (q = H v in one stream of A) and qn_objective_hess_vec_at: behind every existing kernel
 #include "qn_lse_hv.hip.h"
+// the diagonal of the Hessian of the kinds that share that product (one stream of A with squared entries) and qn_objective_hess_diag_at
+#include "qn_hess_diag.hip.h"
 // the logistic objective (two launches per evaluation; its Hessian-vector product is the log-sum-exp one's kernels): behind every existing kernel
 #include "qn_logistic.hip.h"
 #include "qn_host_logistic.hip.h"

@@ -34,6 +34,7 @@ static const QnObjOps kLogitOps = {
     /* no_rows */ nullptr,
     /* no_hessian */ "the dense Hessian of a logistic objective is not built: hess_vec_at gives H(x) v in one stream of A",
     /* no_curvature */ "qn_objective_hess_vec: the Hessian of a logistic objective depends on x: use qn_objective_hess_vec_at",
+    /* hess_diag, its launches and bytes */ dense_enqueue_hess_diag, 2, dense_stream_bytes,
 };
 
 // the device side of a new logistic objective: A, yw and every buffer the launches below use

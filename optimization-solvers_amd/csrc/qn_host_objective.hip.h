@@ -150,7 +150,14 @@ struct QnObjOps {
     // capabilities, NULL where the kind has it, otherwise the refusal: the dense quasi-Newton family with the control-step solvers and Newton;
     // qn_objective_get_rows; a dense Hessian (the projected Newton pair wants `hessian` NULL as well: a device quadratic); qn_objective_hess_vec
     const char *no_dense_family, *no_rows, *no_hessian, *no_curvature;
+    // M_j = H(x)_jj -> m_dev with the weights of the last pass, and rule 2''s 1 / M (qn_newton_cg.hip.h) -> minv_dev where that is not NULL: n_pad
+    // entries each, unpredicated.  NULL: the kind has no diagonal, and every caller refuses before anything is launched.  Its launches and the
+    // bytes it moves, as the members above count them
+    int (*hess_diag)(qn_objective* o, double* m_dev, double* minv_dev); int diag_launches;
+    uint64_t (*diag_bytes)(const qn_objective* o);
 };
+// the dense kinds' diagonal (qn_hess_diag.hip.h), named by the tables of LogSumExp and Logistic
+static int dense_enqueue_hess_diag(qn_objective* o, double* m_dev, double* minv_dev);
 #define QN_VEC_FAMILY_ONLY(name) "a " name " objective runs under SPG, projected gradient, LBFGS / ProjectedLBFGS, NonlinearCG and NewtonCG (the dense quasi-Newton family, the control-step solvers and Newton: out of scope)"
 // the tables of the kinds created in this file live where all their launches are visible: qn_vec_exact.hip.h, qn_lse_hv.hip.h, qn_sparse.hip.h
 static const QnObjOps* quad_ops();

@@ -100,6 +100,19 @@ static int slog_enqueue_hess_vec(qn_objective* o, const double* v_dev, const dou
     return QN_OK;
 }
 
+// enqueue M = diag H(x) into m_dev[0 .. n) and, where minv_dev is not NULL, rule 2''s 1 / M into minv_dev[0 .. n), with d from `wp.w`: ONE launch
+// over A', unpredicated.  Bytes by the model of qn_stats.obj_bytes: 12 nnz + 4 (n + 1) of A', d (8 m), M and 1 / M (16 n)
+static int slog_enqueue_hess_diag(qn_objective* o, double* m_dev, double* minv_dev) {
+    const QnSlogCsr& c = o->sl.at;
+    QnSlogDiagArgs a{};
+    a.row_ptr = c.row_ptr; a.col = c.col; a.val = c.val; a.wg_row_start = c.cut; a.long_rows = c.longs;
+    a.d = o->wp.w; a.m_out = m_dev; a.minv_out = minv_dev; a.mu = o->sl.mu; a.G = c.G; a.n_long = c.n_long;
+    QNCHK(slog_diag_launch(o->ctx->stream, a, c.lanes));
+    HIPCHK(hipGetLastError());
+    return QN_OK;
+}
+static uint64_t slog_diag_bytes(const qn_objective* o) { return 12ull * o->sl.nnz + 4ull * (o->n + 1) + 8ull * o->sl.m + 16ull * o->n; }
+
 // the table's evaluation: d goes to the trial buffer, as the logistic's
 static int slog_eval_trial(qn_objective* o, const double* x, double* f, double* g, int which, const QnObjWork*) { return slog_enqueue_eval(o, x, f, g, o->wp.w_trial, which); }
 // v'Hv: one value, folded by the product's third launch
@@ -116,6 +129,7 @@ static const QnObjOps kSlogOps = {
     /* no_rows */ "a sparse logistic objective has no dense rows / Hessian",
     /* no_hessian */ "a sparse logistic objective has no dense rows / Hessian: hess_vec_at gives H(x) v",
     /* no_curvature */ "qn_objective_hess_vec: the Hessian of a sparse logistic objective depends on x: use qn_objective_hess_vec_at",
+    /* hess_diag, its launches and bytes */ slog_enqueue_hess_diag, 1, slog_diag_bytes,
 };
 
 // the device side of a new objective: both copies, yw and every buffer the launches below use.  The staging vectors live until the stream is idle.

@@ -43,6 +43,7 @@ static int exact_state_alloc(qn_solver* s); // QN_LS_EXACT_QUADRATIC: qn_vec_exa
 static int tn_state_alloc(qn_solver* s); // QN_NEWTON_CG: qn_host_newton_cg.hip.h
 static int tn_check(const qn_solver* s, const qn_linesearch* ls, const qn_objective* obj, int ls_only);
 static int tn_enqueue_direction(VecRun& r, bool fresh, uint64_t* weights_passes);
+static int tn_precond_alloc(qn_solver* s);
 static int exact_enqueue_step(VecRun& r);
 static int exact_enqueue_advance(VecRun& r);
 static int vec_grid(size_t np) { // a function of n alone: four 16-byte accesses per thread until 4 workgroups per CU are out
@@ -70,7 +71,8 @@ static void vec_state_reset(qn_solver* s) { // back to the state right after ::n
     h->has_lambda = 0; h->lambda = 0.0; h->have_eval = 0; h->ring_len = 0; h->k = 0; h->n_iter = 0;
     h->lb_kmem = 0; h->lb_head = 0; h->lb_gamma = 1.0; h->lb_resets = 0; // QN_LBFGS: an empty memory (lb_m and the scaling switch are settings: kept)
     h->cg_has_p = 0; h->cg_beta = 0.0; h->cg_since = 0; h->cg_restarts = 0; // QN_NONLINEAR_CG: no direction yet (the variant, nu and restart_every are settings: kept)
-    h->tn_state = 0; h->tn_inner_last = 0; h->tn_inner_total = 0; h->tn_hv_passes = 0; h->tn_neg_curv = 0; h->tn_fallbacks = 0; // QN_NEWTON_CG: no inner loop has run (eta_max, max_inner and chunk are settings: kept)
+    h->tn_state = 0; h->tn_inner_last = 0; h->tn_inner_total = 0; h->tn_hv_passes = 0; h->tn_neg_curv = 0; h->tn_fallbacks = 0; // QN_NEWTON_CG: no inner loop has run (eta_max, max_inner, chunk and the preconditioner are settings: kept)
+    h->tn_diag_passes = 0; h->tn_floored_last = 0;
     h->ex_since = 0; h->ex_g_true = 0; // QN_LS_EXACT_QUADRATIC: no accepted point yet (the next evaluation at x is the objective's: have_eval is 0)
     h->has_sy = 0; h->s_norm = 0.0; h->y_norm = 0.0; // (the Cholesky factor of a device quadratic's Hessian is kept: it is keyed on the objective)
 }
@@ -294,6 +296,8 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     if (tn) { // the inner loop's cap for this call; the counters speak of this call
         h->tn_cap = h->tn_max_inner > 0 ? h->tn_max_inner : (int32_t)std::min<size_t>(s->n, 100);
         h->tn_state = 0; h->tn_inner_last = 0; h->tn_inner_total = 0; h->tn_hv_passes = 0; h->tn_neg_curv = 0; h->tn_fallbacks = 0;
+        h->tn_diag_passes = 0; h->tn_floored_last = 0;
+        QNCHK(tn_precond_alloc(s)); // (Jacobi: M and 1 / M, on first use)
     }
     uint64_t tn_weights = 0;
     h->w_boxed = wolfe_boxed ? 1 : 0; h->w_err = 0; h->tr_ls_cases = 0; h->tr_ndigits = 0;
@@ -340,6 +344,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
             if (ops->vec_counted) s->stats.obj_bytes += h->n_evals * ops->eval_bytes(r.obj);
             if (exact) s->stats.obj_bytes += h->ex_passes * ops->curv_bytes(r.obj);
             if (tn) s->stats.obj_bytes += (uint64_t)h->tn_hv_passes * ops->hv_bytes(r.obj) + tn_weights * ops->weights_bytes(r.obj);
+            if (tn && h->tn_precond) s->stats.obj_bytes += tn_weights * ops->diag_bytes(r.obj); // (one diagonal pass behind every weights pass)
         }
         stats_add_totals(s); // (no update passes, one rank: total_h_* and total_xchg_* stay)
         s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u) | (lbfgs ? QN_PATH_LBFGS : 0u) | (cg ? QN_PATH_CG : 0u) | (exact ? QN_PATH_EXACT : 0u) | (tn ? QN_PATH_NEWTON_CG : 0u);

@@ -240,6 +240,7 @@ static const QnObjOps kLseOps = {
     /* bytes: eval, product, weights, curvature */ lse_eval_bytes, dense_stream_bytes, lse_weights_bytes, nullptr,
     /* no_dense_family */ nullptr, /* no_rows */ nullptr, /* no_hessian */ nullptr,
     /* no_curvature */ "qn_objective_hess_vec: not built for this objective (a dense or a sparse quadratic has a Hessian-vector product)",
+    /* hess_diag, its launches and bytes */ dense_enqueue_hess_diag, 2, dense_stream_bytes,
 };
 static const QnObjOps* lse_ops() { return &kLseOps; }
 

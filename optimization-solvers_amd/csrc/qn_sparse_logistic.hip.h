@@ -177,3 +177,79 @@ static int slog_launch(hipStream_t st, const QnSlogArgs& a, int lanes, const QnV
     }
     return QN_OK;
 }
+
+// ---- the diagonal of the Hessian: M_j = sum_{i in column j} d_i a_ij^2 + mu over A' (what NewtonCG's Jacobi preconditioner divides by) ----
+//   slog_diag_kernel<L>   slog_cols_kernel's sibling: the same geometry over the rows of A' (the static cut, L lanes per row, the xor tree L/2 .. 1,
+//                         a long row summed by workgroup G + k, thread t: entries t, t + 256, ...; then the block sum).  THE ROUNDING ORDER, per
+//                         entry: s = val val (rounded), then s d[col] (rounded), added in the pass's order (plain adds).  M_j = acc + mu; where
+//                         `minv` is not NULL the same launch writes 1 / M_j by IEEE division when M_j > 0 and finite, else 1 (hd_minv).  An empty
+//                         column gives M_j = mu.  No shares, no finish launch, unpredicated; entries n .. n_pad are never written.
+struct QnSlogDiagArgs {
+    const int* row_ptr;      // n + 1: the rows of A'
+    const int* col;          // nnz: row numbers of A
+    const double* val;       // nnz
+    const int* wg_row_start; // G + 1
+    const int* long_rows;    // n_long
+    const double* d;         // the weights of the last pass (m)
+    double* m_out;           // n entries written
+    double* minv_out;        // n entries written, or NULL
+    double mu;
+    int G, n_long;
+};
+
+__device__ __forceinline__ double slog_diag_product(const QnSlogDiagArgs& a, int j) {
+    const double v = a.val[j];
+    const double s = v * v;
+    return s * a.d[a.col[j]];
+}
+
+__device__ __forceinline__ void slog_diag_end(const QnSlogDiagArgs& a, int j, double acc) {
+    const double mj = acc + a.mu;
+    a.m_out[j] = mj;
+    if (a.minv_out) a.minv_out[j] = hd_minv(mj);
+}
+
+template <int L>
+__global__ __launch_bounds__(SPQ_TPB) void slog_diag_kernel(const QnSlogDiagArgs a) {
+    __shared__ double lds[16];
+    const int tid = threadIdx.x;
+    if ((int)blockIdx.x >= a.G) { // one long row of A' (a dense column of A), the whole workgroup
+        const int i = a.long_rows[blockIdx.x - a.G];
+        const int j1 = a.row_ptr[i + 1];
+        double acc[1] = {0.0};
+        for (int j = a.row_ptr[i] + tid; j < j1; j += SPQ_TPB) acc[0] = acc[0] + slog_diag_product(a, j);
+        ctl_block_sum<1>(acc, lds);
+        if (tid == 0) slog_diag_end(a, i, acc[0]);
+        return;
+    }
+    constexpr int RPT = SPQ_TPB / L; // rows per trip
+    const int r0 = a.wg_row_start[blockIdx.x], r1 = a.wg_row_start[blockIdx.x + 1];
+    const int sub = tid / L, l = tid % L;
+    for (int base = r0; base < r1; base += RPT) {
+        const int i = base + sub;
+        int j0 = 0, j1 = 0;
+        if (i < r1) { j0 = a.row_ptr[i]; j1 = a.row_ptr[i + 1]; }
+        const bool regular = j1 - j0 <= SPQ_LONG_ROW; // (a long row: nothing here, its own workgroup stores its entry)
+        double acc = 0.0;
+        if (regular)
+            for (int j = j0 + l; j < j1; j += L) acc = acc + slog_diag_product(a, j);
+#pragma unroll
+        for (int off = L / 2; off >= 1; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
+        if (l == 0 && i < r1 && regular) slog_diag_end(a, i, acc);
+    }
+}
+
+static int slog_diag_launch(hipStream_t st, const QnSlogDiagArgs& a, int lanes) {
+    const dim3 grid(a.G + a.n_long), tpb(SPQ_TPB);
+    switch (lanes) {
+    case 1: hipLaunchKernelGGL(slog_diag_kernel<1>, grid, tpb, 0, st, a); break;
+    case 2: hipLaunchKernelGGL(slog_diag_kernel<2>, grid, tpb, 0, st, a); break;
+    case 4: hipLaunchKernelGGL(slog_diag_kernel<4>, grid, tpb, 0, st, a); break;
+    case 8: hipLaunchKernelGGL(slog_diag_kernel<8>, grid, tpb, 0, st, a); break;
+    case 16: hipLaunchKernelGGL(slog_diag_kernel<16>, grid, tpb, 0, st, a); break;
+    case 32: hipLaunchKernelGGL(slog_diag_kernel<32>, grid, tpb, 0, st, a); break;
+    case 64: hipLaunchKernelGGL(slog_diag_kernel<64>, grid, tpb, 0, st, a); break;
+    default: return fail(QN_ERROR_INPUT_PARAMS, "sparse logistic: lanes must be 1, 2, 4, 8, 16, 32 or 64");
+    }
+    return QN_OK;
+}

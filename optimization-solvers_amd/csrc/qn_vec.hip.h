@@ -112,6 +112,10 @@ struct QnVecCtl {
     int32_t tn_zg, tn_use_g;          // rule 4 at j = 0: z = g; the direction is -g (rule 4 at j = 0, or rule 8's safeguard)
     double tn_gg, tn_sqgg, tn_rr, tn_eta, tn_kappa, tn_alpha, tn_beta, tn_gz;
     uint64_t tn_inner_last, tn_inner_total, tn_hv_passes, tn_neg_curv, tn_fallbacks;
+    // ---- its preconditioner (qn_newton_cg.hip.h, rules 1' to 7'): the setting; r.(minv o r) beside tn_rr; counters of this call ----
+    int32_t tn_precond, _pad3;        // QN_PRECOND_NONE / QN_PRECOND_JACOBI
+    double tn_rz;
+    uint64_t tn_diag_passes, tn_floored_last; // directions started with a diagonal; entries of the last minv that rule 2' set to 1
 };
 #define QN_TN_IDLE 0
 #define QN_TN_RUNNING 1

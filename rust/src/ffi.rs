@@ -47,6 +47,9 @@ pub const QN_CG_PR_PLUS: c_int = 1;
 pub const QN_CG_HS_PLUS: c_int = 2;
 pub const QN_CG_DY: c_int = 3;
 pub const QN_CG_HZ: c_int = 4;
+// qn_solver_set_newton_cg_preconditioner's kinds
+pub const QN_PRECOND_NONE: c_int = 0;
+pub const QN_PRECOND_JACOBI: c_int = 1;
 
 // qn_option (ABI 5): what rounds 1-5 selected through negative codes of qn_solver_set_tiling; value != 0 on, 0 off
 pub const QN_OPT_GENERIC_KERNELS: c_int = 1;
@@ -261,6 +264,7 @@ extern "C" {
     pub fn qn_objective_hessian(obj: *mut qn_objective, x_host: *const f64, h_colmajor_host: *mut f64) -> c_int;
     pub fn qn_objective_hess_vec(obj: *mut qn_objective, v_host: *const f64, q_host: *mut f64, vqv: *mut f64) -> c_int;
     pub fn qn_objective_hess_vec_at(obj: *mut qn_objective, x_host: *const f64, v_host: *const f64, q_host: *mut f64, vhv: *mut f64) -> c_int;
+    pub fn qn_objective_hess_diag_at(obj: *mut qn_objective, x_host: *const f64, diag_host: *mut f64) -> c_int;
 
     // ---- solvers ----
     pub fn qn_solver_create(ctx: *mut qn_context, method: c_int, tol: f64, x0_host: *const f64, n: usize, out: *mut *mut qn_solver) -> c_int;
@@ -277,6 +281,9 @@ extern "C" {
     pub fn qn_solver_cg_state(s: *mut qn_solver, variant: *mut c_int, beta: *mut f64, restarts: *mut usize, since_restart: *mut usize) -> c_int;
     pub fn qn_solver_set_newton_cg(s: *mut qn_solver, eta_max: f64, max_inner: usize, chunk: usize) -> c_int;
     pub fn qn_solver_newton_cg_state(s: *mut qn_solver, inner_last: *mut usize, inner_total: *mut usize, hv_passes: *mut usize, neg_curv: *mut usize, fallbacks: *mut usize) -> c_int;
+    pub fn qn_solver_set_newton_cg_preconditioner(s: *mut qn_solver, kind: c_int) -> c_int;
+    pub fn qn_solver_newton_cg_precond_state(s: *mut qn_solver, kind: *mut c_int, diag_passes: *mut usize, floored_last: *mut usize) -> c_int;
+    pub fn qn_solver_newton_cg_precond_diag(s: *mut qn_solver, m_host: *mut f64, minv_host: *mut f64) -> c_int;
     pub fn qn_solver_exact_state(s: *mut qn_solver, curvature_passes: *mut usize, refreshes: *mut usize, last_t: *mut f64, last_curvature: *mut f64) -> c_int;
     pub fn qn_solver_reset(s: *mut qn_solver, x0_host: *const f64) -> c_int;
     pub fn qn_minimize(s: *mut qn_solver, ls: *mut qn_linesearch, oracle: *const qn_oracle, max_iter_solver: usize, max_iter_line_search: usize, callback: qn_callback_fn, callback_user: *mut c_void) -> c_int;

@@ -586,6 +586,16 @@ impl DeviceObjective {
         status_to_result(unsafe { qn_objective_hess_vec_at(self.h, x.as_ptr(), v.as_ptr(), q.as_mut_ptr(), &mut c) })?;
         Ok((q, c))
     }
+    /// diag H(x) without the matrix: the weights at x, then one pass over A with squared entries.  Log-sum-exp, logistic (n_pad <= 16384,
+    /// one rank) and sparse logistic; every other objective: `ErrorInputParams` (not built).
+    pub fn hess_diag_at(&self, x: &DVector<Floating>) -> Result<DVector<Floating>, SolverError> {
+        if x.len() != self.n {
+            return Err(SolverError::ErrorInputParams);
+        }
+        let mut d = DVector::zeros(self.n);
+        status_to_result(unsafe { qn_objective_hess_diag_at(self.h, x.as_ptr(), d.as_mut_ptr()) })?;
+        Ok(d)
+    }
 }
 
 impl Drop for DeviceObjective {
@@ -1000,12 +1010,36 @@ impl GpuNewtonCg {
         assert_eq!(unsafe { qn_solver_set_newton_cg(self.core.h, eta_max, max_inner, chunk) }, QN_OK, "{}", last_error());
         self
     }
+    /// the inner loop's preconditioner: `Preconditioner::None` (the default) or `Preconditioner::Jacobi`, the diagonal of H(x_k) by one more pass
+    /// of A per outer iteration.  It pays where the columns of A differ in scale by orders of magnitude; on well-scaled columns, or with m < n
+    /// and a small mu, it buys nothing or loses.  Log-sum-exp, logistic and sparse logistic objectives only.
+    pub fn preconditioner(self, kind: Preconditioner) -> Self {
+        let code = match kind {
+            Preconditioner::None => QN_PRECOND_NONE,
+            Preconditioner::Jacobi => QN_PRECOND_JACOBI,
+        };
+        assert_eq!(unsafe { qn_solver_set_newton_cg_preconditioner(self.core.h, code) }, QN_OK, "{}", last_error());
+        self
+    }
+    /// (the setting, directions of the last minimize that started with a diagonal pass, entries of the last 1 / M that were set to 1)
+    pub fn precond_state(&self) -> (Preconditioner, usize, usize) {
+        let (mut kind, mut passes, mut floored) = (0 as c_int, 0usize, 0usize);
+        assert_eq!(unsafe { qn_solver_newton_cg_precond_state(self.core.h, &mut kind, &mut passes, &mut floored) }, QN_OK, "{}", last_error());
+        (if kind == QN_PRECOND_JACOBI { Preconditioner::Jacobi } else { Preconditioner::None }, passes, floored)
+    }
     /// (inner steps of the last direction, of all directions, Hessian-vector products, non-positive curvature met, rule-8 fallbacks)
     pub fn newton_cg_state(&self) -> (usize, usize, usize, usize, usize) {
         let (mut last, mut total, mut hv, mut neg, mut fb) = (0usize, 0usize, 0usize, 0usize, 0usize);
         assert_eq!(unsafe { qn_solver_newton_cg_state(self.core.h, &mut last, &mut total, &mut hv, &mut neg, &mut fb) }, QN_OK, "{}", last_error());
         (last, total, hv, neg, fb)
     }
+}
+
+/// `qn_solver_set_newton_cg_preconditioner`'s kinds
+#[derive(Clone, Copy, Debug, PartialEq, Eq)]
+pub enum Preconditioner {
+    None,
+    Jacobi,
 }
 
 /// `qn_solver_set_cg`'s variants
