@@ -562,6 +562,18 @@ int qn_solver_set_k(qn_solver* s, size_t k);               /* k_mut() (bfgs.rs:5
 double qn_solver_tol(const qn_solver* s);                  /* tol() */
 int qn_solver_get_x(qn_solver* s, double* out_host);       /* x() / xk() */
 int qn_solver_set_x(qn_solver* s, const double* x_host);   /* xk_mut() */
+/* The vector family (SPG, projected gradient, projected Newton, L-BFGS, NonlinearCG, NewtonCG), for an audit of a run from its own vectors: n
+ * doubles copied from the solver's vectors on its stream; no launch, and a run that never calls them is unchanged bit for bit.
+ * get_direction: the direction of the last accepted iteration.  Inside the callback this is d_k of the iteration just reported (the next batch is
+ * not enqueued before the callback returns).  QN_ERROR_INPUT_PARAMS when none is held: before the first accepted iteration of a call, and after a
+ * call whose last loop top ended it (convergence: that loop top left P(x - g) - x in the vector, which was never searched).
+ * get_gradient: the gradient of the evaluation held at the current x.  Inside the callback, on a memoised oracle, this is g_{k+1}, the accepted
+ * trial's gradient; after a call that converged it is the gradient that passed the test.  QN_ERROR_INPUT_PARAMS when no evaluation at x is held:
+ * nothing evaluated yet (an iteration cap of 0 evaluates nothing, as in the reference), an oracle that is not memoised (the next loop top
+ * evaluates x itself), or x set since.  Under ExactQuadratic it is the gradient the run holds, which may be the recurrence's.
+ * Another method: QN_ERROR_INPUT_PARAMS. */
+int qn_solver_get_direction(qn_solver* s, double* d_host);
+int qn_solver_get_gradient(qn_solver* s, double* g_host);
 int qn_solver_s_norm(qn_solver* s, double* out, int* is_some); /* s_norm(): Option<f64> */
 int qn_solver_y_norm(qn_solver* s, double* out, int* is_some); /* y_norm(): Option<f64> */
 int qn_solver_next_iterate_too_close(qn_solver* s, int* out);          /* bfgs.rs:15-20 */

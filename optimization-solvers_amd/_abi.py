@@ -174,6 +174,8 @@ SYMBOLS = [
     ("qn_solver_tol", C.c_double, [C.c_void_p]),
     ("qn_solver_get_x", C.c_int, [C.c_void_p, dp]),
     ("qn_solver_set_x", C.c_int, [C.c_void_p, dp]),
+    ("qn_solver_get_direction", C.c_int, [C.c_void_p, dp]),
+    ("qn_solver_get_gradient", C.c_int, [C.c_void_p, dp]),
     ("qn_solver_s_norm", C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int)]),
     ("qn_solver_y_norm", C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int)]),
     ("qn_solver_next_iterate_too_close", C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),

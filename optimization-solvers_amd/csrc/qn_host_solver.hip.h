@@ -111,6 +111,7 @@ struct qn_solver {
     uint64_t pn_factor_serial = 0;
     int pn_reuse = 1;
     uint64_t pn_factorisations = 0;
+    bool vec_d_searched = false; // V.d holds the direction of the last accepted iteration (qn_solver_get_direction): the pump's last batch accepted one
     DevBuf<double> lb_ring, lb_part, lb_small; // QN_LBFGS (qn_lbfgs.hip.h): S and Y, [2][lb_m + 1][n_pad]; the Gram kernel's shares; Gram matrices and coefficients
     DevBuf<double> cg_p, cg_part; // QN_NONLINEAR_CG (qn_cg.hip.h): the direction last searched, [n_pad]; the accept kernel's shares, [QN_CG_NQ][QN_VEC_MAXG]
     DevBuf<double> tn_pc;    // its Jacobi preconditioner: M = diag H(x_k) and 1 / M, [2][n_pad] (allocated by the first run that asks for it)
@@ -695,6 +696,7 @@ extern "C" int qn_solver_reset(qn_solver* s, const double* x0_host) {
     }
     HIPCHK(hipMemcpyAsync(s->V.x, xp.empty() ? x0_host : xp.data(), s->n * sizeof(double), hipMemcpyHostToDevice, st));
     memset(s->hctl, 0, sizeof(QnCtl));
+    s->vec_d_searched = false;
     vec_state_reset(s);
     return poke_ctl(s);
 }

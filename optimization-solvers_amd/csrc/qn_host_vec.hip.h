@@ -96,6 +96,31 @@ extern "C" int qn_solver_spg_lambda(qn_solver* s, double* out, int* is_some) {
     return QN_OK;
 }
 
+// The two vectors an audit of a run needs exactly (tests/newton_cg_audit.py): n doubles copied from the solver's own vectors on its stream.  No
+// launch, and nothing a run reads is written: a run that never calls them is the run it was.  INSIDE THE CALLBACK the pump has synchronised
+// (vec_peek) and enqueued nothing behind the batch that accepted iteration k: V.d is still d_k -- the next batch's vec_dir_kernel is what
+// overwrites it -- and V.g is g(x_{k+1}) where the accept kernel stored the accepted trial's gradient (a memoised oracle: have_eval).
+extern "C" int qn_solver_get_direction(qn_solver* s, double* d_host) {
+    if (!s || !d_host) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
+    if (!vec_method(s->method)) return fail(QN_ERROR_INPUT_PARAMS, "get_direction: built for the vector family (SPG, projected gradient, projected Newton, L-BFGS, NonlinearCG, NewtonCG)");
+    if (!s->vec_d_searched)
+        return fail(QN_ERROR_INPUT_PARAMS, "get_direction: no searched direction is held (no iteration has been accepted, or the last loop top ended the run and left P(x - g) - x in its place)");
+    HIPCHK(hipSetDevice(s->ctx->device));
+    HIPCHK(hipMemcpyAsync(d_host, s->V.d, s->n * sizeof(double), hipMemcpyDeviceToHost, s->ctx->stream));
+    HIPCHK(hipStreamSynchronize(s->ctx->stream));
+    return QN_OK;
+}
+extern "C" int qn_solver_get_gradient(qn_solver* s, double* g_host) {
+    if (!s || !g_host) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
+    if (!vec_method(s->method)) return fail(QN_ERROR_INPUT_PARAMS, "get_gradient: built for the vector family (SPG, projected gradient, projected Newton, L-BFGS, NonlinearCG, NewtonCG)");
+    if (!s->hvctl || !s->hvctl->have_eval || !s->hctl->have_cur_eval)
+        return fail(QN_ERROR_INPUT_PARAMS, "get_gradient: no evaluation at the current x is held (nothing has been evaluated yet -- an iteration cap of 0 evaluates nothing --, the oracle is not memoised, or x was set since)");
+    HIPCHK(hipSetDevice(s->ctx->device));
+    HIPCHK(hipMemcpyAsync(g_host, s->V.g, s->n * sizeof(double), hipMemcpyDeviceToHost, s->ctx->stream));
+    HIPCHK(hipStreamSynchronize(s->ctx->stream));
+    return QN_OK;
+}
+
 // ComputeDirection::compute_direction on its own: P(x - lambda g) - x (spg.rs:76-86), P(x - g) - x (projected_gradient_descent.rs:51-60)
 static int vec_compute_direction(qn_solver* s, const double* g_host, double* d_host) {
     const size_t n = s->n, np = s->T.n_pad;
@@ -326,7 +351,11 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     const int G = a.G;
     const bool host_oracle = o->kind == QN_ORACLE_HOST;
     const size_t vb = np * sizeof(double);
-    int64_t k_seen = 0;
+    int64_t k_seen = 0, k_batch = 0;
+    s->vec_d_searched = false;
+    // qn_solver_get_direction / qn_solver_get_gradient (host flags only): a batch that accepted an iteration leaves the searched direction in V.d;
+    // the memo flag is the batch's own, so that a callback reads what the run holds now
+    auto batch_seen = [&]() { s->vec_d_searched = h->k != k_batch; k_batch = h->k; s->hctl->have_cur_eval = h->have_eval; };
     s->pn_factorisations = 0;
     // the run's bookkeeping, also when a batch fails after some iterations (a failed Cholesky, a closure's error): k, the counters, the
     // path and s_norm / y_norm speak of this call, not of the one before
@@ -382,6 +411,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
             // for an iteration this peek has seen through the convergence test (QN_VP_NSOLVE)
             if ((spectral_method(s->method) && !h->has_lambda && !ls_only) || pn) {
                 QNCHK(vec_peek(r, false));
+                batch_seen();
                 done = h->phase == QN_VP_DONE;
                 continue;
             }
@@ -424,6 +454,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
             else VEC_LAUNCH(vec_accept_kernel, G);
             VEC_LAUNCH(vec_post_kernel, 1);
             QNCHK(vec_peek(r, false));
+            batch_seen();
             if (callback && h->k != k_seen) {
                 k_seen = h->k;
                 s->hctl->k = h->k; s->hctl->n_iterations = h->n_iter;
@@ -451,6 +482,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         else VEC_LAUNCH(vec_accept_kernel, G);
         VEC_LAUNCH(vec_post_kernel, 1);
         QNCHK(vec_peek(r, false));
+        batch_seen();
         if (callback && h->k != k_seen) { // ls_solver.rs:105-107: after k += 1 (one iteration per batch at most)
             k_seen = h->k;
             s->hctl->k = h->k; s->hctl->n_iterations = h->n_iter;

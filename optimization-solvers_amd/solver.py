@@ -1139,6 +1139,18 @@ class _SolverBase:
         x = _f64(x)
         _check(A.lib().qn_solver_set_x(self.h, _dp(x)))
 
+    def direction(self):
+        """the vector family: the direction of the last accepted iteration (inside the callback: d_k of the iteration just reported)"""
+        out = np.empty(self.n)
+        _check(A.lib().qn_solver_get_direction(self.h, _dp(out)))
+        return out
+
+    def gradient(self):
+        """the vector family: the gradient of the evaluation held at the current x (inside the callback, memoised: g_{k+1}); refused when none is"""
+        out = np.empty(self.n)
+        _check(A.lib().qn_solver_get_gradient(self.h, _dp(out)))
+        return out
+
     def k(self):
         return A.lib().qn_solver_k(self.h)
 

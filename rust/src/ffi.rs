@@ -294,6 +294,8 @@ extern "C" {
     pub fn qn_solver_tol(s: *const qn_solver) -> f64;
     pub fn qn_solver_get_x(s: *mut qn_solver, out_host: *mut f64) -> c_int;
     pub fn qn_solver_set_x(s: *mut qn_solver, x_host: *const f64) -> c_int;
+    pub fn qn_solver_get_direction(s: *mut qn_solver, d_host: *mut f64) -> c_int;
+    pub fn qn_solver_get_gradient(s: *mut qn_solver, g_host: *mut f64) -> c_int;
     pub fn qn_solver_s_norm(s: *mut qn_solver, out: *mut f64, is_some: *mut c_int) -> c_int;
     pub fn qn_solver_y_norm(s: *mut qn_solver, out: *mut f64, is_some: *mut c_int) -> c_int;
     pub fn qn_solver_next_iterate_too_close(s: *mut qn_solver, out: *mut c_int) -> c_int;

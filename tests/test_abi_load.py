@@ -214,6 +214,23 @@ def test_rust_ffi_matches_the_header_type_for_type():
         assert re.search(r"pub const " + m.group(1) + r": u32 = " + m.group(2) + ";", rs), m.group(1)
 
 
+def test_the_run_audit_getters_are_mirrored_everywhere(qn):
+    """qn_solver_get_direction / qn_solver_get_gradient: one signature in the header, the ctypes table, the Rust extern block and solver.py; a null
+    argument is refused with a text before anything touches a device"""
+    A = qn._abi
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "qn_hip.h")).read(), flags=re.S)
+    rs = open(os.path.join(ROOT, "rust", "src", "ffi.rs")).read()
+    sigs = _header_signatures(hdr)
+    table = {name: (ret, args) for name, ret, args in A.SYMBOLS}
+    for name, arg in (("qn_solver_get_direction", "d_host"), ("qn_solver_get_gradient", "g_host")):
+        assert sigs[name] == ("int", ["qn_solver*", "double*"])
+        assert table[name] == (C.c_int, [C.c_void_p, C.POINTER(C.c_double)])
+        assert f"pub fn {name}(s: *mut qn_solver, {arg}: *mut f64) -> c_int;" in rs
+        assert getattr(A.lib(), name)(None, None) == A.ERROR_INPUT_PARAMS and b"null argument" in A.lib().qn_last_error_message()
+    from optimization_solvers_amd import solver as S
+    assert callable(S._SolverBase.direction) and callable(S._SolverBase.gradient)
+
+
 def test_python_option_names_match_the_header(qn):
     """solver.py's OPTIONS (what set_option("name", v) accepts) and its OPT_* constants are the header's qn_option enumerators, value for value, and
     nothing else: a number that drifted would select another path silently."""
