@@ -466,7 +466,26 @@ enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton
         * counts 8 m n_pad per product and 16 m n_pad per weights pass; profiling mode: t_newton_ms = the product launches, t_hpass_ms = the
         * method's O(n) streams.  Not built: n_pad > 16384, a box, preconditioning, a trust region, row sharding, qn_compute_step_len,
         * qn_solver_compute_direction (QN_ERROR_INPUT_PARAMS). */
-       QN_NEWTON_CG = 14 /* truncated Newton (Newton-CG) on the log-sum-exp Hessian-vector product; no counterpart in the reference */ };
+       QN_NEWTON_CG = 14 /* truncated Newton (Newton-CG) on the log-sum-exp Hessian-vector product; no counterpart in the reference */,
+       /* Spectral proximal gradient (SpaRSA: Wright, Nowak, Figueiredo 2009): min f(x) + sum_j l1_j |x_j| over lb <= x <= ub, l1_j >= 0 finite, one scalar
+        * or one value per entry (qn_solver_set_l1; 0 after qn_solver_create).  QN_SPG with the projection replaced by the proximal map of lambda l1 |.| plus
+        * the box, on the same machine (QN_PATH_VECTOR | QN_PATH_PROX, csrc/qn_vec_prox.hip.h): every oracle kind of the family, memoize 0 / 1, box, trace,
+        * callbacks, one peek per batch, warm restarts (lambda, the ring and the memo survive calls: two calls of k iterations give the bits of one call of
+        * 2 k); qn_solver_set_spg_lambdas / qn_solver_spg_lambda answer for it, and the first qn_minimize makes the constructor's call for lambda0 =
+        * clamp(1 / ||d||_inf) with lambda = 1.  THE RULES, per entry, each operation rounded once, no FMA:
+        *   1. sg = lambda g_j; u = x_j - sg; tau = lambda l1_j; z = u - tau if u > tau, u + tau if u < -tau, else 0.0; p = fmin(fmax(z, lb_j), ub_j);
+        *      d_j = p - x_j.  Where the prox returns 0, d_j = -x_j and an accepted unit step leaves x_j = 0.0 exactly.
+        *   2. the convergence measure replaces the projected gradient: the element of least magnitude of [lo, hi], lo = hi = g_j + l1_j (x_j > 0),
+        *      g_j - l1_j (x_j < 0), lo = g_j - l1_j and hi = g_j + l1_j (x_j == 0); lo = -inf where x_j == lb_j, hi = +inf where x_j == ub_j; QN_OK when the
+        *      largest magnitude is < tol.  It is the trace's gnorm.
+        *   3. h0 = h(x), h1 = sum_j l1_j |x_j + d_j|, Delta = g.d + (h1 - h0), F_k = f + h0 (the trace's f).  Out-of-domain is tested on f; the sign of
+        *      Delta is not tested.
+        *   4. the search along d, first trial t = 1, F_t = f(x + t d) + h(x + t d): QN_LS_GLL_QUADRATIC (the ring holds composite values) and
+        *      QN_LS_BACKTRACKING, with F_t, F_k, Delta where SPG has f_t, f_k, g.d.  Every other search, qn_compute_step_len and
+        *      qn_solver_compute_direction: QN_ERROR_INPUT_PARAMS before any launch.
+        *   5. accept and lambda = clamp(s.s / s.y), lambda_max when s.y <= 0: QN_SPG's.
+        * With l1 == 0 everywhere the run is QN_SPG's, bit for bit.  One rank.  Not built: backtracking on lambda, acceleration, group penalties. */
+       QN_SPECTRAL_PROXIMAL_GRADIENT = 15 /* SpectralProximalGradient: L1-regularised SPG by soft-thresholding; no counterpart in the reference */ };
 #define QN_LBFGS_MAX_M 32
 /* QN_NONLINEAR_CG's variants (qn_solver_set_cg) */
 enum { QN_CG_FR = 0 /* Fletcher-Reeves */, QN_CG_PR_PLUS = 1 /* Polak-Ribiere+ */, QN_CG_HS_PLUS = 2 /* Hestenes-Stiefel+ */, QN_CG_DY = 3 /* Dai-Yuan */,
@@ -485,6 +504,12 @@ int qn_solver_set_spg_lambdas(qn_solver* s, double lambda_min, double lambda_max
  * the first qn_minimize after create / reset makes that call (counted in oracle_calls; with memoize = 1 the point is evaluated once):
  * is_some = 0 until then.  A qn_minimize with max_iter_solver = 0 does just that and returns QN_MAX_ITER_REACHED. */
 int qn_solver_spg_lambda(qn_solver* s, double* out, int* is_some);
+/* QN_SPECTRAL_PROXIMAL_GRADIENT: the penalty h(x) = sum_j l1_j |x_j| -- l1_host's n entries, or l1_scalar for every entry when l1_host is NULL.  A
+ * negative or non-finite value, or another method: QN_ERROR_INPUT_PARAMS.  Between two qn_minimize calls it clears GLLQuadratic's ring (its values
+ * belong to the old penalty) and keeps lambda, x and the memoised evaluation of the smooth part: the regularisation-path use. */
+int qn_solver_set_l1(qn_solver* s, const double* l1_host, double l1_scalar);
+/* ... and the n entries in use (a scalar: n copies). */
+int qn_solver_get_l1(qn_solver* s, double* l1_host);
 /* QN_PROJECTED_NEWTON / QN_SPECTRAL_PROJECTED_NEWTON: Cholesky factorisations enqueued by the last qn_minimize.  With a device quadratic the factor
  * is kept between iterations and calls (keyed on the objective; QN_OPT_PNEWTON_REUSE_FACTOR): 1 for the first call, 0 afterwards; with a host
  * closure, or with the option off, one per iteration that computed a direction.  Other methods: 0.
@@ -663,6 +688,7 @@ typedef struct {
 #define QN_PATH_LBFGS 1024u    /* QN_LBFGS: the direction from the compact form of L-BFGS, two streams of the memory per iteration (csrc/qn_lbfgs.hip.h); set beside QN_PATH_VECTOR */
 #define QN_PATH_CG 2048u       /* QN_NONLINEAR_CG: the direction d = beta p - g written by cg_dir_kernel, beta from the accept pass's sums (csrc/qn_cg.hip.h); set beside QN_PATH_VECTOR */
 #define QN_PATH_EXACT 4096u    /* QN_LS_EXACT_QUADRATIC: the step from one curvature pass, (f, g) of the accepted point by the recurrence or by the objective (csrc/qn_vec_exact.hip.h); set beside QN_PATH_VECTOR */
+#define QN_PATH_PROX 16384u    /* QN_SPECTRAL_PROXIMAL_GRADIENT: the direction from the proximal map of lambda l1 |.| plus the box, the search on composite values (csrc/qn_vec_prox.hip.h); set beside QN_PATH_VECTOR */
 #define QN_PATH_NEWTON_CG 8192u /* QN_NEWTON_CG: the direction from conjugate gradients on H z = g, one log-sum-exp Hessian-vector product per inner step (csrc/qn_newton_cg.hip.h, qn_lse_hv.hip.h); set beside QN_PATH_VECTOR */
 int qn_solver_get_stats(qn_solver* s, qn_stats* out);
 /* profiling != 0: bracket every launch with HIP events on the solver's stream (slower; for roofline reports) */

@@ -750,6 +750,82 @@ class SpectralProjectedGradient : public ProjectedSolver<QN_SPG> {
     Floating lambda() const { Floating v = 0; int some = 0; check(qn_solver_spg_lambda(this->handle(), &v, &some)); return v; }
 };
 
+// Spectral proximal gradient (SpaRSA): min f(x) + sum_j l1_j |x_j| over lb <= x <= ub -- SpectralProjectedGradient with the projection replaced by the
+// proximal map of lambda l1 |.| plus the box, GLLQuadratic or BackTracking on the composite value.  new_(tol, x0, oracle, l1) with one scalar or n
+// entries, with_bounds(lb, ub) before the first minimize; the constructor calls the oracle once, for lambda0.  Entries the prox sets to zero are 0.0.
+class SpectralProximalGradient : public LineSearchSolver<QN_SPECTRAL_PROXIMAL_GRADIENT> {
+    using Base = LineSearchSolver<QN_SPECTRAL_PROXIMAL_GRADIENT>;
+    DVector lb_, ub_;
+    template <class Oracle>
+    void lambda0(Oracle&& oracle) {
+        GLLQuadratic ls(1e-4, 1);
+        Result r = this->minimize(ls, oracle, 0, 0); // no iteration: the constructor's evaluation only
+        if (r.is_err() && r.unwrap_err().kind != SolverError::MaxIterReached) r.unwrap();
+    }
+  public:
+    template <class Oracle>
+    SpectralProximalGradient(Floating tol, const DVector& x0, Oracle&& oracle, const DVector& l1, Context& ctx = Context::default_context()) : Base(tol, x0, ctx) {
+        set_l1(l1);
+        lambda0(oracle);
+    }
+    template <class Oracle>
+    SpectralProximalGradient(Floating tol, const DVector& x0, Oracle&& oracle, Floating l1, Context& ctx = Context::default_context()) : Base(tol, x0, ctx) {
+        set_l1(l1);
+        lambda0(oracle);
+    }
+    template <class Oracle>
+    SpectralProximalGradient(Floating tol, const DVector& x0, Oracle&& oracle, const DVector& l1, DVector lower_bound, DVector upper_bound,
+                             Context& ctx = Context::default_context())
+        : Base(tol, x0, ctx), lb_(std::move(lower_bound)), ub_(std::move(upper_bound)) {
+        check(qn_solver_set_bounds(this->handle(), lb_.data(), ub_.data()));
+        set_l1(l1);
+        lambda0(oracle);
+    }
+    template <class Oracle, class L1>
+    static SpectralProximalGradient new_(Floating tol, const DVector& x0, Oracle&& oracle, const L1& l1) { return SpectralProximalGradient(tol, x0, oracle, l1); }
+    template <class Oracle>
+    static SpectralProximalGradient new_(Floating tol, const DVector& x0, Oracle&& oracle, const DVector& l1, DVector lb, DVector ub) {
+        return SpectralProximalGradient(tol, x0, oracle, l1, std::move(lb), std::move(ub));
+    }
+    // between two minimize calls: GLLQuadratic's ring is cleared; lambda, x and the memoised evaluation of the smooth part are kept
+    void set_l1(const DVector& l1) {
+        if (l1.size() != this->x().size()) throw SolverError(QN_ERROR_INPUT_PARAMS);
+        check(qn_solver_set_l1(this->handle(), l1.data(), 0.0));
+    }
+    void set_l1(Floating l1) { check(qn_solver_set_l1(this->handle(), nullptr, l1)); }
+    DVector l1() const { DVector v(this->x().size()); check(qn_solver_get_l1(this->handle(), v.data())); return v; }
+    SpectralProximalGradient with_lambdas(Floating lambda_min, Floating lambda_max) && {
+        check(qn_solver_set_spg_lambdas(this->handle(), lambda_min, lambda_max));
+        return std::move(*this);
+    }
+    Floating lambda() const { Floating v = 0; int some = 0; check(qn_solver_spg_lambda(this->handle(), &v, &some)); return v; }
+    Floating grad_tol() const { return this->tol(); }
+    Floating penalty() const { // h at x()
+        const DVector w = l1();
+        const DVector& x = this->x();
+        Floating h = 0.0;
+        for (size_t i = 0; i < x.size(); ++i) h += w[i] * std::fabs(x[i]);
+        return h;
+    }
+    Floating composite(const FuncEvalMultivariate& eval) const { return eval.f() + penalty(); }
+    size_t nonzeros() const { size_t c = 0; for (Floating v : this->x()) c += v != 0.0; return c; }
+    // per entry the element of least magnitude of the subdifferential of f + h at x(), opened towards the side a bound blocks; its infinity norm
+    Floating measure(const FuncEvalMultivariate& eval) const {
+        const DVector w = l1();
+        const DVector& x = this->x();
+        Floating acc = 0.0;
+        for (size_t i = 0; i < x.size(); ++i) {
+            const Floating g = eval.g()[i];
+            Floating lo = x[i] > 0.0 ? g + w[i] : g - w[i], hi = x[i] < 0.0 ? g - w[i] : g + w[i];
+            if (!lb_.empty() && x[i] == lb_[i]) lo = -INFINITY;
+            if (!ub_.empty() && x[i] == ub_[i]) hi = INFINITY;
+            acc = std::fmax(acc, std::fabs(lo > 0.0 ? lo : (hi < 0.0 ? hi : 0.0)));
+        }
+        return acc;
+    }
+    bool has_converged(const FuncEvalMultivariate& eval) const { return measure(eval) < this->tol(); }
+};
+
 // newton/projected_newton.rs: new(grad_tol, x0, lower_bound, upper_bound); d = P(x - H^-1 g) - x, H^-1 g by one Cholesky factorisation (the
 // Hessian's lower triangle) and one solve on the GPU.  The closure returns FuncEvalMultivariate(f, g).with_hessian(h), or the oracle is a Quadratic.
 class ProjectedNewton : public ProjectedSolver<QN_PROJECTED_NEWTON> {

@@ -19,6 +19,7 @@ LBFGS = 12  # limited-memory BFGS (ProjectedLBFGS once bounds are set); not the 
 LBFGS_MAX_M = 32
 NONLINEAR_CG = 13  # nonlinear conjugate gradient (unbounded only); no counterpart in the reference
 NEWTON_CG = 14  # truncated Newton on the log-sum-exp Hessian-vector product (unbounded only); no counterpart in the reference
+SPECTRAL_PROXIMAL_GRADIENT = 15  # L1-regularised SPG by soft-thresholding (SpaRSA); no counterpart in the reference
 CG_FR, CG_PR_PLUS, CG_HS_PLUS, CG_DY, CG_HZ = 0, 1, 2, 3, 4  # qn_solver_set_cg's variants
 PRECOND_NONE, PRECOND_JACOBI = 0, 1  # qn_solver_set_newton_cg_preconditioner's kinds
 UNIQUE_ID_BYTES = 128
@@ -76,6 +77,7 @@ PATH_LBFGS = 1024
 PATH_CG = 2048
 PATH_EXACT = 4096
 PATH_NEWTON_CG = 8192
+PATH_PROX = 16384
 
 
 # every symbol include/qn_hip.h declares: (name, restype, argtypes)
@@ -154,6 +156,8 @@ SYMBOLS = [
     ("qn_solver_get_inverse_p", C.c_int, [C.c_void_p, dp]),
     ("qn_solver_set_spg_lambdas", C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     ("qn_solver_spg_lambda", C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int)]),
+    ("qn_solver_set_l1", C.c_int, [C.c_void_p, dp, C.c_double]),
+    ("qn_solver_get_l1", C.c_int, [C.c_void_p, dp]),
     ("qn_solver_newton_factorisations", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
     ("qn_solver_set_lbfgs_memory", C.c_int, [C.c_void_p, C.c_size_t]),
     ("qn_solver_lbfgs_state", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), dp, C.POINTER(C.c_size_t)]),

@@ -97,3 +97,6 @@ extern "C" const char* qn_status_string(int status) {
 // truncated Newton (NewtonCG) on the first-order family's machine: conjugate gradients on H z = g with that product, behind every existing kernel
 #include "qn_newton_cg.hip.h"
 #include "qn_host_newton_cg.hip.h"
+// spectral proximal gradient (L1 by soft-thresholding) on the first-order family's machine: its direction, trial and decision kernels, behind every existing kernel
+#include "qn_vec_prox.hip.h"
+#include "qn_host_prox.hip.h"

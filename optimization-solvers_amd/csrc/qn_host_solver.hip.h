@@ -116,6 +116,9 @@ struct qn_solver {
     DevBuf<double> cg_p, cg_part; // QN_NONLINEAR_CG (qn_cg.hip.h): the direction last searched, [n_pad]; the accept kernel's shares, [QN_CG_NQ][QN_VEC_MAXG]
     DevBuf<double> tn_pc;    // its Jacobi preconditioner: M = diag H(x_k) and 1 / M, [2][n_pad] (allocated by the first run that asks for it)
     DevBuf<double> tn_block; // QN_NEWTON_CG (qn_newton_cg.hip.h): r, p, q, the copy of gbar, [4][n_pad]; the shares of its inner products, [QN_TN_NPART][QN_VEC_MAXG]
+    // QN_SPECTRAL_PROXIMAL_GRADIENT (qn_vec_prox.hip.h): l1 per entry, [n_pad] zero-padded (once a vector was set) with its host copy, or the scalar;
+    // h0, Delta, F_k of the iteration being searched, [4]
+    DevBuf<double> px_l1, px_state; std::vector<double> px_l1_host; double px_l1_scalar = 0.0; bool px_l1_vec = false;
     DevBuf<double> ex_q, ex_c; // QN_LS_EXACT_QUADRATIC (qn_vec_exact.hip.h): q = Q d of the last curvature pass, [n_pad]; d'Qd of a dense quadratic, [2]
     DevBuf<double> bounds_block; // lb, ub (solver), llb, lub (bounded line search): 4 n_pad vectors
     int bounded = 0;

@@ -45,7 +45,7 @@ enum QnVecPhase : int32_t {
 
 // the second-order variants (newton/projected_newton.rs, newton/spn.rs): the same machine, with z = H^-1 g where the first-order family has g
 __device__ __forceinline__ bool vec_newton(int method) { return method == QN_PROJECTED_NEWTON || method == QN_SPECTRAL_PROJECTED_NEWTON; }
-__device__ __forceinline__ bool vec_spectral(int method) { return method == QN_SPG || method == QN_SPECTRAL_PROJECTED_NEWTON; }
+__device__ __forceinline__ bool vec_spectral(int method) { return method == QN_SPG || method == QN_SPECTRAL_PROJECTED_NEWTON || method == QN_SPECTRAL_PROXIMAL_GRADIENT; }
 // update_next_iterate calls the oracle at the accepted point, for y (spg.rs:130, spn.rs:135, projected_newton.rs:134)
 __device__ __forceinline__ bool vec_needs_y(int method) { return vec_spectral(method) || method == QN_PROJECTED_NEWTON || method == QN_LBFGS || method == QN_NONLINEAR_CG; }
 // the direction is P(x - z) - x with a z that arrives from outside this file, in phase QN_VP_NSOLVE (QN_NONLINEAR_CG: the direction itself does)

@@ -1421,6 +1421,94 @@ class SpectralProjectedGradient(_ProjectedBase):
         return getattr(self, "_lmax", 1e3)
 
 
+class SpectralProximalGradient(_SolverBase):
+    """Spectral proximal gradient (SpaRSA): min f(x) + sum_j l1_j |x_j| over lb <= x <= ub.  SPG with the projection replaced by the proximal map
+    of lambda l1 |.| plus the box: d = clip(soft(x - lambda g, lambda l1)) - x, the search (GLLQuadratic or BackTracking) on the composite value
+    with Tseng and Yun's decrease g.d + h(x + d) - h(x).  `l1`: one scalar or one value per entry, >= 0 and finite.  The constructor evaluates once,
+    for lambda0, as SpectralProjectedGradient's does.  Entries the prox sets to zero are exactly 0.0 in x()."""
+    METHOD = A.SPECTRAL_PROXIMAL_GRADIENT
+
+    def __init__(self, tol, x0, oracle, l1, lower_bound=None, upper_bound=None, ctx=None, memoize=None):
+        super().__init__(tol, x0, ctx)
+        self._lb = self._ub = None
+        if lower_bound is not None or upper_bound is not None:
+            self._lb = _f64(np.full(self.n, -np.inf) if lower_bound is None else lower_bound)
+            self._ub = _f64(np.full(self.n, np.inf) if upper_bound is None else upper_bound)
+            _check(A.lib().qn_solver_set_bounds(self.h, _dp(self._lb), _dp(self._ub)))
+        self.set_l1(l1)
+        self.memoize = memoize
+        try:  # a call with no iterations: the constructor's evaluation only
+            self.minimize(GLLQuadratic(1e-4, 1), oracle, 0, 0)
+        except MaxIterReached:
+            pass
+
+    @classmethod
+    def new(cls, tol, x0, oracle, l1, lower_bound=None, upper_bound=None, ctx=None, memoize=None):
+        return cls(tol, x0, oracle, l1, lower_bound, upper_bound, ctx, memoize)
+
+    def set_l1(self, v):
+        """a scalar or n entries; between two minimize calls: the ring is cleared, lambda, x and the memoised evaluation are kept"""
+        if np.ndim(v) == 0:
+            _check(A.lib().qn_solver_set_l1(self.h, None, float(v)))
+        else:
+            v = _f64(v)
+            if v.size != self.n:
+                raise ErrorInputParams("l1 has the wrong dimension")
+            _check(A.lib().qn_solver_set_l1(self.h, _dp(v), 0.0))
+
+    @property
+    def l1(self):
+        out = np.empty(self.n)
+        _check(A.lib().qn_solver_get_l1(self.h, _dp(out)))
+        return out
+
+    with_lambdas = SpectralProjectedGradient.with_lambdas
+    lambda_ = SpectralProjectedGradient.lambda_
+    lambda_min = SpectralProjectedGradient.lambda_min
+    lambda_max = SpectralProjectedGradient.lambda_max
+
+    def grad_tol(self):
+        return self.tol()
+
+    def lower_bound(self):
+        return self._lb
+
+    def upper_bound(self):
+        return self._ub
+
+    def penalty(self):
+        """h at x()"""
+        return float(np.dot(self.l1, np.abs(self.x())))
+
+    def composite(self, eval_x_k):
+        """F = f + h at x(), from an evaluation of the smooth part there"""
+        f = eval_x_k.f() if isinstance(eval_x_k, FuncEvalMultivariate) else eval_x_k[0]
+        return float(f) + self.penalty()
+
+    def nonzeros(self):
+        return int(np.count_nonzero(self.x()))
+
+    def measure(self, eval_x_k):
+        """per entry, the element of least magnitude of the subdifferential of F at x(), opened towards the side a bound blocks"""
+        g = np.asarray(eval_x_k.g() if isinstance(eval_x_k, FuncEvalMultivariate) else eval_x_k[1], dtype=np.float64)
+        x, l1 = self.x(), self.l1
+        lo = np.where(x > 0.0, g + l1, g - l1)
+        hi = np.where(x < 0.0, g - l1, g + l1)
+        if self._lb is not None:
+            lo = np.where(x == self._lb, -np.inf, lo)
+            hi = np.where(x == self._ub, np.inf, hi)
+        return np.where(lo > 0.0, lo, np.where(hi < 0.0, hi, 0.0))
+
+    def has_converged(self, eval_x_k):
+        return float(np.max(np.abs(self.measure(eval_x_k)))) < self.tol()
+
+    def approx_inv_hessian(self, all_ranks=True):  # there is none
+        _check(A.lib().qn_solver_get_inv_hessian(self.h, None, 0))
+
+    def set_approx_inv_hessian(self, h):
+        _check(A.lib().qn_solver_set_inv_hessian(self.h, None))
+
+
 class ProjectedNewton(_ProjectedBase):
     """newton/projected_newton.rs: `new(grad_tol, x0, lower_bound, upper_bound)`; d = P(x - H^-1 g) - x with H^-1 g from one Cholesky
     factorisation (the lower triangle of the Hessian) and one solve on the GPU.  The oracle is a `Quadratic` (its matrix is the Hessian) or

@@ -42,6 +42,7 @@ pub const QN_LBFGS: c_int = 12;
 pub const QN_LBFGS_MAX_M: usize = 32;
 pub const QN_NONLINEAR_CG: c_int = 13;
 pub const QN_NEWTON_CG: c_int = 14;
+pub const QN_SPECTRAL_PROXIMAL_GRADIENT: c_int = 15;
 pub const QN_CG_FR: c_int = 0;
 pub const QN_CG_PR_PLUS: c_int = 1;
 pub const QN_CG_HS_PLUS: c_int = 2;
@@ -97,6 +98,7 @@ pub const QN_PATH_LBFGS: u32 = 1024;
 pub const QN_PATH_CG: u32 = 2048;
 pub const QN_PATH_EXACT: u32 = 4096;
 pub const QN_PATH_NEWTON_CG: u32 = 8192;
+pub const QN_PATH_PROX: u32 = 16384;
 
 #[repr(C)] pub struct qn_context { _p: [u8; 0] }
 #[repr(C)] pub struct qn_solver { _p: [u8; 0] }
@@ -274,6 +276,8 @@ extern "C" {
     pub fn qn_solver_get_inverse_p(s: *mut qn_solver, out_colmajor_host: *mut f64) -> c_int;
     pub fn qn_solver_set_spg_lambdas(s: *mut qn_solver, lambda_min: f64, lambda_max: f64) -> c_int;
     pub fn qn_solver_spg_lambda(s: *mut qn_solver, out: *mut f64, is_some: *mut c_int) -> c_int;
+    pub fn qn_solver_set_l1(s: *mut qn_solver, l1_host: *const f64, l1_scalar: f64) -> c_int;
+    pub fn qn_solver_get_l1(s: *mut qn_solver, l1_host: *mut f64) -> c_int;
     pub fn qn_solver_newton_factorisations(s: *mut qn_solver, out: *mut usize) -> c_int;
     pub fn qn_solver_set_lbfgs_memory(s: *mut qn_solver, m: usize) -> c_int;
     pub fn qn_solver_lbfgs_state(s: *mut qn_solver, m: *mut usize, stored: *mut usize, gamma: *mut f64, resets: *mut usize) -> c_int;

@@ -843,7 +843,7 @@ macro_rules! gpu_solver {
                     // the direction needs the Cholesky solve and (spn.rs) the device-resident lambda: `minimize_on_device` / `minimize_objective`
                     return Err(SolverError::ErrorInputParams);
                 }
-                if $method == QN_SPG {
+                if $method == QN_SPG || $method == QN_SPECTRAL_PROXIMAL_GRADIENT {
                     // spg.rs:126-143 updates lambda here; it lives on the device and only qn_minimize updates it.  Refuse rather than run
                     // a fixed-lambda projected gradient under SPG's name: use `minimize_on_device` / `minimize_objective`.
                     return Err(SolverError::ErrorInputParams);
@@ -1118,6 +1118,7 @@ macro_rules! bounded_first_order {
 }
 bounded_first_order!(GpuProjectedGradientDescent);
 bounded_first_order!(GpuSpectralProjectedGradient);
+bounded_first_order!(GpuSpectralProximalGradient);
 bounded_first_order!(GpuProjectedNewton);
 bounded_first_order!(GpuSpectralProjectedNewton);
 bounded_first_order!(GpuProjectedLbfgs);
@@ -1161,6 +1162,54 @@ impl GpuSpectralProjectedNewton {
     }
     pub fn lambda(&self) -> Option<Floating> {
         self.core.option(qn_solver_spg_lambda)
+    }
+}
+
+gpu_solver!(
+    /// Spectral proximal gradient (SpaRSA): min f(x) + sum_j l1_j |x_j| over the box -- `GpuSpectralProjectedGradient` with the projection replaced
+    /// by the proximal map of lambda l1 |.| plus the box (QN_PATH_PROX).  `new(tol, x0).with_l1(&l1)` or `.with_l1_scalar(v)`, optionally
+    /// `.with_bounds(lb, ub)`; `GpuGllQuadratic` or `GpuBackTracking`, on the composite value.  The weights the prox switches off are exactly 0.0.
+    /// The constructor's oracle call (lambda0) is made by the first `minimize_on_device` / `minimize_objective`; drive it with those two.
+    GpuSpectralProximalGradient, QN_SPECTRAL_PROXIMAL_GRADIENT, false
+);
+
+impl GpuSpectralProximalGradient {
+    /// one value per entry, each finite and >= 0
+    pub fn with_l1(mut self, l1: &DVector<Floating>) -> Self {
+        self.set_l1(l1);
+        self
+    }
+    pub fn with_l1_scalar(mut self, l1: Floating) -> Self {
+        self.set_l1_scalar(l1);
+        self
+    }
+    /// between two minimize calls (the regularisation path): GLLQuadratic's ring is cleared; lambda, x and the memoised evaluation are kept
+    pub fn set_l1(&mut self, l1: &DVector<Floating>) {
+        assert_eq!(l1.len(), self.core.x.len());
+        assert_eq!(unsafe { qn_solver_set_l1(self.core.h, l1.as_ptr(), 0.0) }, QN_OK, "{}", last_error());
+    }
+    pub fn set_l1_scalar(&mut self, l1: Floating) {
+        assert_eq!(unsafe { qn_solver_set_l1(self.core.h, std::ptr::null(), l1) }, QN_OK, "{}", last_error());
+    }
+    pub fn l1(&self) -> DVector<Floating> {
+        let mut v = DVector::zeros(self.core.x.len());
+        assert_eq!(unsafe { qn_solver_get_l1(self.core.h, v.as_mut_ptr()) }, QN_OK, "{}", last_error());
+        v
+    }
+    pub fn with_lambdas(self, lambda_min: Floating, lambda_max: Floating) -> Self {
+        assert_eq!(unsafe { qn_solver_set_spg_lambdas(self.core.h, lambda_min, lambda_max) }, QN_OK, "{}", last_error());
+        self
+    }
+    /// None until the first minimize call has made the constructor's evaluation
+    pub fn lambda(&self) -> Option<Floating> {
+        self.core.option(qn_solver_spg_lambda)
+    }
+    /// h at x()
+    pub fn penalty(&self) -> Floating {
+        self.l1().iter().zip(self.core.x.iter()).map(|(w, x)| w * x.abs()).sum()
+    }
+    pub fn nonzeros(&self) -> usize {
+        self.core.x.iter().filter(|v| **v != 0.0).count()
     }
 }
 
