@@ -485,7 +485,28 @@ enum { QN_BFGS = 0, QN_DFP = 1, QN_GRADIENT_DESCENT = 2, QN_NEWTON = 3 /* newton
         *      qn_solver_compute_direction: QN_ERROR_INPUT_PARAMS before any launch.
         *   5. accept and lambda = clamp(s.s / s.y), lambda_max when s.y <= 0: QN_SPG's.
         * With l1 == 0 everywhere the run is QN_SPG's, bit for bit.  One rank.  Not built: backtracking on lambda, acceleration, group penalties. */
-       QN_SPECTRAL_PROXIMAL_GRADIENT = 15 /* SpectralProximalGradient: L1-regularised SPG by soft-thresholding; no counterpart in the reference */ };
+       QN_SPECTRAL_PROXIMAL_GRADIENT = 15 /* SpectralProximalGradient: L1-regularised SPG by soft-thresholding; no counterpart in the reference */,
+       /* Orthant-wise limited-memory quasi-Newton (OWL-QN: Andrew and Gao, ICML 2007): min f(x) + sum_j l1_j |x_j|, unbounded, l1 as for
+        * QN_SPECTRAL_PROXIMAL_GRADIENT (qn_solver_set_l1).  QN_LBFGS's memory, compact-form direction and commit rule on the same machine
+        * (QN_PATH_VECTOR | QN_PATH_LBFGS | QN_PATH_OWLQN, csrc/qn_vec_owlqn.hip.h), with four element-wise steps of its own.  Every oracle kind of
+        * QN_LBFGS, memoize 0 / 1, trace, callbacks, one peek per batch, warm restarts (two calls of k iterations give the bits of one call of 2 k);
+        * qn_solver_set_lbfgs_memory, qn_solver_lbfgs_state and QN_OPT_LBFGS_UNIT_SCALING answer for it.  THE RULES, each operation rounded once, no FMA:
+        *   1. the pseudo-gradient v_j = g_j + l1_j (x_j > 0), g_j - l1_j (x_j < 0); at x_j == 0: g_j - l1_j if that is > 0, g_j + l1_j if that is < 0,
+        *      else 0.  QN_OK when ||v||_inf < tol (QN_SPECTRAL_PROXIMAL_GRADIENT's measure without a box); it is the trace's gnorm.  Out-of-domain is
+        *      tested on the smooth f.
+        *   2. z = H_k v by QN_LBFGS's kernels (the safeguard reads v.z > 0 and leaves z = v; no pair: z = v).
+        *   3. d_j = -z_j where l1_j == 0 or z_j and v_j have the same strict sign, else 0.0.  v.d not < 0 or not finite: QN_ABNORMAL_TERMINATION, "not a
+        *      descent direction", x left at x_k.
+        *   4. the orthant xi_j = sign(x_j), or sign(-v_j) where x_j == 0.
+        *   5. the trial xt_j = x_j + t d_j (t d_j rounded first) where l1_j == 0 or that value has xi_j's strict sign, else 0.0; first trial t = 1.
+        *   6. QN_LS_BACKTRACKING only, accepted when F_t - F_k <= c1 v.(xt - x) (no factor t), F = f + h; a non-finite F_t shrinks without counting.  Every
+        *      other search, a box, qn_compute_step_len and qn_solver_compute_direction: QN_ERROR_INPUT_PARAMS before any launch.
+        *   7. x_next = xt (never x + t d); s = x_next - x, y the difference of the SMOOTH gradients; the pair is kept when s.y > DBL_EPSILON y.y.
+        *   8. trace: f = F_k, gnorm = ||v||_inf, updated = the pair was kept.
+        *   9. the memory, gamma, the resets and the memo survive calls; qn_solver_set_l1 keeps the pairs, x and the memo; qn_solver_set_lbfgs_memory drops
+        *      the pairs.
+        * One rank.  Not built: a box, StrongWolfe or a non-monotone search, an initial step 1 / ||v||, group penalties. */
+       QN_OWLQN = 16 /* OWLQN: orthant-wise L-BFGS for L1-regularised objectives; no counterpart in the reference */ };
 #define QN_LBFGS_MAX_M 32
 /* QN_NONLINEAR_CG's variants (qn_solver_set_cg) */
 enum { QN_CG_FR = 0 /* Fletcher-Reeves */, QN_CG_PR_PLUS = 1 /* Polak-Ribiere+ */, QN_CG_HS_PLUS = 2 /* Hestenes-Stiefel+ */, QN_CG_DY = 3 /* Dai-Yuan */,
@@ -510,6 +531,9 @@ int qn_solver_spg_lambda(qn_solver* s, double* out, int* is_some);
 int qn_solver_set_l1(qn_solver* s, const double* l1_host, double l1_scalar);
 /* ... and the n entries in use (a scalar: n copies). */
 int qn_solver_get_l1(qn_solver* s, double* l1_host);
+/* (QN_OWLQN takes both as well; there qn_solver_set_l1 leaves the memory of pairs as it is: they are differences of the smooth gradient.)
+ * QN_OWLQN: the pseudo-gradient v of the last loop top (rule 1), n entries; zeros before the first one.  Other methods: QN_ERROR_INPUT_PARAMS. */
+int qn_solver_get_pseudo_gradient(qn_solver* s, double* out_host);
 /* QN_PROJECTED_NEWTON / QN_SPECTRAL_PROJECTED_NEWTON: Cholesky factorisations enqueued by the last qn_minimize.  With a device quadratic the factor
  * is kept between iterations and calls (keyed on the objective; QN_OPT_PNEWTON_REUSE_FACTOR): 1 for the first call, 0 afterwards; with a host
  * closure, or with the option off, one per iteration that computed a direction.  Other methods: 0.
@@ -689,6 +713,7 @@ typedef struct {
 #define QN_PATH_CG 2048u       /* QN_NONLINEAR_CG: the direction d = beta p - g written by cg_dir_kernel, beta from the accept pass's sums (csrc/qn_cg.hip.h); set beside QN_PATH_VECTOR */
 #define QN_PATH_EXACT 4096u    /* QN_LS_EXACT_QUADRATIC: the step from one curvature pass, (f, g) of the accepted point by the recurrence or by the objective (csrc/qn_vec_exact.hip.h); set beside QN_PATH_VECTOR */
 #define QN_PATH_PROX 16384u    /* QN_SPECTRAL_PROXIMAL_GRADIENT: the direction from the proximal map of lambda l1 |.| plus the box, the search on composite values (csrc/qn_vec_prox.hip.h); set beside QN_PATH_VECTOR */
+#define QN_PATH_OWLQN 32768u   /* QN_OWLQN: the pseudo-gradient, the aligned direction and the orthant projection of the trial point around QN_LBFGS's direction kernels (csrc/qn_vec_owlqn.hip.h); set beside QN_PATH_VECTOR | QN_PATH_LBFGS */
 #define QN_PATH_NEWTON_CG 8192u /* QN_NEWTON_CG: the direction from conjugate gradients on H z = g, one log-sum-exp Hessian-vector product per inner step (csrc/qn_newton_cg.hip.h, qn_lse_hv.hip.h); set beside QN_PATH_VECTOR */
 int qn_solver_get_stats(qn_solver* s, qn_stats* out);
 /* profiling != 0: bracket every launch with HIP events on the solver's stream (slower; for roofline reports) */

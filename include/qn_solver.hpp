@@ -887,6 +887,56 @@ class LBFGS : public ProjectedLBFGS {
     LBFGS with_memory(size_t m) && { check(qn_solver_set_lbfgs_memory(this->handle(), m)); return std::move(*this); }
 };
 
+// Orthant-wise limited-memory quasi-Newton (OWL-QN, Andrew and Gao 2007): min f(x) + sum_j l1_j |x_j|, UNBOUNDED ONLY.  new_(tol, x0, l1) with one
+// scalar or n entries, .with_memory(m); LBFGS's memory and direction kernels applied to the pseudo-gradient, the direction aligned with it, every trial
+// point projected onto the orthant of x; BackTracking only, on the composite value.  Entries the projection switches off are exactly 0.0.  The pairs
+// are differences of the smooth gradient: set_l1 between two minimize calls keeps them, x and the memoised evaluation (the regularisation path).
+class OWLQN : public LineSearchSolver<QN_OWLQN> {
+    using Base = LineSearchSolver<QN_OWLQN>;
+  public:
+    OWLQN(Floating tol, const DVector& x0, const DVector& l1, Context& ctx = Context::default_context()) : Base(tol, x0, ctx) { set_l1(l1); }
+    OWLQN(Floating tol, const DVector& x0, Floating l1, Context& ctx = Context::default_context()) : Base(tol, x0, ctx) { set_l1(l1); }
+    template <class L1>
+    static OWLQN new_(Floating tol, const DVector& x0, const L1& l1) { return OWLQN(tol, x0, l1); }
+    OWLQN with_memory(size_t m) && { check(qn_solver_set_lbfgs_memory(this->handle(), m)); return std::move(*this); }
+    void set_memory(size_t m) { check(qn_solver_set_lbfgs_memory(this->handle(), m)); } // the stored pairs are dropped
+    void set_l1(const DVector& l1) {
+        if (l1.size() != this->x().size()) throw SolverError(QN_ERROR_INPUT_PARAMS);
+        check(qn_solver_set_l1(this->handle(), l1.data(), 0.0));
+    }
+    void set_l1(Floating l1) { check(qn_solver_set_l1(this->handle(), nullptr, l1)); }
+    DVector l1() const { DVector v(this->x().size()); check(qn_solver_get_l1(this->handle(), v.data())); return v; }
+    size_t memory() const { size_t v = 0; check(qn_solver_lbfgs_state(this->handle(), &v, nullptr, nullptr, nullptr)); return v; }
+    size_t stored_pairs() const { size_t v = 0; check(qn_solver_lbfgs_state(this->handle(), nullptr, &v, nullptr, nullptr)); return v; }
+    Floating gamma() const { Floating v = 0; check(qn_solver_lbfgs_state(this->handle(), nullptr, nullptr, &v, nullptr)); return v; }
+    size_t resets() const { size_t v = 0; check(qn_solver_lbfgs_state(this->handle(), nullptr, nullptr, nullptr, &v)); return v; }
+    Floating grad_tol() const { return this->tol(); }
+    // v of the last loop top
+    DVector pseudo_gradient() const { DVector v(this->x().size()); check(qn_solver_get_pseudo_gradient(this->handle(), v.data())); return v; }
+    Floating penalty() const { // h at x()
+        const DVector w = l1();
+        const DVector& x = this->x();
+        Floating h = 0.0;
+        for (size_t i = 0; i < x.size(); ++i) h += w[i] * std::fabs(x[i]);
+        return h;
+    }
+    Floating composite(const FuncEvalMultivariate& eval) const { return eval.f() + penalty(); }
+    size_t nonzeros() const { size_t c = 0; for (Floating v : this->x()) c += v != 0.0; return c; }
+    // the infinity norm of the pseudo-gradient at x() from an evaluation of the smooth part there: SpectralProximalGradient's measure without a box
+    Floating measure(const FuncEvalMultivariate& eval) const {
+        const DVector w = l1();
+        const DVector& x = this->x();
+        Floating acc = 0.0;
+        for (size_t i = 0; i < x.size(); ++i) {
+            const Floating g = eval.g()[i];
+            const Floating lo = x[i] > 0.0 ? g + w[i] : g - w[i], hi = x[i] < 0.0 ? g - w[i] : g + w[i];
+            acc = std::fmax(acc, std::fabs(lo > 0.0 ? lo : (hi < 0.0 ? hi : 0.0)));
+        }
+        return acc;
+    }
+    bool has_converged(const FuncEvalMultivariate& eval) const { return measure(eval) < this->tol(); }
+};
+
 // Nonlinear conjugate gradient: new(tol, x0).with_variant(NonlinearCG::Variant::HZ, powell_nu, restart_every); d+ = beta d - g+, one extra vector of
 // state on the GPU.  Restarts d = -g by Powell's test |g+.g| >= powell_nu g+.g+ (INFINITY: off), every restart_every iterations (0: never) and whenever
 // beta d - g+ would not descend.  UNBOUNDED ONLY; StrongWolfe (what FR, DY and HS+ assume) or BackTracking.  has_converged: ||g||_inf < tol.

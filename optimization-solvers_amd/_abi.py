@@ -20,6 +20,7 @@ LBFGS_MAX_M = 32
 NONLINEAR_CG = 13  # nonlinear conjugate gradient (unbounded only); no counterpart in the reference
 NEWTON_CG = 14  # truncated Newton on the log-sum-exp Hessian-vector product (unbounded only); no counterpart in the reference
 SPECTRAL_PROXIMAL_GRADIENT = 15  # L1-regularised SPG by soft-thresholding (SpaRSA); no counterpart in the reference
+OWLQN = 16  # orthant-wise L-BFGS for L1-regularised objectives (unbounded only); no counterpart in the reference
 CG_FR, CG_PR_PLUS, CG_HS_PLUS, CG_DY, CG_HZ = 0, 1, 2, 3, 4  # qn_solver_set_cg's variants
 PRECOND_NONE, PRECOND_JACOBI = 0, 1  # qn_solver_set_newton_cg_preconditioner's kinds
 UNIQUE_ID_BYTES = 128
@@ -78,6 +79,7 @@ PATH_CG = 2048
 PATH_EXACT = 4096
 PATH_NEWTON_CG = 8192
 PATH_PROX = 16384
+PATH_OWLQN = 32768
 
 
 # every symbol include/qn_hip.h declares: (name, restype, argtypes)
@@ -158,6 +160,7 @@ SYMBOLS = [
     ("qn_solver_spg_lambda", C.c_int, [C.c_void_p, dp, C.POINTER(C.c_int)]),
     ("qn_solver_set_l1", C.c_int, [C.c_void_p, dp, C.c_double]),
     ("qn_solver_get_l1", C.c_int, [C.c_void_p, dp]),
+    ("qn_solver_get_pseudo_gradient", C.c_int, [C.c_void_p, dp]),
     ("qn_solver_newton_factorisations", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t)]),
     ("qn_solver_set_lbfgs_memory", C.c_int, [C.c_void_p, C.c_size_t]),
     ("qn_solver_lbfgs_state", C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), dp, C.POINTER(C.c_size_t)]),

@@ -100,3 +100,6 @@ extern "C" const char* qn_status_string(int status) {
 // spectral proximal gradient (L1 by soft-thresholding) on the first-order family's machine: its direction, trial and decision kernels, behind every existing kernel
 #include "qn_vec_prox.hip.h"
 #include "qn_host_prox.hip.h"
+// orthant-wise L-BFGS (OWL-QN, L1 with curvature) on the same machine: its element-wise kernels, behind the prox pair whose penalty it shares
+#include "qn_vec_owlqn.hip.h"
+#include "qn_host_owlqn.hip.h"

@@ -29,7 +29,7 @@ static int lbfgs_set_unit_scaling(qn_solver* s, bool on) { // QN_OPT_LBFGS_UNIT_
 
 extern "C" int qn_solver_set_lbfgs_memory(qn_solver* s, size_t m) {
     if (!s) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
-    if (s->method != QN_LBFGS) return fail(QN_ERROR_INPUT_PARAMS, "the memory belongs to an L-BFGS solver");
+    if (s->method != QN_LBFGS && s->method != QN_OWLQN) return fail(QN_ERROR_INPUT_PARAMS, "the memory belongs to an L-BFGS or OWLQN solver");
     if (m < 1 || m > QN_LBFGS_MAX_M) return fail(QN_ERROR_INPUT_PARAMS, "L-BFGS: the memory m must be 1 .. 32 (the small solves run in one workgroup)");
     QnVecCtl* h = s->hvctl;
     h->lb_m = (int32_t)m;
@@ -39,7 +39,7 @@ extern "C" int qn_solver_set_lbfgs_memory(qn_solver* s, size_t m) {
 
 extern "C" int qn_solver_lbfgs_state(qn_solver* s, size_t* m, size_t* stored, double* gamma, size_t* resets) {
     if (!s) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
-    if (s->method != QN_LBFGS) return fail(QN_ERROR_INPUT_PARAMS, "the memory belongs to an L-BFGS solver");
+    if (s->method != QN_LBFGS && s->method != QN_OWLQN) return fail(QN_ERROR_INPUT_PARAMS, "the memory belongs to an L-BFGS or OWLQN solver");
     const QnVecCtl* h = s->hvctl;
     if (m) *m = (size_t)h->lb_m;
     if (stored) *stored = (size_t)h->lb_kmem;

@@ -11,7 +11,7 @@ static int prox_state_alloc(qn_solver* s) { // h0, Delta, F_k of the iteration b
 
 extern "C" int qn_solver_set_l1(qn_solver* s, const double* l1_host, double l1_scalar) {
     if (!s) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
-    if (s->method != QN_SPECTRAL_PROXIMAL_GRADIENT) return fail(QN_ERROR_INPUT_PARAMS, "the L1 penalty belongs to a SpectralProximalGradient solver");
+    if (s->method != QN_SPECTRAL_PROXIMAL_GRADIENT && s->method != QN_OWLQN) return fail(QN_ERROR_INPUT_PARAMS, "the L1 penalty belongs to a SpectralProximalGradient or OWLQN solver");
     if (l1_host) {
         for (size_t i = 0; i < s->n; ++i)
             if (!(l1_host[i] >= 0.0) || !std::isfinite(l1_host[i])) return fail(QN_ERROR_INPUT_PARAMS, "l1: every entry must be finite and not negative");
@@ -32,13 +32,14 @@ extern "C" int qn_solver_set_l1(qn_solver* s, const double* l1_host, double l1_s
         s->px_l1_vec = false;
     }
     // the ring's values belong to the old penalty; lambda, x and the memo (the smooth f and its gradient) do not
-    if (s->hvctl) s->hvctl->ring_len = 0;
+    // (QN_OWLQN keeps no such ring, and its pairs are differences of the smooth gradient: the memory is not touched)
+    if (s->hvctl && s->method == QN_SPECTRAL_PROXIMAL_GRADIENT) s->hvctl->ring_len = 0;
     return QN_OK;
 }
 
 extern "C" int qn_solver_get_l1(qn_solver* s, double* l1_host) {
     if (!s || !l1_host) return fail(QN_ERROR_INPUT_PARAMS, "null argument");
-    if (s->method != QN_SPECTRAL_PROXIMAL_GRADIENT) return fail(QN_ERROR_INPUT_PARAMS, "the L1 penalty belongs to a SpectralProximalGradient solver");
+    if (s->method != QN_SPECTRAL_PROXIMAL_GRADIENT && s->method != QN_OWLQN) return fail(QN_ERROR_INPUT_PARAMS, "the L1 penalty belongs to a SpectralProximalGradient or OWLQN solver");
     for (size_t i = 0; i < s->n; ++i) l1_host[i] = s->px_l1_vec ? s->px_l1_host[i] : s->px_l1_scalar;
     return QN_OK;
 }

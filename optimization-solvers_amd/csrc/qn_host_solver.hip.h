@@ -119,6 +119,7 @@ struct qn_solver {
     // QN_SPECTRAL_PROXIMAL_GRADIENT (qn_vec_prox.hip.h): l1 per entry, [n_pad] zero-padded (once a vector was set) with its host copy, or the scalar;
     // h0, Delta, F_k of the iteration being searched, [4]
     DevBuf<double> px_l1, px_state; std::vector<double> px_l1_host; double px_l1_scalar = 0.0; bool px_l1_vec = false;
+    DevBuf<double> ow_v; // QN_OWLQN (qn_vec_owlqn.hip.h): the pseudo-gradient of the last loop top, [n_pad]; its penalty is px_l1, its scalars px_state, its memory lb_*
     DevBuf<double> ex_q, ex_c; // QN_LS_EXACT_QUADRATIC (qn_vec_exact.hip.h): q = Q d of the last curvature pass, [n_pad]; d'Qd of a dense quadratic, [2]
     DevBuf<double> bounds_block; // lb, ub (solver), llb, lub (bounded line search): 4 n_pad vectors
     int bounded = 0;
@@ -527,7 +528,7 @@ extern "C" int qn_solver_set_option(qn_solver* s, int option, int value) {
     case QN_OPT_HPASS_STORE_SKIP: s->hpass_skip = on ? 1 : 0; return QN_OK; // (read once per call: plan_s2_args)
     case QN_OPT_PNEWTON_REUSE_FACTOR: s->pn_reuse = on ? 1 : 0; s->pn_factor_serial = 0; return QN_OK;
     case QN_OPT_LBFGS_UNIT_SCALING:
-        if (s->method != QN_LBFGS) return fail(QN_ERROR_INPUT_PARAMS, "unit scaling belongs to an L-BFGS solver");
+        if (s->method != QN_LBFGS && s->method != QN_OWLQN) return fail(QN_ERROR_INPUT_PARAMS, "unit scaling belongs to an L-BFGS or OWLQN solver");
         return lbfgs_set_unit_scaling(s, on);
     case QN_OPT_PNORM_NONTEMPORAL:
         if (value < -1 || value > 1) return fail(QN_ERROR_INPUT_PARAMS, "non-temporal loads of inverse_p: 0 (plain), 1 (non-temporal) or -1 (by size)");

@@ -31,7 +31,7 @@ extern "C" int qn_strong_wolfe_with_xtol(qn_linesearch* ls, double xtol) {
 
 static bool pn_method(int method) { return method == QN_PROJECTED_NEWTON || method == QN_SPECTRAL_PROJECTED_NEWTON; }
 static bool spectral_method(int method) { return method == QN_SPG || method == QN_SPECTRAL_PROJECTED_NEWTON || method == QN_SPECTRAL_PROXIMAL_GRADIENT; }
-static bool vec_method(int method) { return method == QN_SPG || method == QN_PROJECTED_GRADIENT || pn_method(method) || method == QN_LBFGS || method == QN_NONLINEAR_CG || method == QN_NEWTON_CG || method == QN_SPECTRAL_PROXIMAL_GRADIENT; }
+static bool vec_method(int method) { return method == QN_SPG || method == QN_PROJECTED_GRADIENT || pn_method(method) || method == QN_LBFGS || method == QN_NONLINEAR_CG || method == QN_NEWTON_CG || method == QN_SPECTRAL_PROXIMAL_GRADIENT || method == QN_OWLQN; }
 struct VecRun;
 static int lbfgs_state_alloc(qn_solver* s); // QN_LBFGS: qn_host_lbfgs.hip.h
 static int lbfgs_enqueue_direction(VecRun& r, bool wolfe_clip);
@@ -51,6 +51,12 @@ static int prox_check(const qn_solver* s, const qn_linesearch* ls, int ls_only);
 static int prox_enqueue_direction(VecRun& r);
 static int prox_enqueue_trial(VecRun& r);
 static int prox_enqueue_decide(VecRun& r);
+static int owl_state_alloc(qn_solver* s); // QN_OWLQN: qn_host_owlqn.hip.h
+static int owl_check(const qn_solver* s, const qn_linesearch* ls, int ls_only);
+static int owl_enqueue_direction(VecRun& r);
+static int owl_enqueue_trial(VecRun& r);
+static int owl_enqueue_decide(VecRun& r);
+static int owl_enqueue_accept(VecRun& r);
 static int vec_grid(size_t np) { // a function of n alone: four 16-byte accesses per thread until 4 workgroups per CU are out
     const size_t per = (size_t)QN_VEC_TPB * 2 * 4;
     return (int)std::min<size_t>(QN_VEC_MAXG, std::max<size_t>(1, (np + per - 1) / per));
@@ -69,6 +75,7 @@ static int vec_state_alloc(qn_solver* s) {
     if (s->method == QN_NONLINEAR_CG) QNCHK(cg_state_alloc(s));
     if (s->method == QN_NEWTON_CG) QNCHK(tn_state_alloc(s));
     if (s->method == QN_SPECTRAL_PROXIMAL_GRADIENT) QNCHK(prox_state_alloc(s));
+    if (s->method == QN_OWLQN) QNCHK(owl_state_alloc(s));
     return QN_OK;
 }
 static void vec_state_reset(qn_solver* s) { // back to the state right after ::new: no lambda, an empty f_previous, no memo
@@ -135,6 +142,7 @@ static int vec_compute_direction(qn_solver* s, const double* g_host, double* d_h
     if (s->method == QN_NONLINEAR_CG) return fail(QN_ERROR_INPUT_PARAMS, "the NonlinearCG direction is formed from the device-resident previous direction: use qn_minimize");
     if (s->method == QN_NEWTON_CG) return fail(QN_ERROR_INPUT_PARAMS, "the NewtonCG direction is formed by an inner loop on the device objective: use qn_minimize");
     if (s->method == QN_SPECTRAL_PROXIMAL_GRADIENT) return fail(QN_ERROR_INPUT_PARAMS, "the SpectralProximalGradient direction is formed by the device's proximal map: use qn_minimize");
+    if (s->method == QN_OWLQN) return fail(QN_ERROR_INPUT_PARAMS, "the OWLQN direction is formed from the device-resident memory and pseudo-gradient: use qn_minimize");
     if (s->method == QN_SPG && !s->hvctl->has_lambda) return fail(QN_ERROR_INPUT_PARAMS, "lambda0 needs the oracle: the first qn_minimize evaluates it");
     std::vector<double> x(n), lb(n), ub(n);
     QNCHK(qn_solver_get_x(s, x.data()));
@@ -265,10 +273,11 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     HIPCHK(hipSetDevice(c->device));
     if (c->world > 1) return fail(QN_ERROR_INPUT_PARAMS, "SPG / projected gradient / projected Newton / L-BFGS / nonlinear CG run on one rank");
     const bool pn = pn_method(s->method), lbfgs = s->method == QN_LBFGS, cg = s->method == QN_NONLINEAR_CG, tn = s->method == QN_NEWTON_CG;
-    const bool prox = s->method == QN_SPECTRAL_PROXIMAL_GRADIENT;
+    const bool prox = s->method == QN_SPECTRAL_PROXIMAL_GRADIENT, owl = s->method == QN_OWLQN;
     VecRun r{s, o, nullptr, {}};
     QNCHK(check_oracle(c, s->n, o, &r.obj));
     if (prox) QNCHK(prox_check(s, ls, ls_only)); // GLLQuadratic or BackTracking, whole runs only
+    if (owl) QNCHK(owl_check(s, ls, ls_only)); // BackTracking, whole runs, no box
     if (tn) QNCHK(tn_check(s, ls, r.obj, ls_only)); // unbounded, log-sum-exp, BackTracking or StrongWolfe without a box
     const bool exact = ls->kind == QN_LS_EXACT_QUADRATIC;
     if (exact) { // the exact step -g.d / d'Qd: a device quadratic under the four O(n) methods (qn_vec_exact.hip.h)
@@ -385,7 +394,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
             if (tn && h->tn_precond) s->stats.obj_bytes += tn_weights * ops->diag_bytes(r.obj); // (one diagonal pass behind every weights pass)
         }
         stats_add_totals(s); // (no update passes, one rank: total_h_* and total_xchg_* stay)
-        s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u) | (lbfgs ? QN_PATH_LBFGS : 0u) | (cg ? QN_PATH_CG : 0u) | (exact ? QN_PATH_EXACT : 0u) | (tn ? QN_PATH_NEWTON_CG : 0u) | (prox ? QN_PATH_PROX : 0u);
+        s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u) | (lbfgs ? QN_PATH_LBFGS : 0u) | (cg ? QN_PATH_CG : 0u) | (exact ? QN_PATH_EXACT : 0u) | (tn ? QN_PATH_NEWTON_CG : 0u) | (prox ? QN_PATH_PROX : 0u) | (owl ? (QN_PATH_LBFGS | QN_PATH_OWLQN) : 0u);
         if (s->method == QN_PROJECTED_NEWTON) { // s_norm() / y_norm() (projected_newton.rs:10-11) through the getters every solver answers
             s->hctl->has_s_norm = h->has_sy; s->hctl->has_y_norm = h->has_sy; s->hctl->s_norm = h->s_norm; s->hctl->y_norm = h->y_norm;
         }
@@ -414,6 +423,8 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         if (ph == QN_VP_EVAL_X || ph == QN_VP_DIR || ph == QN_VP_LS_ONLY) {
             if (prox) { // prox_dir_kernel and prox_top_kernel in their places (qn_vec_prox.hip.h)
                 QNCHK(prox_enqueue_direction(r));
+            } else if (owl) { // the pseudo-gradient and the loop top, z = H_k v by L-BFGS's three kernels, the aligned direction and rule 3's test (qn_vec_owlqn.hip.h)
+                QNCHK(owl_enqueue_direction(r));
             } else {
                 VEC_LAUNCH(vec_dir_kernel, G);
                 if (wolfe_boxed && !pn && !lbfgs) VEC_LAUNCH(wolfe_clip_kernel, G); // (those two form the direction the search follows in phase QN_VP_NSOLVE: the clip runs there)
@@ -477,6 +488,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
             continue;
         }
         if (prox) QNCHK(prox_enqueue_trial(r)); // xt and the shares of h(xt)
+        else if (owl) QNCHK(owl_enqueue_trial(r)); // the projected xt and the shares of h(xt) and v.(xt - x)
         else VEC_LAUNCH(vec_trial_kernel, G);
         if (host_oracle) { // a host closure is called only for a point the machine asked for
             QNCHK(vec_peek(r, true));
@@ -490,11 +502,14 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
             VEC_LAUNCH(wolfe_decide_kernel, 1);
         } else if (prox) {
             QNCHK(prox_enqueue_decide(r)); // the same two branches on the composite values
+        } else if (owl) {
+            QNCHK(owl_enqueue_decide(r)); // Andrew and Gao's condition on the composite values
         } else {
             VEC_LAUNCH(vec_decide_kernel, 1);
         }
         if (lbfgs) QNCHK(lbfgs_enqueue_accept(r));
         else if (cg) QNCHK(cg_enqueue_accept(r));
+        else if (owl) QNCHK(owl_enqueue_accept(r)); // x_next = xt, the projected point
         else VEC_LAUNCH(vec_accept_kernel, G);
         VEC_LAUNCH(vec_post_kernel, 1);
         QNCHK(vec_peek(r, false));
@@ -511,6 +526,8 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     if (status == QN_ABNORMAL_TERMINATION && h->w_err) // dcsrch's START errors; the loop top ran, x is x_k
         return fail(QN_ABNORMAL_TERMINATION, h->w_err == 1 ? "StrongWolfe: not a descent direction (g.d >= 0 at the start of the search); x is left at x_k"
                                                            : "StrongWolfe: not a descent direction the search can follow (the box leaves stpmax < stpmin); x is left at x_k");
+    if (status == QN_ABNORMAL_TERMINATION && owl) // rule 3 is the only one that ends a run so: the loop top ran, x is x_k
+        return fail(QN_ABNORMAL_TERMINATION, "OWLQN: not a descent direction (v.d is not < 0 after the alignment); x is left at x_k");
     if (status == QN_ABNORMAL_TERMINATION && h->ex_err) // the loop top ran, x is x_k
         return fail(QN_ABNORMAL_TERMINATION, h->ex_err == 1 ? "ExactQuadratic: not a descent direction (g.d >= 0 at the start of the search); x is left at x_k"
                                                             : "ExactQuadratic: non-positive curvature along the direction (d'Qd is not positive and finite); x is left at x_k");

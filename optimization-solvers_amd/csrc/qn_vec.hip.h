@@ -47,9 +47,9 @@ enum QnVecPhase : int32_t {
 __device__ __forceinline__ bool vec_newton(int method) { return method == QN_PROJECTED_NEWTON || method == QN_SPECTRAL_PROJECTED_NEWTON; }
 __device__ __forceinline__ bool vec_spectral(int method) { return method == QN_SPG || method == QN_SPECTRAL_PROJECTED_NEWTON || method == QN_SPECTRAL_PROXIMAL_GRADIENT; }
 // update_next_iterate calls the oracle at the accepted point, for y (spg.rs:130, spn.rs:135, projected_newton.rs:134)
-__device__ __forceinline__ bool vec_needs_y(int method) { return vec_spectral(method) || method == QN_PROJECTED_NEWTON || method == QN_LBFGS || method == QN_NONLINEAR_CG; }
+__device__ __forceinline__ bool vec_needs_y(int method) { return vec_spectral(method) || method == QN_PROJECTED_NEWTON || method == QN_LBFGS || method == QN_NONLINEAR_CG || method == QN_OWLQN; }
 // the direction is P(x - z) - x with a z that arrives from outside this file, in phase QN_VP_NSOLVE (QN_NONLINEAR_CG: the direction itself does)
-__device__ __forceinline__ bool vec_nsolve(int method) { return vec_newton(method) || method == QN_LBFGS || method == QN_NONLINEAR_CG || method == QN_NEWTON_CG; }
+__device__ __forceinline__ bool vec_nsolve(int method) { return vec_newton(method) || method == QN_LBFGS || method == QN_NONLINEAR_CG || method == QN_NEWTON_CG || method == QN_OWLQN; }
 
 struct QnVecCtl {
     // ---- configuration (host, per call) ----
@@ -434,7 +434,7 @@ __global__ __launch_bounds__(QN_VEC_TPB) void vec_post_kernel(const QnVecArgs a)
     const double sy = vec_sum_parts(a.part, 2, a.G, lds);
     const double ss = vec_sum_parts(a.part, 3, a.G, lds);
     const bool second = vec_newton(c->method) && c->gt_valid;
-    const bool lbfgs = c->method == QN_LBFGS; // (lbfgs_accept_kernel ran in vec_accept_kernel's place)
+    const bool lbfgs = c->method == QN_LBFGS || c->method == QN_OWLQN; // (lbfgs_accept_kernel, or owl_accept_kernel, ran in vec_accept_kernel's place)
     double pgn = 0.0, yy = 0.0;
     if (second) {
         pgn = vec_max_parts(a.part, 4, a.G, lds);

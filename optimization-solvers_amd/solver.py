@@ -1588,6 +1588,60 @@ class LBFGS(ProjectedLBFGS):
         return cls(tol, x0, m, ctx, memoize)
 
 
+class OWLQN(_SolverBase):
+    """Orthant-wise limited-memory quasi-Newton (Andrew and Gao 2007): min f(x) + sum_j l1_j |x_j|, unbounded.  `new(tol, x0, l1, m=5)`; L-BFGS's
+    memory and compact-form direction applied to the pseudo-gradient v, the direction aligned with -v, every trial point projected onto the orthant
+    of x (of -v where x is 0), `BackTracking` on the composite value.  `l1`: one scalar or one value per entry, >= 0 and finite; an entry with
+    l1 == 0 is smooth.  Entries the projection switches off are exactly 0.0 in x().  The pairs are differences of the smooth gradient: `set_l1`
+    between two minimize calls keeps them, x and the memoised evaluation (the regularisation path)."""
+    METHOD = A.OWLQN
+
+    def __init__(self, tol, x0, l1, m=5, ctx=None, memoize=None):
+        super().__init__(tol, x0, ctx)
+        self.memoize = memoize
+        self.set_l1(l1)
+        if m != 5:
+            self.set_memory(m)
+
+    @classmethod
+    def new(cls, tol, x0, l1, m=5, ctx=None, memoize=None):
+        return cls(tol, x0, l1, m, ctx, memoize)
+
+    set_l1 = SpectralProximalGradient.set_l1
+    l1 = SpectralProximalGradient.l1
+    penalty = SpectralProximalGradient.penalty
+    composite = SpectralProximalGradient.composite
+    nonzeros = SpectralProximalGradient.nonzeros
+    approx_inv_hessian = SpectralProximalGradient.approx_inv_hessian
+    set_approx_inv_hessian = SpectralProximalGradient.set_approx_inv_hessian
+    set_memory = ProjectedLBFGS.set_memory
+    _lbfgs_state = ProjectedLBFGS._lbfgs_state
+    memory = ProjectedLBFGS.memory
+    stored_pairs = ProjectedLBFGS.stored_pairs
+    gamma = ProjectedLBFGS.gamma
+    resets = ProjectedLBFGS.resets
+
+    def grad_tol(self):
+        return self.tol()
+
+    def pseudo_gradient(self):
+        """v of the last loop top (inside the callback: v_k of the iteration just reported)"""
+        out = np.empty(self.n)
+        _check(A.lib().qn_solver_get_pseudo_gradient(self.h, _dp(out)))
+        return out
+
+    def measure(self, eval_x_k):
+        """the pseudo-gradient at x() from an evaluation of the smooth part there: SpectralProximalGradient's measure without a box"""
+        g = np.asarray(eval_x_k.g() if isinstance(eval_x_k, FuncEvalMultivariate) else eval_x_k[1], dtype=np.float64)
+        x, l1 = self.x(), self.l1
+        lo = np.where(x > 0.0, g + l1, g - l1)
+        hi = np.where(x < 0.0, g - l1, g + l1)
+        return np.where(lo > 0.0, lo, np.where(hi < 0.0, hi, 0.0))
+
+    def has_converged(self, eval_x_k):
+        return float(np.max(np.abs(self.measure(eval_x_k)))) < self.tol()
+
+
 class NonlinearCG(_SolverBase):
     """Nonlinear conjugate gradient: `new(tol, x0, variant="pr+", powell_nu=0.2, restart_every=0)`; d+ = beta d - g+ with beta by the variant --
     "fr" (Fletcher-Reeves), "pr+" (Polak-Ribiere+), "hs+" (Hestenes-Stiefel+), "dy" (Dai-Yuan), "hz" (Hager-Zhang) -- and restarts d = -g by

@@ -43,6 +43,7 @@ pub const QN_LBFGS_MAX_M: usize = 32;
 pub const QN_NONLINEAR_CG: c_int = 13;
 pub const QN_NEWTON_CG: c_int = 14;
 pub const QN_SPECTRAL_PROXIMAL_GRADIENT: c_int = 15;
+pub const QN_OWLQN: c_int = 16;
 pub const QN_CG_FR: c_int = 0;
 pub const QN_CG_PR_PLUS: c_int = 1;
 pub const QN_CG_HS_PLUS: c_int = 2;
@@ -99,6 +100,7 @@ pub const QN_PATH_CG: u32 = 2048;
 pub const QN_PATH_EXACT: u32 = 4096;
 pub const QN_PATH_NEWTON_CG: u32 = 8192;
 pub const QN_PATH_PROX: u32 = 16384;
+pub const QN_PATH_OWLQN: u32 = 32768;
 
 #[repr(C)] pub struct qn_context { _p: [u8; 0] }
 #[repr(C)] pub struct qn_solver { _p: [u8; 0] }
@@ -278,6 +280,7 @@ extern "C" {
     pub fn qn_solver_spg_lambda(s: *mut qn_solver, out: *mut f64, is_some: *mut c_int) -> c_int;
     pub fn qn_solver_set_l1(s: *mut qn_solver, l1_host: *const f64, l1_scalar: f64) -> c_int;
     pub fn qn_solver_get_l1(s: *mut qn_solver, l1_host: *mut f64) -> c_int;
+    pub fn qn_solver_get_pseudo_gradient(s: *mut qn_solver, out_host: *mut f64) -> c_int;
     pub fn qn_solver_newton_factorisations(s: *mut qn_solver, out: *mut usize) -> c_int;
     pub fn qn_solver_set_lbfgs_memory(s: *mut qn_solver, m: usize) -> c_int;
     pub fn qn_solver_lbfgs_state(s: *mut qn_solver, m: *mut usize, stored: *mut usize, gamma: *mut f64, resets: *mut usize) -> c_int;

@@ -843,6 +843,10 @@ macro_rules! gpu_solver {
                     // the direction needs the Cholesky solve and (spn.rs) the device-resident lambda: `minimize_on_device` / `minimize_objective`
                     return Err(SolverError::ErrorInputParams);
                 }
+                if $method == QN_OWLQN {
+                    // the accepted point is the trial kernel's orthant projection, never x + t d, and the pairs live on the device: `minimize_on_device` / `minimize_objective`
+                    return Err(SolverError::ErrorInputParams);
+                }
                 if $method == QN_SPG || $method == QN_SPECTRAL_PROXIMAL_GRADIENT {
                     // spg.rs:126-143 updates lambda here; it lives on the device and only qn_minimize updates it.  Refuse rather than run
                     // a fixed-lambda projected gradient under SPG's name: use `minimize_on_device` / `minimize_objective`.
@@ -986,6 +990,55 @@ macro_rules! lbfgs_memory {
 }
 lbfgs_memory!(GpuLbfgs);
 lbfgs_memory!(GpuProjectedLbfgs);
+
+gpu_solver!(
+    /// Orthant-wise limited-memory quasi-Newton (OWL-QN, Andrew and Gao 2007): min f(x) + sum_j l1_j |x_j|, UNBOUNDED ONLY.
+    /// `new(tol, x0).with_l1(&l1)` or `.with_l1_scalar(v)`, `.with_memory(m)`; `GpuLbfgs`'s memory and direction kernels applied to the
+    /// pseudo-gradient, the direction aligned with it, every trial point projected onto the orthant of x (QN_PATH_LBFGS | QN_PATH_OWLQN);
+    /// `GpuBackTracking` only, on the composite value.  The weights the projection switches off are exactly 0.0.  The pairs are differences of
+    /// the smooth gradient: `set_l1` between two minimize calls keeps them, x and the memoised evaluation.  Drive it with
+    /// `minimize_on_device` / `minimize_objective`: `update_next_iterate` returns `ErrorInputParams`.
+    GpuOwlqn, QN_OWLQN, false
+);
+lbfgs_memory!(GpuOwlqn);
+
+impl GpuOwlqn {
+    /// one value per entry, each finite and >= 0; an entry with 0 is smooth
+    pub fn with_l1(mut self, l1: &DVector<Floating>) -> Self {
+        self.set_l1(l1);
+        self
+    }
+    pub fn with_l1_scalar(mut self, l1: Floating) -> Self {
+        self.set_l1_scalar(l1);
+        self
+    }
+    /// between two minimize calls (the regularisation path): the pairs, x and the memoised evaluation are kept
+    pub fn set_l1(&mut self, l1: &DVector<Floating>) {
+        assert_eq!(l1.len(), self.core.x.len());
+        assert_eq!(unsafe { qn_solver_set_l1(self.core.h, l1.as_ptr(), 0.0) }, QN_OK, "{}", last_error());
+    }
+    pub fn set_l1_scalar(&mut self, l1: Floating) {
+        assert_eq!(unsafe { qn_solver_set_l1(self.core.h, std::ptr::null(), l1) }, QN_OK, "{}", last_error());
+    }
+    pub fn l1(&self) -> DVector<Floating> {
+        let mut v = DVector::zeros(self.core.x.len());
+        assert_eq!(unsafe { qn_solver_get_l1(self.core.h, v.as_mut_ptr()) }, QN_OK, "{}", last_error());
+        v
+    }
+    /// v of the last loop top
+    pub fn pseudo_gradient(&self) -> DVector<Floating> {
+        let mut v = DVector::zeros(self.core.x.len());
+        assert_eq!(unsafe { qn_solver_get_pseudo_gradient(self.core.h, v.as_mut_ptr()) }, QN_OK, "{}", last_error());
+        v
+    }
+    /// h at x()
+    pub fn penalty(&self) -> Floating {
+        self.l1().iter().zip(self.core.x.iter()).map(|(w, x)| w * x.abs()).sum()
+    }
+    pub fn nonzeros(&self) -> usize {
+        self.core.x.iter().filter(|v| **v != 0.0).count()
+    }
+}
 
 gpu_solver!(
     /// Nonlinear conjugate gradient: `new(tol, x0).with_variant(CgVariant::HagerZhang, 0.2, 0)`; d+ = beta d - g+ with one extra vector of state on
