@@ -1,5 +1,5 @@
-"""The replay of a dense quasi-Newton run (DFP, BFGS, SR1; free or in a box) from its own recorded iterates in extended precision: what
-tests/lse_eval_cases.py (the log-sum-exp objective) and tests/quad_replay_cases.py (device quadratics) share.  Test infrastructure: the product does
+"""The replay of a dense quasi-Newton run (DFP, BFGS, SR1, Broyden; free or in a box) from its own recorded iterates in extended precision: what
+tests/lse_eval_cases.py (the log-sum-exp objective), tests/quad_replay_cases.py (device quadratics) and tests/broyden_replay_cases.py share.  Test infrastructure: the product does
 not import this file.
 
 A TRUTH is any object with f, g (np.longdouble) at a point and the bounds bf, bg (float64) a float64 evaluation of that objective must meet, plus
@@ -15,6 +15,26 @@ belongs to and derives every half-width below; what this file adds to it:
   c_su = -c.  The denominator, whether the device forms it as s'y - y'u or as (s - u)'y, is off by at most dys + dyu (the two inner products' own
   bounds, each a sum of magnitudes) plus the subtraction's rounding, hence c by _inv_bound(s'y - y'u, dys + dyu + 2 eps |s'y - y'u|).  An update
   that cannot be bounded makes the later direction checks and the H check `skipped`.
+
+  BROYDEN (broyden.rs:115-118).  u = H y, a = s - u, w = H' s (a row vector times H: the COLUMN sums), c = 1 / s'y -- the denominator as the
+  reference writes it, not s'Hy -- and H+ = H + c a w': one term (c, a, w), not symmetric, so `times_t` forms H' v (h0' in row chunks plus the
+  terms with p and q exchanged).  s = fl(x+ - x) is the device's own, bit for bit.  With the device's H off by at most DH entry by entry:
+      du   as for the other methods;
+      dw = DH' |s| + (n + 4) eps Habs' |s|            (a column sum of n products, bracketed anyhow: per-lane chains, four waves, the tile rows);
+      da = du + eps (|s| + |u| + du)                  (one subtraction of the computed u);
+      dc = _inv_bound(s'y, dys)                       (dys the inner product's own bound, as for DFP's 1 / s'y).
+  Habs grows by |c| |a| |w|', and every factor of c a w' moved by its bound, written out as non-negative terms:
+      DH+ = DH + dc (|a| + da)(|w| + dw)' + |c| (da |w|' + |a| dw' + da dw') + 8 eps Habs+.
+  The applied update h + c (a_i w_j) is three roundings, each of a quantity Habs+ bounds: 3 eps Habs+ at first order, inside the 8.
+  THE LAZY DIRECTION (qn_ctl_step.hip.h, QN_ST_AFTER_U) is another bracketing of H+ g+: d+ = -(v + c (a (w . g+))) with v = H g+ from the
+  same pass.  v is held by the row sum's bound with |H| and DH; w . g+ is off by (|w| + dw) . bg + dw . |g| + (n + 2) eps (|w| + dw) . (|g| + bg);
+  c, a move by dc, da; three products and one addition round once each.  Collected:
+      |d+ + H+ g+| <= Habs+ bg + (n + 4) eps Habs+ |g| + [DH + dc (..)(..)' + |c| (..)] (|g| + bg) + 4 eps Habs+ |g|,
+  which is `apply`'s bound with DH+ (the bracket is DH+ less its 8 eps Habs+, of which the four roundings take half) PROVIDED the sum's term
+  (n + 4) eps |H| |g| is taken with Habs+ = |H| + |c| |a| |w|' in the place of |H+|: the magnitudes of the two addends, which cancellation
+  between H and c a w' can leave far above |H + c a w'|.  The dense |H+| the other methods use does not cover that, so for this method
+  `apply` takes Habs (>= |H_k| entry by entry, and what either bracketing sums in magnitude).  `symmetric` is never set for it; the caller
+  asserts instead that the matrix read back is clearly NOT symmetric, max |H - H'| far above `Report.dh_max` = max DH.
 
   A BOX (bfgs_b.rs compute_direction / update_next_iterate).  d = P(x - H g) - x and x+ = x + t d.  Projection onto a box is 1-Lipschitz entry by
   entry, so entry j of x_{k+1} - x_k is held to t (clip(x_j - (H_k g_k)_j, lb_j, ub_j) - x_j) with the half-width of the free step plus
@@ -81,6 +101,7 @@ class Report:
     def __init__(self, name, kind="lse"):
         self.name, self.kind = name, kind
         self.rows = []  # (iteration, check, ratio, asserted)
+        self.dh_max = None  # max DH at the segment's end, where the H check ran
 
     def add(self, k, check, ratio, asserted=True):
         self.rows.append((k, check, float(ratio), bool(asserted)))
@@ -132,6 +153,19 @@ class InverseHessian:
             out = out + (coef * np.dot(q, v)) * p
         return out
 
+    def times_t(self, v):
+        """H_k' v: h0' in row chunks (row i of h0 scaled by v_i, summed over the chunk), plus the terms with p and q exchanged"""
+        vl = v.astype(LD)
+        if self.h0 is None:
+            out = vl.copy()
+        else:
+            out = np.zeros(self.n, dtype=LD)
+            for i in range(0, self.n, ROWS):
+                out = out + vl[i:i + ROWS] @ self.h0[i:i + ROWS].astype(LD)
+        for coef, p, q in self.terms:
+            out = out + (coef * np.dot(p, vl)) * q
+        return out
+
     def dense_abs(self):
         h = np.eye(self.n) if self.h0 is None else self.h0.copy()
         for coef, p, q in self.terms:
@@ -155,7 +189,7 @@ class InverseHessian:
             return g, bg + (self.n + 4) * EPS * gabs
         if not self.bounded:
             return self.times(g), np.full(self.n, INF)
-        habs = self.dense_abs()
+        habs = self.habs if self.method == "broyden" else self.dense_abs()  # (Broyden: the lazy direction sums |H| + |c| |a| |w|', the docstring)
         return self.times(g), (habs @ bg + (self.n + 4) * EPS * (habs @ gabs) + self.dh @ (gabs + bg)) * (1.0 + 1e-9)
 
     def update(self, s, y, dy):
@@ -165,6 +199,8 @@ class InverseHessian:
         sl, sa, ya = s.astype(LD), np.abs(s), np.abs(y).astype(np.float64)
         u = self.times(y)
         ua = np.abs(u).astype(np.float64)
+        if self.method == "broyden":
+            return self._update_broyden(sl, sa, y, ya, dy, u, ua)
         ys, yu = np.dot(sl, y), np.dot(y, u)
         css, csu, cuu = coefficients(self.method, ys, yu)
         if self.method == "bfgs":
@@ -202,6 +238,28 @@ class InverseHessian:
         else:
             self.habs += acss * _outer(sa, sa) + acuu * _outer(ua, ua)
             dt = dcss * _outer(sa, sa) + acuu * (_outer(ua, du) + _outer(du, ua) + _outer(du, du)) + dcuu * _outer(ub, ub)
+        self.dh = (self.dh + dt + 8.0 * EPS * self.habs) * (1.0 + 1e-9)
+
+    def _update_broyden(self, sl, sa, y, ya, dy, u, ua):
+        """H+ = H + c a w', a = s - u, w = H' s, c = 1 / s'y (the docstring's paragraph BROYDEN)"""
+        n = self.n
+        w = self.times_t(sl)
+        a = sl - u
+        ys = np.dot(sl, y)
+        with np.errstate(divide="ignore"):  # (s'y = 0: dc below is not finite and the update counts as not bounded)
+            c = 1 / ys
+        self.terms.append((c, a, w))
+        aa, wa, ac = np.abs(a).astype(np.float64), np.abs(w).astype(np.float64), abs(float(c))
+        du = self.dh @ ya + self.habs @ dy + (n + 4) * EPS * (self.habs @ (ya + dy))
+        dw = self.dh.T @ sa + (n + 4) * EPS * (self.habs.T @ sa)
+        da = du + EPS * (sa + ua + du)
+        dys = float(sa @ dy) + (n + 2) * EPS * float(sa @ (ya + dy))
+        dc = _inv_bound(float(ys), dys)
+        if not math.isfinite(dc) or not np.all(np.isfinite(du)) or not np.all(np.isfinite(dw)):
+            self.bounded = False
+            return
+        self.habs += ac * _outer(aa, wa)
+        dt = dc * _outer(aa + da, wa + dw) + ac * (_outer(da, wa) + _outer(aa, dw) + _outer(da, dw))
         self.dh = (self.dh + dt + 8.0 * EPS * self.habs) * (1.0 + 1e-9)
 
     def check_dense(self, h_dev):
@@ -277,6 +335,7 @@ def replay(name, truth, x0, method, tr, xs, h0=None, box=None, h_dev=None, symme
         if symmetric and not np.array_equal(h_dev, np.asarray(h_dev).T):
             ratio, ok = INF, True
         rep.add(iters - 1, "H", ratio, asserted=ok)
+        rep.dh_max = float(np.max(hk.dh)) if hk.dh is not None and hk.bounded else (0.0 if hk.bounded else INF)
     return rep
 
 

@@ -3,7 +3,8 @@ of tests/broyden_cases.py.  Sizes: n = 2 (the one-workgroup path in the referenc
 (2 x 2 tiles, ragged edge: padding must stay zero), 384 (3 x 3 tiles: the second stage sums three row blocks), 1024 (8 x 8).
 
 Tolerances.  Iterate sequences: tests/broyden_cases.py (the window's recorded CPU order spread x 8, floor 16 ulp, relative to the compared array's
-largest magnitude -- fixed before any GPU run).  The single-update unit test: an element-wise a-priori bound, written out at `_update_bound`."""
+largest magnitude -- fixed before any GPU run).  The single-update unit test: an element-wise a-priori bound, written out at `_update_bound`, at the
+tile edges (n = 128, 129, 257 too) and on a matrix over twelve decades.  Whole runs entry by entry: tests/test_gpu_broyden_replay.py."""
 import os
 import subprocess
 
@@ -97,10 +98,27 @@ def _update_bound(h, s, y):
     return g * np.abs(h) + (4.0 + kappa) * g / abs(s @ y) * np.outer(A, W)
 
 
-@pytest.mark.parametrize("n", [2, 7, 130, 384])
+SINGLE_N = [2, 7, 128, 129, 130, 257, 384]  # 128: one exactly full tile; 129: the edge tile has one live column; 257: a ragged third tile
+
+
+@pytest.mark.parametrize("n", SINGLE_N)
 def test_single_update_on_a_non_symmetric_h(qn, n):
-    rng = np.random.default_rng(100 + n)
+    _single_update(qn, n, False)
+
+
+@pytest.mark.parametrize("n", SINGLE_N)
+def test_single_update_on_a_non_symmetric_h_over_twelve_decades(qn, n):
+    """the second matrix: D1 M D2 with D = diag(10^U(-3, 3)), where only an element-wise bound sees the small entries.  (The seeds 200 + n were
+    picked on the CPU: both discrimination margins below stand at 5e10 or more, the reference's own order at 2e-2 of the bound or less.)"""
+    _single_update(qn, n, True)
+
+
+def _single_update(qn, n, scaled):
+    rng = np.random.default_rng((200 if scaled else 100) + n)
     h = np.eye(n) + rng.standard_normal((n, n)) / np.sqrt(n)
+    if scaled:
+        d1, d2 = 10.0 ** rng.uniform(-3, 3, n), 10.0 ** rng.uniform(-3, 3, n)
+        h = (d1[:, None] * h) * d2[None, :]
     s, y = rng.standard_normal(n), rng.standard_normal(n)
     want = R.broyden_update(h, s, y, "factored", "fsum")
     bound = _update_bound(h, s, y)
@@ -120,7 +138,7 @@ def test_single_update_on_a_non_symmetric_h(qn, n):
     b.secant_update(s, y)
     got = b.approx_inv_hessian()
     ratio = float(np.max(np.abs(got - want) / bound))
-    print(f"n = {n}: max |H+ - restatement| / bound = {ratio:.3e}")
+    print(f"n = {n}{' scaled' if scaled else ''}: max |H+ - restatement| / bound = {ratio:.3e}")
     assert ratio <= 1.0
     assert b.s_norm() == pytest.approx(np.linalg.norm(s), rel=1e-14) and b.y_norm() == pytest.approx(np.linalg.norm(y), rel=1e-14)
     b.close()

@@ -77,13 +77,15 @@ def _ls(qn, lsname, n=None, bx=None):
 class Runner:
     """one solver driven call by call (quad_replay_cases.run_plan)"""
 
-    def __init__(self, qn, method, lsname, oracle, x0, total, bx=None, options=(), sync=None, ctx=None, all_ranks=False):
+    def __init__(self, qn, method, lsname, oracle, x0, total, bx=None, options=(), sync=None, ctx=None, all_ranks=False, memoize=None):
         self.qn, self.oracle, self.all_ranks = qn, oracle, all_ranks
         kw = {"ctx": ctx} if ctx is not None else {}
         if bx is None:
-            self.s = {"bfgs": qn.BFGS, "dfp": qn.DFP}[method](1e-10, x0, **kw)
+            self.s = {"bfgs": qn.BFGS, "dfp": qn.DFP, "broyden": qn.Broyden}[method](1e-10, x0, **kw)
         else:
-            self.s = {"bfgs": qn.BFGSB, "dfp": qn.DFPB, "sr1": qn.SR1B}[method].new(1e-10, x0, bx[0], bx[1])
+            self.s = {"bfgs": qn.BFGSB, "dfp": qn.DFPB, "sr1": qn.SR1B, "broyden": qn.BroydenB}[method].new(1e-10, x0, bx[0], bx[1])
+        if memoize is not None:  # (None: the solver's default for the oracle's kind)
+            self.s.memoize = memoize
         self.s.set_trace(total, with_x=True)
         for name, v in options:
             self.s.configure(name, v)
