@@ -377,6 +377,13 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
     s->pn_factorisations = 0;
     // the run's bookkeeping, also when a batch fails after some iterations (a failed Cholesky, a closure's error): k, the counters, the
     // path and s_norm / y_norm speak of this call, not of the one before
+    // s_norm() / y_norm() (projected_newton.rs:10-11) through the getters every solver answers: of the iteration just accepted, also inside
+    // the callback (ls_solver.rs:105-107 hands the callback the solver behind update_next_iterate)
+    auto publish_norms = [&]() {
+        if (s->method == QN_PROJECTED_NEWTON) {
+            s->hctl->has_s_norm = h->has_sy; s->hctl->has_y_norm = h->has_sy; s->hctl->s_norm = h->s_norm; s->hctl->y_norm = h->y_norm;
+        }
+    };
     auto epilogue = [&]() {
         s->hctl->k = h->k; s->hctl->n_iterations = h->n_iter; s->hctl->ls_result = h->ls_result;
         s->hctl->have_cur_eval = h->have_eval;
@@ -395,9 +402,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         }
         stats_add_totals(s); // (no update passes, one rank: total_h_* and total_xchg_* stay)
         s->stats.path = QN_PATH_VECTOR | (pn ? QN_PATH_PNEWTON : 0u) | (lbfgs ? QN_PATH_LBFGS : 0u) | (cg ? QN_PATH_CG : 0u) | (exact ? QN_PATH_EXACT : 0u) | (tn ? QN_PATH_NEWTON_CG : 0u) | (prox ? QN_PATH_PROX : 0u) | (owl ? (QN_PATH_LBFGS | QN_PATH_OWLQN) : 0u);
-        if (s->method == QN_PROJECTED_NEWTON) { // s_norm() / y_norm() (projected_newton.rs:10-11) through the getters every solver answers
-            s->hctl->has_s_norm = h->has_sy; s->hctl->has_y_norm = h->has_sy; s->hctl->s_norm = h->s_norm; s->hctl->y_norm = h->y_norm;
-        }
+        publish_norms();
     };
 
     while (!done) {
@@ -482,6 +487,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
             if (callback && h->k != k_seen) {
                 k_seen = h->k;
                 s->hctl->k = h->k; s->hctl->n_iterations = h->n_iter;
+                publish_norms();
                 callback(callback_user, s);
             }
             done = h->phase == QN_VP_DONE;
@@ -517,6 +523,7 @@ static int vec_minimize(qn_solver* s, qn_linesearch* ls, const qn_oracle* o, siz
         if (callback && h->k != k_seen) { // ls_solver.rs:105-107: after k += 1 (one iteration per batch at most)
             k_seen = h->k;
             s->hctl->k = h->k; s->hctl->n_iterations = h->n_iter;
+            publish_norms();
             callback(callback_user, s);
         }
         done = h->phase == QN_VP_DONE;

@@ -60,10 +60,12 @@ CHUNK = 1 << 15
 
 
 class Recorder:
-    """fn(x) -> (f, g) with every evaluation kept by the bytes of x: the replay uses the gradient the solver was handed and never re-evaluates"""
+    """fn(x) -> (f, g) with every evaluation kept by the bytes of x: the replay uses the gradient the solver was handed and never re-evaluates.
+    `order` is the sequence of evaluations, as keys; with keep_x the points themselves are kept beside it (tests/vec_replay.py reads both)."""
 
-    def __init__(self, fn):
+    def __init__(self, fn, keep_x=False):
         self.fn, self.seen, self.calls = fn, {}, 0
+        self.order, self.points = [], ({} if keep_x else None)
 
     @staticmethod
     def _key(x):
@@ -74,7 +76,11 @@ class Recorder:
         f, g = self.fn(x)
         g = np.array(g, dtype=np.float64)
         self.calls += 1
-        self.seen[self._key(x)] = (float(f), g)
+        k = self._key(x)
+        self.seen[k] = (float(f), g)
+        self.order.append(k)
+        if self.points is not None:
+            self.points[k] = x
         return float(f), g.copy()
 
     def grad(self, x, what=""):

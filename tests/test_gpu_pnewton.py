@@ -4,7 +4,8 @@ tol 1e-10) and the 1e-9 relative tolerance are licensed case by case by tests/te
 
 ProjectedNewton's s_norm / y_norm in the trace get bounds that follow from the 1e-9 on x: s = x_next - x differs by at most
 2e-9 max(1, ||x||), and y = g(x_next) - g(x) by at most L times that, L a bound on the Hessian's norm (its largest absolute row sum for the
-quadratic, ||A||_2^2 + mu for the log-sum-exp problem)."""
+quadratic, ||A||_2^2 + mu for the log-sum-exp problem).
+The exact check of these kernels is the step-by-step replay: tests/vec_replay.py, tests/test_gpu_vec_replay.py."""
 import ctypes as C
 
 import numpy as np

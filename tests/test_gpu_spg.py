@@ -1,7 +1,8 @@
 """GPU tests of the first-order family: QN_SPG / QN_PROJECTED_GRADIENT with GLLQuadratic and BackTrackingB through the device-wide vector
 kernels (csrc/qn_vec.hip.h), against the restatement tests/ref_spg.py.  The windows (30 iterations, kappa = 1e2) and the tolerance
 (1e-9 relative, as __graft_entry__.smoke() uses) are licensed case by case by the summation-order self-checks of tests/test_ref_spg.py:
-the quadratic cases by test_summation_order_self_check, the device closure's and the log-sum-exp problem by the two tests beside it."""
+the quadratic cases by test_summation_order_self_check, the device closure's and the log-sum-exp problem by the two tests beside it.
+The exact check of these kernels is the step-by-step replay: tests/vec_replay.py, tests/test_gpu_vec_replay.py."""
 import numpy as np
 import pytest
 
